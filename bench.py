@@ -14,7 +14,10 @@ JSON line and exits non-zero unless all N ranks finished.  torch.distributed (RC
 for the barrier and the max-over-ranks of the wall time; the sampling loop has no collective.
 Prompt shards are independent (rank r samples the global prompts [r*B, (r+1)*B)) => weak scaling.
 
-Prints ONE JSON line (see the driver contract) with extra objects:
+Prints ONE JSON line (see the driver contract).  A plain run sets up, warms up, times --steps steps, writes the last timed
+step's samples with --dump-outputs DIR (DIR/samples.npy, f32 [B, L, 3]; samples_rank<r>.npy per rank when N>1) and prints
+the line.  --full adds the secondary figures as extra objects (each takes runs of its own; `--no-<figure>` leaves one out):
+  work_per_sample_call, model_tflops — algorithmic FLOPs / bytes of one denoiser call and the model TFLOP/s of the timed steps
   roofline     — for the dominant kernel FUNCTION (launch labels grouped as rocprofv3 groups them): algorithmic FLOPs and
                  bytes per launch over the mean launch duration measured with HIP events on the launch stream (library
                  profile mode); `all_stroke_kernels` = the time-weighted figure over every fused stroke-side kernel
@@ -23,6 +26,7 @@ Prints ONE JSON line (see the driver contract) with extra objects:
   cpu_baseline — the oracle (CPU restatement of the reference, kind "port") timed on this box's host
                  cores on a bounded sample of the same workload (rank 0, N=1 only)
   fp32_mode    — the same workload through the library's fp32 parity mode (N=1 only)
+With --train, --full adds bf16_mode (the update with bf16 GEMM operands) and cpu_baseline (the oracle's forward + backward).
 """
 from __future__ import annotations
 
@@ -60,10 +64,16 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-profile", action="store_true")
     ap.add_argument("--no-fp32", action="store_true", help="skip the other-precision throughput figure (fp32_mode; bf16_mode with --train)")
-    ap.add_argument("--no-longseq", action="store_true", help="skip the configs[3] figure (longseq_mode: L=1000, T=1000, batch=32) in the default line")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the short configs[4] training-step figure (train_step) in the default line")
+    ap.add_argument("--no-longseq", action="store_true", help="skip the configs[3] figure (longseq_mode: L=1000, T=1000, batch=32) in the --full line")
+    ap.add_argument("--no-train-step", action="store_true", help="skip the short configs[4] training-step figure (train_step) in the --full line")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--streams", type=int, default=0, help="concurrent prompt sub-batches per GPU (0 = library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures (roofline / kernel profile, other precisions and depths, configs[3], "
+                         "the training step, CPU baselines); a plain run times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (sampling: samples.npy, f32 [B, L, 3]; "
+                         "--train: loss.npy); the inputs depend only on the arguments")
     # launcher / distributed plumbing rehearsal on CPU (tests/test_bench_launcher_cpu.py): gloo, no GPU, no library
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal on a box with fewer GPUs than ranks: rank r uses GPU r %% device_count, gloo instead of RCCL "
@@ -73,6 +83,8 @@ def parse_args(argv=None):
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--stub-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     a.precision = a.precision or ("fp32" if a.train else "bf16")
     a.batch = a.batch or (32 if a.train else 64)
     a.L = a.L or (480 if a.train else 488)
@@ -134,6 +146,26 @@ _JSON_OUT = None   # the rank's real stdout (worker() points fd 1 at stderr so t
 
 def emit(line: str):
     print(line, file=_JSON_OUT or sys.stdout, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d: str, arrays: dict, rank: int, world: int):
+    """--dump-outputs: every array the timed path returned in its last step as f32 `d/<name>.npy` (`<name>_rank<r>.npy` when
+    N>1: each rank writes its own prompt shard).  An array larger than the budget is written as a fixed, seeded sample of its
+    flattened elements (`<name>_sample_index.npy` holds the flat indices)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    budget = DUMP_LIMIT_BYTES // max(1, world * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, budget // 16, replace=False))
+            np.save(os.path.join(d, f"{name}_sample_index{suffix}.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, f"{name}{suffix}.npy"), a)
 
 
 def worker(args):
@@ -240,6 +272,8 @@ def worker(args):
         dist.all_gather(own, torch.tensor([dt_own], device=cdev, dtype=torch.float64))
         per_rank = [float(x.item()) for x in own]
     assert out is not None and bool(torch.isfinite(out).all()), "non-finite samples"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"samples": out}, rank, world)
 
     points = world * B * L * args.steps
     value = points / dt
@@ -269,7 +303,7 @@ def worker(args):
 
     if rank == 0:
         print(f"[bench] {value:.4g} stroke-points/s, {dt / args.steps * 1e3:.2f} ms/step", file=sys.stderr, flush=True)
-        if model is not None:
+        if model is not None and args.full:
             fl, by = model.work(L, Lt)
             res["work_per_sample_call"] = {"flops": fl, "block_boundary_bytes": by}
             res["model_tflops"] = fl * B * T * world * args.steps / dt / 1e12
@@ -347,6 +381,8 @@ def train_worker(args, dev, dist, rank, world):
         per_rank = [float(x.item()) for x in own]
     lv = [float(x[0]) for x in losses]
     assert all(np.isfinite(lv)), "non-finite loss"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": losses[-1]}, rank, world)
     value = world * B * args.steps / dt
     gemm_tflops = model.last_gemm_flops * args.steps / dt_own / 1e12
     res = {"metric": "training samples/sec (forward + loss + backward + grad all-reduce + clip + Adam; L=480)", "value": value,
@@ -381,7 +417,7 @@ def train_worker(args, dev, dist, rank, world):
                                        "note": "five bucketed RCCL all-reduces issued on a one-rank group (identity; skipped in the timed run)"}
         step_fn._reducer.reduce_one_rank = False
     if rank == 0:
-        if world == 1 and args.precision == "fp32" and not args.no_fp32:
+        if world == 1 and args.full and args.precision == "fp32" and not args.no_fp32:
             # the same update with mixed-precision GEMMs (bf16-rounded operands, fp32 accumulation, fp32 master weights)
             m2 = tm.TrainModel(sd, num_layers=args.num_layers, device=dev, precision="bf16")
             s2 = tm.GraphedTrainStep(m2, train.Adam(m2.parameters()), B, L, Lt)
@@ -394,7 +430,7 @@ def train_worker(args, dev, dist, rank, world):
             sync()
             d2 = (time.perf_counter() - t1) / args.steps
             res["bf16_mode"] = {"value": B / d2, "unit": "samples/s", "ms_per_step": d2 * 1e3, "steps": args.steps}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_train_baseline(args, spec)
         emit(json.dumps(res))
     if dist is not None:

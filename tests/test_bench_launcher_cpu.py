@@ -47,3 +47,20 @@ def test_single_rank_needs_no_launcher():
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert j["n_gpus"] == 1 and len(j["per_rank_ms"]) == 1
+
+
+def test_dump_outputs_writes_the_last_step_of_every_rank(tmp_path):
+    """--dump-outputs DIR: the last timed step's result as f32 DIR/<name>.npy (one file per rank when N>1)."""
+    import numpy as np
+    r = _run("--gpus", "1", "--dump-outputs", str(tmp_path / "one"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    a = np.load(tmp_path / "one" / "samples.npy")
+    assert a.dtype == np.float32 and a.shape == (1,)
+    r = _run("--gpus", "2", "--dump-outputs", str(tmp_path / "two"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(os.listdir(tmp_path / "two")) == ["samples_rank0.npy", "samples_rank1.npy"]
+
+
+def test_steps_must_be_positive():
+    r = _run("--gpus", "1", "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -204,3 +204,45 @@ def test_bench_prints_exactly_one_json_line_with_rccl_initialised():
     assert len(lines) == 1, r.stdout[:2000]
     res = json.loads(lines[0])
     assert res["n_gpus"] == 1 and res["value"] > 0 and res["metric"].startswith("stroke-points")
+
+
+def _bench(*argv, timeout=600):
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], cwd=ROOT, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[:2000]
+    return json.loads(lines[0])
+
+
+SECONDARY_FIGURES = ("work_per_sample_call", "model_tflops", "roofline", "kernels", "fp32_mode", "nl4_mode", "longseq_mode", "train_step",
+                     "cpu_baseline")
+
+
+def test_plain_bench_run_times_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR`: K timed steps, none of the --full figures, and DIR/samples.npy is the
+    sample the last timed step (seed 1000 + W + K - 1) returned — recomputed here through the library at the bench's inputs."""
+    K, W = 2, 1
+    res = _bench("--steps", str(K), "--warmup", str(W), "--dump-outputs", str(tmp_path))
+    assert res["steps"] == K and res["warmup"] == W and res["ms_per_step"] > 0 and res["dtype"] == "bf16"
+    assert res["metric"].startswith("stroke-points/sec") and res["unit"] == "stroke-points/s" and res["higher_is_better"] is True
+    assert abs(res["value"] - 64 * 488 / (res["ms_per_step"] * 1e-3)) / res["value"] < 1e-6
+    assert not set(SECONDARY_FIGURES) & set(res), sorted(res)
+    got = np.load(tmp_path / "samples.npy")
+    assert got.dtype == np.float32 and got.shape == (64, 488, 3)
+    B, L, Lt = 64, 488, 30
+    m = _model("bf16", B, L, Lt)
+    inp = spec.synthetic_inputs_range(0, B, L, Lt, seed=1, T=0)
+    want = dhg_amd.sample(m, torch.from_numpy(inp["text"]).cuda(), torch.from_numpy(inp["style"]).cuda(), L=L, T=60,
+                          seed=1000 + W + K - 1).cpu().numpy()
+    assert np.array_equal(got, want)
+
+
+def test_full_bench_run_keeps_the_secondary_figures():
+    """--full: the kernel profile / roofline and the other-precision and depth figures are still measured (the two slow legs,
+    configs[3] and the CPU oracle, and the training step are left out here)."""
+    res = _bench("--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-longseq", "--no-train-step")
+    for k in ("work_per_sample_call", "model_tflops", "roofline", "kernels", "fp32_mode", "nl4_mode"):
+        assert k in res, sorted(res)
+    assert res["roofline"]["frac"] > 0 and res["fp32_mode"]["value"] > 0

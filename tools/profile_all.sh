@@ -30,7 +30,7 @@ python3 tools/pmc_sq.py "$out/sq" "$out/${tag}_sq_counters.json" > "$out/sq.txt"
 python3 tools/pmc_insts.py "$out/insts" "$out/${tag}_inst_mix.json" > "$out/insts.txt"
 python3 tools/pmc_l2.py "$out/l2" "$out/${tag}_l2_counters.json" > "$out/l2.txt"
 cp $(find "$out/trace" -name "*kernel_stats.csv" | head -1) "$out/${tag}_rocprof_kernel_stats.csv"
-python3 bench.py --steps 10 --warmup 3 > "$out/${tag}_bench.json" 2> "$out/bench.err"
+python3 bench.py --full --steps 10 --warmup 3 > "$out/${tag}_bench.json" 2> "$out/bench.err"
 # the big per-dispatch CSVs stay on the box; only the summaries are merged back
 rm -rf "$out/trace" "$out/fetch" "$out/write" "$out/sq" "$out/insts" "$out/l2"
 ls -la "$out"
