@@ -9,7 +9,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdhw_hip.so")
-SOURCES = ["gemm.hip", "convblock.hip", "enclayer.hip", "persist.hip", "attn.hip", "misc.hip", "style.hip", "textside.hip", "train.hip", "dhw_api.cpp", "dhw_style_api.cpp", "dhw_train_api.cpp"]
+SOURCES = ["gemm.hip", "convblock.hip", "enclayer.hip", "ragged/gemm_ragged.hip", "ragged/convblock_ragged.hip",
+           "ragged/enclayer_ragged.hip", "ragged/attn_ragged.hip", "persist.hip", "attn.hip", "misc.hip", "style.hip", "textside.hip", "train.hip", "dhw_api.cpp", "dhw_style_api.cpp", "dhw_train_api.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
 
@@ -36,8 +37,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
     jobs = []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
-        obj = os.path.join(objdir, s.rsplit(".", 1)[0] + ".o")
-        if force or _stale(obj, [src] + headers):
+        obj = os.path.join(objdir, os.path.basename(s).rsplit(".", 1)[0] + ".o")
+        # ragged/<f>_ragged.hip: <f>.hip compiled with per-sample lengths (csrc/dhw_kernels.h, DHW_LENS)
+        base = [os.path.join(CSRC, os.path.basename(s).replace("_ragged", ""))] if s.startswith("ragged/") else []
+        if force or _stale(obj, [src] + base + headers):
             cmd = [hipcc, *FLAGS, "-x", "hip", "-c", src, "-o", obj]
             jobs.append(cmd)
 
@@ -53,7 +56,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         for w in ex.map(run, jobs):
             if verbose and w:
                 print(w)
-    objs = [os.path.join(objdir, s.rsplit(".", 1)[0] + ".o") for s in SOURCES]
+    objs = [os.path.join(objdir, os.path.basename(s).rsplit(".", 1)[0] + ".o") for s in SOURCES]
     if force or jobs or _stale(LIB, objs):
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
     return LIB

@@ -26,7 +26,8 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
   const int l15 = lane & 15, g = lane >> 4;
   const int h = blockIdx.y, b = blockIdx.z;
   const int q0 = blockIdx.x * 64 + wave * 16;
-  if (q0 >= p.Lq) return;   // wave-uniform
+  const int Lq = sample_len(p.lens, p.lsh, b, p.Lq), Lk = p.lens_keys ? sample_len(p.lens, p.lsh, b, p.Lk) : p.Lk;   // (ragged batches)
+  if (q0 >= Lq) return;   // wave-uniform
 
   const T* Q = reinterpret_cast<const T*>(p.Q);
   // Q fragments (B operand): query q0+l15, d = 32c + 8g .. +8; d >= D is zero (D = 48)
@@ -39,8 +40,8 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
   f32x4 o[DT];
   attn_wave16_auto<T, D>(qf, reinterpret_cast<const T*>(p.K) + (size_t)(b * p.Lk + l15) * p.ldk + p.koff + h * D, p.ldk,
                     reinterpret_cast<const T*>(p.Vt) + ((size_t)(b * p.H + h) * D + l15) * p.lpad + 4 * g, p.lpad,
-                    p.text ? p.text + (size_t)b * p.ldt : nullptr, p.Lk, o);
-  if (q0 + l15 < p.Lq) {
+                    p.text ? p.text + (size_t)b * p.ldt : nullptr, Lk, o);
+  if (q0 + l15 < Lq) {
     T* out = reinterpret_cast<T*>(p.out) + (size_t)(b * p.Lq + q0 + l15) * p.ldo + h * D + 4 * g;
 #pragma unroll
     for (int t = 0; t < DT; ++t) store4(out + 16 * t, o[t]);

@@ -128,6 +128,10 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
 
   // (DHW_UNIFORM_WAVE: the wave index as a scalar — `wave < 6` of the 192-channel blocks, whose layouts leave two waves without channels, is then a
   // scalar branch instead of an exec mask)
+  // this sample's rows at this level (ragged batches: p.lens; p.L is then the padded length and stays the row stride).  A tile that
+  // starts at or past the end has no row to write: the whole workgroup leaves before its first barrier.
+  const int Ls = sample_len(p.lens, p.lsh, b, p.L);
+  if constexpr (DHW_LENS) { if (m0 >= Ls) return; }
   const int tid = body_tid(), lane = tid & 63, wave = DHW_UNIFORM_WAVE ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   const int l15 = lane & 15, g = lane >> 4;
   const int Cin = SK ? CIN : p.Cin;
@@ -209,9 +213,9 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
       cl.load(RX * CPX, tid, NTHR, [&](int id) { const int r = id / CPX, cc = id - r * CPX, lrow = min(max(m0 - 2 + r, 0), p.L - 1);
                                                  return reinterpret_cast<const uint4*>(low + ((size_t)(b * (p.L / 2) + (lrow >> 1)) * UPC) * ES + (size_t)cc * 16); });
       ch.store(RH * CPRH, tid, NTHR, [&](int id) { const int r = id / CPRH, cc = id - r * CPRH; return reinterpret_cast<uint4*>(HS + r * SHh + cc * 16); },
-               [&](int id) { const int lrow = m0 - 3 + id / CPRH; return lrow >= 0 && lrow < p.L; });
+               [&](int id) { const int lrow = m0 - 3 + id / CPRH; return lrow >= 0 && lrow < Ls; });
       cl.store(RX * CPX, tid, NTHR, [&](int id) { const int r = id / CPX, cc = id - r * CPX; return reinterpret_cast<uint4*>(XR + r * SX + cc * 16); },
-               [&](int id) { const int lrow = m0 - 2 + id / CPX; return lrow >= 0 && lrow < p.L; });
+               [&](int id) { const int lrow = m0 - 2 + id / CPX; return lrow >= 0 && lrow < Ls; });
     }
     // (requested behind the staging loads: see below)
     ringu.template fill_s<3 * UCH / 32>(reinterpret_cast<const T*>(p.up_w) + ((size_t)ntu0 * KCh * 3 * 64 + lane) * 8);
@@ -234,7 +238,7 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
     }
     {
       // x = round(conv + bias + low) (the block's own 'same' padding: zero outside the sample) -> XR; SiLU(x) -> XS
-      auto keep = [&](int j) { const int lrow = m0 - 2 + rowu0 + j * 16 + l15; return lrow >= 0 && lrow < p.L; };
+      auto keep = [&](int j) { const int lrow = m0 - 2 + rowu0 + j * 16 + l15; return lrow >= 0 && lrow < Ls; };
       auto valid = [&](int j) { return rowu0 + j * 16 + l15 < RX; };
 #pragma unroll
       for (int i = 0; i < NTU; ++i)
@@ -273,7 +277,7 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
     for (int it = 0; it < IT; ++it) {
       const int r = r0 + it * RSTEP, lrow = m0 - 2 + r;
       if (r < RX) {
-        const bool in = lrow >= 0 && lrow < p.L;
+        const bool in = lrow >= 0 && lrow < Ls;
         const float s0 = sp[it].x, s1 = sp[it].y;
         f32x4 v, sv;
 #pragma unroll
@@ -293,7 +297,7 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
       const int r = id / cpr, c = (id - r * cpr) * 4;
       const int lrow = m0 - 2 + r;
       f32x4 v = (f32x4){0, 0, 0, 0}, sv = v;
-      if (lrow >= 0 && lrow < p.L) {
+      if (lrow >= 0 && lrow < Ls) {
         const float s0 = p.strokes[(size_t)(b * p.L + lrow) * 2], s1 = p.strokes[(size_t)(b * p.L + lrow) * 2 + 1];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -327,7 +331,7 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
         if (id < total) {
           const int r = id / cpr, cc = id - r * cpr;
           const int lrow = m0 - 2 + r;
-          const bool k = lrow >= 0 && lrow < p.L;
+          const bool k = lrow >= 0 && lrow < Ls;
           uint4 w = make_uint4(k ? v[u].x : 0u, k ? v[u].y : 0u, k ? v[u].z : 0u, k ? v[u].w : 0u);
           *reinterpret_cast<uint4*>(XR + r * SX + cc * 16) = w;
           *reinterpret_cast<uint4*>(XS + r * SX + cc * 16) = (DHW_ABL & 8) ? w : silu_piece<T>(w);
@@ -375,7 +379,7 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
     if (act1) {
       epilogue_pairs<T, NT1, MT1, !(DHW_ABL & 8)>(lane, H1, SH1, row01, n1, acc,
           [&](int i, const f32x4& a) { return (a + ep1.bias[i]) * ep1.gam[i] + ep1.bet[i]; },
-          [&](int j) { const int srow = m0 - 1 + row01 + j * 16 + l15; return srow >= 0 && srow < p.L; },   // conv2 pads h1 with zeros
+          [&](int j) { const int srow = m0 - 1 + row01 + j * 16 + l15; return srow >= 0 && srow < Ls; },   // conv2 pads h1 with zeros
           [](int) { return true; },
           [&](int step) {
             if (act2) {
@@ -449,7 +453,7 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
   if constexpr (PPX) { if (pp_lead && p.out_f32) CB_BARRIER(); }
   STAMP(8);
 
-  const int rows_valid = min(BMO, p.L - m0);
+  const int rows_valid = min(BMO, Ls - m0);
   if (p.out_f32) {
     constexpr int SO = CO * 4 + 16;
     if (act2) {

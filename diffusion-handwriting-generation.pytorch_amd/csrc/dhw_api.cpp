@@ -259,6 +259,11 @@ struct dhw_handle {
   float* d_noise_stage = nullptr;
   size_t noise_stage_cap = 0;
   uint64_t* d_seed = nullptr;   // [seed, first_sample] read by the noise kernels
+  // ragged calls (dhw_forward_ragged / dhw_sample_ragged): the per-sample lengths, copied on the caller's stream from a pinned host
+  // buffer the handle owns.  The kernels read them at run time, so one captured graph serves every set of lengths of a shape.
+  int* d_lens = nullptr;          // [max_B]
+  int* h_lens_pin = nullptr;      // [max_B] pinned source of that copy
+  hipEvent_t lens_ev = nullptr;   // recorded behind the last copy: the pinned buffer is rewritten only once that copy has read it
 
   // One persistent launch per denoiser call inside dhw_sample's graph (persist.h): env DHW_PERSIST=1.  OFF by default: measured
   // 359 us per call against 328 us for the eleven launches (profiles/r04_persistent_step_trace.log) — bit-identical
@@ -630,6 +635,9 @@ int alloc_shared(dhw_handle* h) {
   if ((rc = dev_alloc(h, (void**)&h->d_text_stage, (size_t)(B * Lt + 64) * 8))) return rc;
   if ((rc = dev_alloc(h, (void**)&h->d_style_stage, (size_t)(B * S5 + SLACK_ROWS) * STYLE_CH * 4))) return rc;
   if ((rc = dev_alloc(h, (void**)&h->d_out_stage, (size_t)(B * L + SLACK_ROWS) * 3 * 4))) return rc;
+  if ((rc = dev_alloc(h, (void**)&h->d_lens, (size_t)B * 4))) return rc;
+  if (hipHostMalloc((void**)&h->h_lens_pin, (size_t)B * 4) != hipSuccess) return fail(h, DHW_ERR_HIP, "pinned length buffer: %s", hipGetErrorString(hipGetLastError()));
+  if (hipEventCreateWithFlags(&h->lens_ev, hipEventDisableTiming) != hipSuccess) return fail(h, DHW_ERR_HIP, "event create failed");
   return 0;
 }
 
@@ -688,7 +696,15 @@ struct Ctx {
   // anything the persistent kernel has no phase for sets rec_fail
   std::vector<StepPhase>* rec = nullptr;
   bool rec_fail = false;
+  const int* lens = nullptr;   // ragged batch: device lengths of samples [0, B) at full resolution (GemmParams.lens), or null
 };
+
+// level of a stroke-side launch: L_full >> shift == L (full, /2, /4, /8)
+int level_shift(int L_full, int L) {
+  int k = 0;
+  while ((L << k) < L_full) ++k;
+  return k;
+}
 
 // append one phase of the persistent per-step kernel (record mode)
 void rec_phase(Ctx& c, int kind, int L, const ConvBlockParams* cb, const EncLayerParams* el, const EncChain* nx) {
@@ -718,6 +734,9 @@ void* need(Ctx& c, void* p, const char* what) {
 #define ELT(c, li, field) need((c), ((c).planeT ? (c).ws->el[li].tT : (c).ws->el[li].t).field, (c).planeT ? #field ".T" : #field)   /* its text projections, as the text side writes them */
 #define ELK(c, li, field) need((c), ((c).use_plane ? (c).ws->el[li].tT : (c).ws->el[li].t).field, (c).use_plane ? #field ".T" : #field)   /* ... as the stroke side reads them */
 
+GemmParams gp_base(const Ctx& c, int L, int N);
+// a GEMM of the stroke path at a level of L rows per sample: in a ragged batch it carries the per-sample lengths
+GemmParams gp_stroke(const Ctx& c, int L, int N);
 GemmParams gp_base(const Ctx& c, int L, int N) {
   GemmParams p{};
   p.nseg = 1;
@@ -727,6 +746,12 @@ GemmParams gp_base(const Ctx& c, int L, int N) {
   p.n_store = N;
   p.film_bs = c.film_bs;
   p.film_div = c.film_div;
+  return p;
+}
+GemmParams gp_stroke(const Ctx& c, int L, int N) {
+  GemmParams p = gp_base(c, L, N);
+  p.lens = c.lens;
+  p.lsh = level_shift(c.L, L);
   return p;
 }
 // All-steps text plane: a GEMM with no per-sample structure (no position bias, no transposed-V output) can see each
@@ -768,7 +793,7 @@ void run_gemm(Ctx& c, const char* label, const GemmParams& p) {
   Launch l(c.h, c.st, label, gemm_flops(p), gemm_bytes(c.h, p));
   GemmParams q = p;
   if (q.ln) q.ln_n = true_width(c.h, q.N);
-  hipError_t e = launch_gemm(c.h->prec, q, c.st);
+  hipError_t e = q.lens ? launch_gemm_ragged(c.h->prec, q, c.st) : launch_gemm(c.h->prec, q, c.st);
   if (e != hipSuccess) c.err = fail(c.h, DHW_ERR_HIP, "gemm %s: %s", label, hipGetErrorString(e));
 }
 void run_attn(Ctx& c, const char* label, const AttnParams& p) {
@@ -776,7 +801,7 @@ void run_attn(Ctx& c, const char* label, const AttnParams& p) {
   if (c.err) return;
   Launch l(c.h, c.st, label, 4.0 * p.B * p.H * (double)p.Lq * p.Lk * p.D,
            (double)p.B * p.H * p.D * (2.0 * p.Lq + 2.0 * p.Lk) * c.h->es);
-  hipError_t e = launch_attn(c.h->prec, p, c.st);
+  hipError_t e = p.lens ? launch_attn_ragged(c.h->prec, p, c.st) : launch_attn(c.h->prec, p, c.st);
   if (e != hipSuccess) c.err = fail(c.h, DHW_ERR_HIP, "attn %s: %s", label, hipGetErrorString(e));
 }
 #define RUN_SMALL(c, label, call)                                                                  \
@@ -820,6 +845,7 @@ void conv_block(Ctx& c, int id, const ConvBlockW& w, const void* x, int L, void*
     q.film = c.film; q.film_bs = c.film_bs; q.film_tot = h->film_tot;
     q.f1 = w.f1; q.f2 = w.f2; q.f3 = w.f3;
     q.out = out; q.out_f32 = out_f32; q.pool = pool;
+    q.lens = c.lens; q.lsh = level_shift(c.L, L);
     if (c.fhp && id == CB_DEC1) {
       q.fuse_heads = 1;
       q.hp = *c.fhp;
@@ -852,7 +878,8 @@ void conv_block(Ctx& c, int id, const ConvBlockW& w, const void* x, int L, void*
       Launch l(h, c.st, ch ? "convblock.fused+a" : "convblock.fused", 2.0 * rows * (4.5 * w.cin * w.cout + 2.5 * w.cout * w.cout + upf) + chf,
                rows * ((up ? up->cin + 0.5 * w.cin : w.cin) * h->es + w.cout * (out_f32 ? 4.0 : (double)h->es) * (pool ? 1.5 : 1.0)) +
                    (4.5 * w.cin * w.cout + 2.5 * w.cout * w.cout + upf) * h->es + chb);
-      hipError_t e = ch ? launch_convblock_chain(h->prec, q, *chain, c.st) : launch_convblock(h->prec, q, c.st);
+      hipError_t e = q.lens ? (ch ? launch_convblock_chain_ragged(h->prec, q, *chain, c.st) : launch_convblock_ragged(h->prec, q, c.st))
+                            : (ch ? launch_convblock_chain(h->prec, q, *chain, c.st) : launch_convblock(h->prec, q, c.st));
       if (e != hipSuccess) c.err = fail(h, DHW_ERR_HIP, "convblock %s: %s", n, hipGetErrorString(e));
     }
     tap(c, tap_conv(id), out, L, w.cout, out_f32);
@@ -860,7 +887,7 @@ void conv_block(Ctx& c, int id, const ConvBlockW& w, const void* x, int L, void*
   }
   if (c.rec) { c.rec_fail = true; return; }
   {  // h1 = SiLU(FiLM1(conv1(SiLU(x))))
-    GemmParams p = gp_base(c, L, w.cout / 2);
+    GemmParams p = gp_stroke(c, L, w.cout / 2);
     p.seg[0] = GemmSeg{x, w.w_c1, w.cin, 3, 1};
     p.bias0 = w.b_c1;
     set_film(c, p, w.f1, 1);
@@ -869,7 +896,7 @@ void conv_block(Ctx& c, int id, const ConvBlockW& w, const void* x, int L, void*
     run_gemm(c, "convblock.conv1", p);
   }
   {  // h2 = SiLU(FiLM2(conv2(h1)))
-    GemmParams p = gp_base(c, L, w.cout);
+    GemmParams p = gp_stroke(c, L, w.cout);
     p.seg[0] = GemmSeg{CBB(c, id, h1), w.w_c2, w.cout / 2, 3, 0};
     p.bias0 = w.b_c2;
     set_film(c, p, w.f2, 1);
@@ -878,7 +905,7 @@ void conv_block(Ctx& c, int id, const ConvBlockW& w, const void* x, int L, void*
     run_gemm(c, "convblock.conv2", p);
   }
   {  // out = FiLM3(fc(h2)) + conv_skip(x)
-    GemmParams p = gp_base(c, L, w.cout);
+    GemmParams p = gp_stroke(c, L, w.cout);
     p.nseg = 2;
     p.seg[0] = GemmSeg{CBB(c, id, h2), w.w_fc, w.cout, 1, 0};
     p.seg[1] = GemmSeg{x, w.w_skip, w.cin, 3, 0};
@@ -956,6 +983,7 @@ EncLayerParams enc_params(Ctx& c, int li, const EncLayerW& w, const void* x, int
   q.k1 = k1p; q.vt1 = vt1p; q.lpadT = h->lpadT; q.text = text;
   q.x2 = ELB(c, li, x2); q.qk2 = ELB(c, li, qk2); q.vt2 = ELB(c, li, vt2); q.lpadX = lpad;
   q.out = ELB(c, li, out); q.pool = pool;
+  q.lens = c.lens; q.lsh = level_shift(c.L, Lk);
   return q;
 }
 
@@ -1002,7 +1030,7 @@ void enc_layer(Ctx& c, int li, const EncLayerW& w, const void* x, int Lk, int lp
         by += r2 * d2 * 5 * h->es + 5.0 * d2 * d2 * h->es;
       }
       Launch l(h, c.st, which == 0 ? "enc.fused_a" : (ch && ch->mode ? "enc.fused_bc+a" : "enc.fused_bc"), fl, by);
-      hipError_t e = launch_enclayer(h->prec, q, which, c.st, ch);
+      hipError_t e = q.lens ? launch_enclayer_ragged(h->prec, q, which, c.st, ch) : launch_enclayer(h->prec, q, which, c.st, ch);
       if (e != hipSuccess) c.err = fail(h, DHW_ERR_HIP, "enclayer %s/%d: %s", h->el_name[li].c_str(), which, hipGetErrorString(e));
     }
     tap(c, tap_el(li, 1), ELB(c, li, x2), Lk, d);
@@ -1011,7 +1039,7 @@ void enc_layer(Ctx& c, int li, const EncLayerW& w, const void* x, int Lk, int lp
   }
   if (c.rec) { c.rec_fail = true; return; }
   {  // q1 = Wq(x + PE)
-    GemmParams p = gp_base(c, Lk, d);
+    GemmParams p = gp_stroke(c, Lk, d);
     p.seg[0] = GemmSeg{x, w.w_q1, d, 1, 0};
     p.bias0 = w.b_q1;
     p.posb = w.pb_q1;
@@ -1027,10 +1055,11 @@ void enc_layer(Ctx& c, int li, const EncLayerW& w, const void* x, int Lk, int lp
     a.text = text; a.ldt = c.Lt;
     a.out = ELB(c, li, a1); a.ldo = d;
     a.B = c.B; a.H = w.heads; a.D = d / w.heads; a.Lq = Lk; a.Lk = c.Lt;
+    a.lens = c.lens; a.lsh = level_shift(c.L, Lk);   // (ragged: this sample's query rows; the keys are the text's)
     run_attn(c, "attn.cross", a);
   }
   {  // x2 = FiLM1(LN(dense(a1))) + x
-    GemmParams p = gp_base(c, Lk, d);
+    GemmParams p = gp_stroke(c, Lk, d);
     p.seg[0] = GemmSeg{ELB(c, li, a1), w.w_d1, d, 1, 0};
     p.bias0 = w.b_d1;
     p.ln = 1;
@@ -1040,7 +1069,7 @@ void enc_layer(Ctx& c, int li, const EncLayerW& w, const void* x, int Lk, int lp
     run_gemm(c, "enc.dense_cross", p);
   }
   {  // q2,k2 = W(x2 + PE), v2 = Wv x2
-    GemmParams p = gp_base(c, Lk, 3 * d);
+    GemmParams p = gp_stroke(c, Lk, 3 * d);
     p.seg[0] = GemmSeg{ELB(c, li, x2), w.w_qkv2, d, 1, 0};
     p.bias0 = w.b_qkv2;
     p.posb = w.pb_qk2;
@@ -1059,10 +1088,11 @@ void enc_layer(Ctx& c, int li, const EncLayerW& w, const void* x, int Lk, int lp
     a.text = nullptr;
     a.out = ELB(c, li, a2); a.ldo = d;
     a.B = c.B; a.H = w.heads; a.D = d / w.heads; a.Lq = Lk; a.Lk = Lk;
+    a.lens = c.lens; a.lsh = level_shift(c.L, Lk); a.lens_keys = 1;   // (ragged: this sample's rows are its keys)
     run_attn(c, "attn.self", a);
   }
   {  // x3 = FiLM2(LN(x2 + dense(a2)))
-    GemmParams p = gp_base(c, Lk, d);
+    GemmParams p = gp_stroke(c, Lk, d);
     p.seg[0] = GemmSeg{ELB(c, li, a2), w.w_d2, d, 1, 0};
     p.bias0 = w.b_d2;
     p.res1 = ELB(c, li, x2);
@@ -1072,7 +1102,7 @@ void enc_layer(Ctx& c, int li, const EncLayerW& w, const void* x, int Lk, int lp
     run_gemm(c, "enc.dense_self", p);
   }
   {  // f = SiLU(W1 SiLU(x3) + b1)
-    GemmParams p = gp_base(c, Lk, 2 * d);
+    GemmParams p = gp_stroke(c, Lk, 2 * d);
     p.seg[0] = GemmSeg{ELB(c, li, x3), w.w_f1, d, 1, 1};
     p.bias0 = w.b_f1;
     p.silu_out = 1;
@@ -1080,7 +1110,7 @@ void enc_layer(Ctx& c, int li, const EncLayerW& w, const void* x, int Lk, int lp
     run_gemm(c, "enc.ffn1", p);
   }
   {  // out = FiLM3(LN(W2 f + b2 + x3))
-    GemmParams p = gp_base(c, Lk, d);
+    GemmParams p = gp_stroke(c, Lk, d);
     p.seg[0] = GemmSeg{ELB(c, li, f), w.w_f2, 2 * d, 1, 0};
     p.bias0 = w.b_f2;
     p.res1 = ELB(c, li, x3);
@@ -1274,6 +1304,7 @@ void stroke_path(Ctx& c, const float* strokes, const int64_t* text) {
     p.seg[0] = GemmSeg{WS(c, enc5_pool), h->w_attd, d.c3, 1, 0};
     p.bias0 = h->b_attd;
     p.out = WS(c, att_dense);
+    p.lens = c.lens; p.lsh = 3;
     run_gemm(c, "att_dense", p);
   }
   tap(c, TAP_ATT_DENSE, WS(c, att_dense), L / 8, dt);
@@ -1312,6 +1343,7 @@ void stroke_path(Ctx& c, const float* strokes, const int64_t* text) {
     p.res2 = u.low;
     p.res2_half = 1;
     p.out = xd;
+    p.lens = c.lens; p.lsh = level_shift(c.L, u.L);
     run_gemm(c, "skip_conv_up", p);
     tap(c, u.tap, xd, u.L, u.cout);
     conv_block(c, u.cb, *decs[i], xd, u.L, CBB(c, u.cb, out), i == 2, nullptr);
@@ -1491,6 +1523,8 @@ int dhw_create(dhw_handle** out, const dhw_dims* dims, int device) {
       }
     }
     if (!rc && enclayer_init() != hipSuccess) rc = fail(h, DHW_ERR_HIP, "kernel attribute setup failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!rc && (enclayer_init_ragged() != hipSuccess || convblock_init_ragged() != hipSuccess || gemm_init_ragged() != hipSuccess))
+      rc = fail(h, DHW_ERR_HIP, "kernel attribute setup failed: %s", hipGetErrorString(hipGetLastError()));
     if (!rc && convblock_init() != hipSuccess) rc = fail(h, DHW_ERR_HIP, "kernel attribute setup failed: %s", hipGetErrorString(hipGetLastError()));
     if (!rc && textside_init() != hipSuccess) rc = fail(h, DHW_ERR_HIP, "kernel attribute setup failed: %s", hipGetErrorString(hipGetLastError()));
     if (!rc && gemm_init() != hipSuccess) rc = fail(h, DHW_ERR_HIP, "kernel attribute setup failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1521,6 +1555,8 @@ void destroy_impl(dhw_handle* h) {
     if (h->sub_streams[i]) hipStreamDestroy(h->sub_streams[i]);
   for (void* p : h->allocs) hipFree(p);
   if (h->h_step_err) hipHostFree(h->h_step_err);
+  if (h->h_lens_pin) hipHostFree(h->h_lens_pin);
+  if (h->lens_ev) hipEventDestroy(h->lens_ev);
   delete h;
 }
 }  // namespace
@@ -1654,17 +1690,35 @@ static int launch_heads_for(Ctx& c, HeadsParams hp) {
   return c.err;
 }
 
-int dhw_forward(dhw_handle* h, const float* strokes, const int64_t* text, const float* sigma, const float* style,
-                int B, int L, int Lt, float* eps_out, float* pen_out, void* hip_stream) {
-  DHW_GUARD(h, "dhw_forward", int, {
+// Ragged calls: check the caller's lengths (host pointer, B entries), refuse the diagnostic configurations that have no per-sample
+// ends, and copy the lengths into h->d_lens on the caller's stream.  The copy's source is the handle's pinned buffer, rewritten only
+// once the previous call's copy has read it (an event on that copy, not a device-wide synchronize).
+static int stage_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling, hipStream_t st) {
+  if (!lens) return fail(h, DHW_ERR_ARG, "%s: lens is NULL (B = %d entries expected)", fn, B);
+  for (int b = 0; b < B; ++b)
+    if (lens[b] < 8 || lens[b] > L || lens[b] % 8)
+      return fail(h, DHW_ERR_ARG, "%s: lens[%d] = %d: every length must be a multiple of 8 in [8, L = %d]", fn, b, (int)lens[b], L);
+  if (sampling && h->persist) return fail(h, DHW_ERR_ARG, "%s: the persistent step kernel (DHW_PERSIST=1) does not support per-sample lengths", fn);
+  HIPCK(h, hipEventSynchronize(h->lens_ev));
+  memcpy(h->h_lens_pin, lens, (size_t)B * 4);
+  HIPCK(h, hipMemcpyAsync(h->d_lens, h->h_lens_pin, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  HIPCK(h, hipEventRecord(h->lens_ev, st));
+  return 0;
+}
+
+static int forward_impl(dhw_handle* h, const char* fn, const float* strokes, const int64_t* text, const float* sigma, const float* style,
+                        int B, int L, int Lt, float* eps_out, float* pen_out, void* hip_stream, const int32_t* lens_host, bool ragged) {
+  {
     if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
-    if (!strokes || !text || !sigma || !style || !eps_out || !pen_out) return fail(h, DHW_ERR_ARG, "dhw_forward: null pointer");
+    if (!strokes || !text || !sigma || !style || !eps_out || !pen_out) return fail(h, DHW_ERR_ARG, "%s: null pointer", fn);
     int rc = check_shapes(h, B, L, Lt);
     if (rc) return rc;
     if ((rc = dhw_finalize(h))) return rc;
     HIPCK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
+    if (ragged && (rc = stage_lens(h, fn, lens_host, B, L, false, st))) return rc;
     Ctx c{h, &h->ws[0], st, B, L, Lt, h->dims.S * 5, h->d_film, 2L * h->film_tot};
+    c.lens = ragged ? h->d_lens : nullptr;
     taps_clear(h);
     RUN_SMALL(c, "sigma_ffn", launch_sigma_ffn(sigma, B, h->sg_w1, h->sg_b1, h->sg_w2, h->sg_b2, h->d_sig32, st));
     RUN_SMALL(c, "film_table", launch_film(h->d_sig32, B, h->d_film_w, h->d_film_b, 2 * h->film_tot, h->d_film, st));
@@ -1676,9 +1730,23 @@ int dhw_forward(dhw_handle* h, const float* strokes, const int64_t* text, const 
     hp.eps = eps_out;
     hp.pen = pen_out;
     launch_heads_for(c, hp);
+    if (c.lens) {   // ragged: eps / pen past each sample's end are 0
+      RUN_SMALL(c, "zero_tail", launch_zero_tail(eps_out, B, L, 2, c.lens, st));
+      RUN_SMALL(c, "zero_tail", launch_zero_tail(pen_out, B, L, 1, c.lens, st));
+    }
     h->last_B = B; h->last_L = L; h->last_Lt = Lt;
     return c.err;
-  });
+  }
+}
+
+int dhw_forward(dhw_handle* h, const float* strokes, const int64_t* text, const float* sigma, const float* style,
+                int B, int L, int Lt, float* eps_out, float* pen_out, void* hip_stream) {
+  DHW_GUARD(h, "dhw_forward", int, { return forward_impl(h, "dhw_forward", strokes, text, sigma, style, B, L, Lt, eps_out, pen_out, hip_stream, nullptr, false); });
+}
+
+int dhw_forward_ragged(dhw_handle* h, const float* strokes, const int64_t* text, const float* sigma, const float* style,
+                       int B, int L, int Lt, const int32_t* lens, float* eps_out, float* pen_out, void* hip_stream) {
+  DHW_GUARD(h, "dhw_forward_ragged", int, { return forward_impl(h, "dhw_forward_ragged", strokes, text, sigma, style, B, L, Lt, eps_out, pen_out, hip_stream, lens, true); });
 }
 
 // sampler steps whose text side is precomputed together (bounds the plane's memory for long schedules)
@@ -1690,7 +1758,7 @@ static int plane_chunk(int T) { return std::min(T, 64); }
 static int sample_enqueue(dhw_handle* h, Workspace* w, int b0, int Bs, int B, const int64_t* text, const float* style,
                           int L, int Lt, int T, int mode, const float* noise, float* out, hipStream_t st,
                           const std::vector<float>& beta, const std::vector<float>& alpha, const StepPlan* d_plans = nullptr,
-                          std::vector<StepPlan>* rec_out = nullptr) {
+                          std::vector<StepPlan>* rec_out = nullptr, const int* lens = nullptr) {
   const long rows = (long)Bs * L;
   const size_t step_stride = (size_t)B * L * 2;   // one noise draw for the whole batch
   text += (size_t)b0 * Lt;
@@ -1699,6 +1767,7 @@ static int sample_enqueue(dhw_handle* h, Workspace* w, int b0, int Bs, int B, co
   if (noise) noise += (size_t)b0 * L * 2;
   Ctx c{h, w, st, Bs, L, Lt, h->dims.S * 5, h->d_film_T, 0};
   c.fuse_input = true;
+  c.lens = lens ? lens + b0 : nullptr;
   // x_T
   if (rec_out) {
   } else if (noise) {
@@ -1707,6 +1776,8 @@ static int sample_enqueue(dhw_handle* h, Workspace* w, int b0, int Bs, int B, co
   } else {
     RUN_SMALL(c, "randn_init", launch_randn_init(w->d_xt, rows, L, h->d_seed, b0, st));
   }
+  // ragged: the padding rows of the sampler state start (and stay) 0 — nothing of a valid row reads them
+  if (!rec_out && c.lens) RUN_SMALL(c, "zero_tail", launch_zero_tail(w->d_xt, Bs, L, 2, c.lens, st));
   if (!rec_out) text_style_static(c, text, style);   // sigma-independent: once per sample batch, not per step
   const int TC = plane_chunk(T);
   for (int step = 0, i = T - 1; i >= 0; --i, ++step) {
@@ -1790,8 +1861,11 @@ static int sample_enqueue(dhw_handle* h, Workspace* w, int b0, int Bs, int B, co
     }
     stroke_path(c, w->d_xt, text);
     if (!fh) launch_heads_for(c, hp);
+    if (!fh && c.lens) RUN_SMALL(c, "zero_tail", launch_zero_tail(w->d_xt, Bs, L, 2, c.lens, st));   // (the stand-alone heads step every row)
     if (c.err) return c.err;
   }
+  // ragged: the output rows past each sample's end (the last step's tiles there exited without writing) are 0
+  if (!rec_out && c.lens) RUN_SMALL(c, "zero_tail", launch_zero_tail(out, Bs, L, 3, c.lens, st));
   return c.err;
 }
 
@@ -1826,13 +1900,14 @@ static const StepPlan* ensure_step_plans(dhw_handle* h, const std::vector<uint64
 // side streams (parallel graph branches) and join back; eagerly (profiling) they run one after another.
 static int sample_enqueue_all(dhw_handle* h, bool fork, int B, const int64_t* text, const float* style, int L, int Lt,
                               int T, int mode, const float* noise, float* out, hipStream_t st,
-                              const std::vector<float>& beta, const std::vector<float>& alpha, const StepPlan* d_plans = nullptr) {
+                              const std::vector<float>& beta, const std::vector<float>& alpha, const StepPlan* d_plans = nullptr,
+                              const int* lens = nullptr) {
   const int ns = std::min(h->nstreams, B);
   const int per = (B + ns - 1) / ns;
   taps_clear(h);
   if (!fork || ns == 1) {
     for (int s = 0, b0 = 0; b0 < B; ++s, b0 += per) {
-      int rc = sample_enqueue(h, &h->ws[s], b0, std::min(per, B - b0), B, text, style, L, Lt, T, mode, noise, out, st, beta, alpha, ns == 1 ? d_plans : nullptr);
+      int rc = sample_enqueue(h, &h->ws[s], b0, std::min(per, B - b0), B, text, style, L, Lt, T, mode, noise, out, st, beta, alpha, ns == 1 ? d_plans : nullptr, nullptr, lens);
       if (rc) return rc;
     }
     return 0;
@@ -1844,12 +1919,12 @@ static int sample_enqueue_all(dhw_handle* h, bool fork, int B, const int64_t* te
   for (int s = 1, b0 = per; !rc && b0 < B; ++s, b0 += per) {
     hipStream_t ss = h->sub_streams[s];
     if (hipStreamWaitEvent(ss, fork_ev, 0) != hipSuccess) { rc = fail(h, DHW_ERR_HIP, "fork wait failed"); break; }
-    rc = sample_enqueue(h, &h->ws[s], b0, std::min(per, B - b0), B, text, style, L, Lt, T, mode, noise, out, ss, beta, alpha);
+    rc = sample_enqueue(h, &h->ws[s], b0, std::min(per, B - b0), B, text, style, L, Lt, T, mode, noise, out, ss, beta, alpha, nullptr, nullptr, lens);
     if (rc) break;
     if (hipEventCreateWithFlags(&join_ev[s], hipEventDisableTiming) != hipSuccess || hipEventRecord(join_ev[s], ss) != hipSuccess)
       rc = fail(h, DHW_ERR_HIP, "join record failed");
   }
-  if (!rc) rc = sample_enqueue(h, &h->ws[0], 0, std::min(per, B), B, text, style, L, Lt, T, mode, noise, out, st, beta, alpha);
+  if (!rc) rc = sample_enqueue(h, &h->ws[0], 0, std::min(per, B), B, text, style, L, Lt, T, mode, noise, out, st, beta, alpha, nullptr, nullptr, lens);
   for (int s = 1; s < MAX_STREAMS; ++s)
     if (join_ev[s]) {
       if (!rc && hipStreamWaitEvent(st, join_ev[s], 0) != hipSuccess) rc = fail(h, DHW_ERR_HIP, "join wait failed");
@@ -1859,17 +1934,19 @@ static int sample_enqueue_all(dhw_handle* h, bool fork, int B, const int64_t* te
   return rc;
 }
 
-int dhw_sample(dhw_handle* h, const int64_t* text, const float* style, int B, int L, int Lt, int T, int mode,
-               const float* noise, uint64_t seed, int64_t first_sample, float* out, void* hip_stream) {
-  DHW_GUARD(h, "dhw_sample", int, {
+static int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float* style, int B, int L, int Lt, int T, int mode,
+                       const float* noise, uint64_t seed, int64_t first_sample, float* out, void* hip_stream, const int32_t* lens_host, bool ragged) {
+  {
     if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
-    if (!text || !style || !out) return fail(h, DHW_ERR_ARG, "dhw_sample: null pointer");
-    if (T < 1 || (mode != 0 && mode != 1)) return fail(h, DHW_ERR_ARG, "dhw_sample: bad T/mode");
+    if (!text || !style || !out) return fail(h, DHW_ERR_ARG, "%s: null pointer", fn);
+    if (T < 1 || (mode != 0 && mode != 1)) return fail(h, DHW_ERR_ARG, "%s: bad T/mode", fn);
     int rc = check_shapes(h, B, L, Lt);
     if (rc) return rc;
     if ((rc = dhw_finalize(h))) return rc;
     HIPCK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
+    if (ragged && (rc = stage_lens(h, fn, lens_host, B, L, true, st))) return rc;
+    const int* lens = ragged ? h->d_lens : nullptr;
     if (h->h_step_err && *(volatile unsigned*)h->h_step_err) {
       // a persistent step kernel gave up waiting (bounded spin, persist.h): its results were wrong; say so and fall back for good
       const unsigned code = *(volatile unsigned*)h->h_step_err;
@@ -1935,17 +2012,18 @@ int dhw_sample(dhw_handle* h, const int64_t* text, const float* style, int B, in
     if (!graph) {
       // eager launches: sub-batches still fork onto the side streams (concurrent kernels of different sub-batches);
       // profiling keeps one stream so the per-launch events bracket one kernel each
-      rc = sample_enqueue_all(h, !h->prof, B, h->d_text_stage, h->d_style_stage, L, Lt, T, mode, nz, h->d_out_stage, st, beta, alpha);
+      rc = sample_enqueue_all(h, !h->prof, B, h->d_text_stage, h->d_style_stage, L, Lt, T, mode, nz, h->d_out_stage, st, beta, alpha, nullptr, lens);
     } else {
-      const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)Lt, (uint64_t)T, (uint64_t)mode, (uint64_t)(nz != nullptr), (uint64_t)h->nstreams, (uint64_t)h->plane, (uint64_t)h->fuse_heads, (uint64_t)h->fuse_up, (uint64_t)h->chain, (uint64_t)h->persist};
+      const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)Lt, (uint64_t)T, (uint64_t)mode, (uint64_t)(nz != nullptr), (uint64_t)h->nstreams, (uint64_t)h->plane, (uint64_t)h->fuse_heads, (uint64_t)h->fuse_up, (uint64_t)h->chain, (uint64_t)h->persist,
+                                           (uint64_t)ragged};   // (ragged: the kernels read the lengths from h->d_lens at replay)
       auto it = h->graphs.find(key);
       if (it == h->graphs.end()) {
-        const StepPlan* d_plans = ensure_step_plans(h, key, B, L, Lt, T, mode, nz, beta, alpha);   // (before the capture: it uploads)
+        const StepPlan* d_plans = ragged ? nullptr : ensure_step_plans(h, key, B, L, Lt, T, mode, nz, beta, alpha);   // (before the capture: it uploads)
         hipStream_t cs;
         HIPCK(h, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
         hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
         if (e != hipSuccess) { hipStreamDestroy(cs); return fail(h, DHW_ERR_HIP, "begin capture: %s", hipGetErrorString(e)); }
-        rc = sample_enqueue_all(h, true, B, h->d_text_stage, h->d_style_stage, L, Lt, T, mode, nz, h->d_out_stage, cs, beta, alpha, d_plans);
+        rc = sample_enqueue_all(h, true, B, h->d_text_stage, h->d_style_stage, L, Lt, T, mode, nz, h->d_out_stage, cs, beta, alpha, d_plans, lens);
         hipGraph_t g = nullptr;
         e = hipStreamEndCapture(cs, &g);
         if (rc == 0 && e != hipSuccess) rc = fail(h, DHW_ERR_HIP, "graph capture failed: %s", hipGetErrorString(e));
@@ -1964,6 +2042,18 @@ int dhw_sample(dhw_handle* h, const int64_t* text, const float* style, int B, in
     if (rc == 0) HIPCK(h, hipMemcpyAsync(out, h->d_out_stage, rows * 3 * 4, hipMemcpyDeviceToDevice, st));
     h->last_B = B; h->last_L = L; h->last_Lt = Lt;
     return rc;
+  }
+}
+
+int dhw_sample(dhw_handle* h, const int64_t* text, const float* style, int B, int L, int Lt, int T, int mode,
+               const float* noise, uint64_t seed, int64_t first_sample, float* out, void* hip_stream) {
+  DHW_GUARD(h, "dhw_sample", int, { return sample_impl(h, "dhw_sample", text, style, B, L, Lt, T, mode, noise, seed, first_sample, out, hip_stream, nullptr, false); });
+}
+
+int dhw_sample_ragged(dhw_handle* h, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens, int T, int mode,
+                      const float* noise, uint64_t seed, int64_t first_sample, float* out, void* hip_stream) {
+  DHW_GUARD(h, "dhw_sample_ragged", int, {
+    return sample_impl(h, "dhw_sample_ragged", text, style, B, L, Lt, T, mode, noise, seed, first_sample, out, hip_stream, lens, true);
   });
 }
 

@@ -5,6 +5,14 @@
 
 enum { PREC_BF16 = 0, PREC_F32 = 1 };
 
+#define DHW_LENS_DEV __host__ __device__
+// DHW_LENS: whether the kernels of a translation unit honour per-sample lengths.  The stroke-path kernels are compiled twice:
+// gemm.hip / convblock.hip / enclayer.hip (and persist.hip) with 0 — the uniform path keeps exactly its instruction stream, so its
+// speed and its bits — and ragged/*_ragged.hip with 1 (the launchers there carry a _ragged suffix; dhw_api.cpp picks them for ragged calls).
+#ifndef DHW_LENS
+#define DHW_LENS 0
+#endif
+
 // ---------------------------------------------------------------- fused GEMM
 // out[b, m, n] = epilogue( sum_seg sum_tap sum_c  act_seg[b, m + tap - halo, c] * W_seg[n][tap*C + c] )
 // All activations are C-last [B, L, C] of the handle's element type.
@@ -46,10 +54,17 @@ struct GemmParams {
   void* vt;              // [B][N-n_store][vt_lpad] element type (keys contiguous)
   int vt_lpad;
   unsigned long long* stamps;   // diagnostics only: phase times (s_memrealtime) of the middle workgroup, or null
+  const int* lens;       // per-sample stroke lengths at full resolution [B] (device), or null = every sample is L rows long:
+  int lsh;               //   sample b then ends at row lens[b] >> lsh (rows past it are zero padding; strides stay L)
 };
+
+// Sample b's row count at a level whose samples are `L` rows apart: lens[b] >> lsh, or L when the batch is uniform.  lens[b] is a
+// multiple of 8, so the shift is exact at every level of the U-Net (full, /2, /4, /8).  b is uniform in a workgroup: one scalar load.
+DHW_LENS_DEV inline int sample_len(const int* lens, int lsh, int b, int L) { return DHW_LENS && lens ? lens[b] >> lsh : L; }
 
 // returns hipError; chooses the tile from (prec, L, N, ln)
 hipError_t launch_gemm(int prec, const GemmParams& p, hipStream_t st);
+hipError_t launch_gemm_ragged(int prec, const GemmParams& p, hipStream_t st);   // p.lens honoured (ragged/gemm_ragged.hip)
 // tile actually chosen (for tests / work accounting)
 void gemm_tile_for(int prec, const GemmParams& p, int* BM, int* BN);
 hipError_t gemm_init();
@@ -73,6 +88,8 @@ struct HeadsParams {
   const uint64_t* seed_ptr; int sample_off; int L; int iter;   // Philox: device [seed, first_sample]; counter = (sample, pos, iter)
   float* out3;             // optional [rows,3] final cat(x, pen)
 };
+// (ragged batches: the heads run on every row; the launch sequence then zeroes the padding rows of eps / pen / xt / out3 with
+// launch_zero_tail, and the fused dec1 heads only ever see rows inside their sample)
 
 // ---------------------------------------------------------------- fused ConvBlock (cnn.py:64-87), one launch
 struct ConvBlockParams {
@@ -94,9 +111,12 @@ struct ConvBlockParams {
   HeadsParams hp;                     //   output tile in LDS (hp.x/rows/C unused); `out` may then be null (no activation write)
   unsigned long long* stamps;         // diagnostics only: per-stage s_memrealtime of workgroup 0, or null
   int stagger;                        // two-workgroups-per-CU variants: the second half of the grid starts this many x 0.5 us late
+  const int* lens; int lsh;           // per-sample lengths (GemmParams.lens): sample b has lens[b] >> lsh rows, or null = L; tiles past it exit
 };
 hipError_t launch_convblock(int prec, const ConvBlockParams& p, hipStream_t st);
 hipError_t convblock_init();
+hipError_t launch_convblock_ragged(int prec, const ConvBlockParams& p, hipStream_t st);   // p.lens honoured (ragged/convblock_ragged.hip)
+hipError_t convblock_init_ragged();
 
 // ---------------------------------------------------------------- fused EncoderLayer stroke side (model.py:37-58), two launches
 struct EncLayerParams {
@@ -114,6 +134,7 @@ struct EncLayerParams {
   int bm_min;                                      // 0, or the smallest row tile to use (32 when enc_bc chains into a pooled layer)
   int dbg;                                         // diagnostics only: bit0 = skip the attention stage (a = q)
   unsigned long long* stamps;                      // diagnostics only: per-stage s_memrealtime of workgroup 0 (16 slots per kernel) or null
+  const int* lens; int lsh;                        // per-sample lengths (GemmParams.lens): sample b has lens[b] >> lsh rows and as many keys, or null = Lk
 };
 // What an enc_bc (or ConvBlock) workgroup goes on to compute for its own rows after its own block — the stages up to the
 // next self-attention are row-local, so they need no launch boundary:
@@ -128,12 +149,15 @@ struct EncChain {
 // A ConvBlock whose output feeds an EncoderLayer continues into that layer's enc_a on its own output tile (mode 1).
 bool convblock_chain_supported(int prec, const ConvBlockParams& p, const EncChain& chain);
 hipError_t launch_convblock_chain(int prec, const ConvBlockParams& p, const EncChain& chain, hipStream_t st);
+hipError_t launch_convblock_chain_ragged(int prec, const ConvBlockParams& p, const EncChain& chain, hipStream_t st);
 bool convblock_chain_auto(const ConvBlockParams& p);   // the chain is a measured win for this launch geometry (enc4 on the asymmetric 32-row tiles)
 bool enclayer_supported(int prec, int d, int heads);
 // whether enc_bc of a (d, B, Lk) layer can continue with `mode`; mode 2 needs EncLayerParams.bm_min = 32 on that layer
 bool enclayer_chain_supported(int prec, int d, int B, int Lk, int mode, int d_next);
 hipError_t launch_enclayer(int prec, const EncLayerParams& p, int which, hipStream_t st, const EncChain* chain = nullptr);
 hipError_t enclayer_init();
+hipError_t launch_enclayer_ragged(int prec, const EncLayerParams& p, int which, hipStream_t st, const EncChain* chain);   // p.lens honoured
+hipError_t enclayer_init_ragged();
 
 // ---------------------------------------------------------------- attention
 struct AttnParams {
@@ -143,8 +167,11 @@ struct AttnParams {
   const int64_t* text; int ldt; // key padding mask: key k masked (score += -1e9) iff text[b*ldt + k] == 0; null = none
   void* out; int ldo;          // out[(b*Lq + q)*ldo + h*D + d]
   int B, H, D, Lq, Lk;
+  const int* lens; int lsh;    // ragged batch (GemmParams.lens): sample b has lens[b] >> lsh query rows (and as many keys when
+  int lens_keys;               //   lens_keys: self-attention), or null = Lq / Lk
 };
 hipError_t launch_attn(int prec, const AttnParams& p, hipStream_t st);
+hipError_t launch_attn_ragged(int prec, const AttnParams& p, hipStream_t st);   // p.lens honoured (ragged/attn_ragged.hip)
 
 // ---------------------------------------------------------------- small kernels
 // sigma_ffn: sig32[n,32] = W2 SiLU(W1 SiLU(sigma) + b1) + b2        (model.py:83,134)
@@ -171,8 +198,11 @@ hipError_t launch_heads(const HeadsParams& p, hipStream_t st);
 hipError_t launch_randn_init(float* xt, long rows, int L, const uint64_t* seed_ptr, int sample_off, hipStream_t st, int iter = -1);
 // seed_ptr[0] = seed, seed_ptr[1] = first_sample (by-value kernel arguments: no host buffer lifetime)
 hipError_t launch_set_seed(uint64_t* seed_ptr, uint64_t seed, int64_t first_sample, hipStream_t st);
+// x[b, r, :] = 0 for r >= lens[b] (rows of C fp32 values, L rows per sample): the padding rows of ragged sampler state / outputs
+hipError_t launch_zero_tail(float* x, int B, int L, int C, const int* lens, hipStream_t st);
 // one-time per-process kernel attribute setup (dynamic LDS > 64 KiB)
 hipError_t gemm_init();
+hipError_t gemm_init_ragged();
 
 // ---------------------------------------------------------------- StyleExtractor spatial kernels (style.hip): NHWC, channels padded to Cp
 hipError_t launch_style_stem(int prec, const float* img, int B, int H, int W, const float* w, const float* bias, int Cp,

@@ -168,6 +168,7 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
   const bool act = DUP ? true : (WN * WM == 8 || wave < WN * WM);   // (DM = 192, 6 x 1 without DUP: waves 6, 7 own no channels in the GEMM stages)
   const int wm = DUP ? 0 : (act ? wave / WN : 0), wn = DUP ? wave % WN : (act ? wave % WN : 0);
   const int S = tile_stride<T>(DM);
+  const int Ls = sample_len(p.lens, p.lsh, b, p.Lk);   // this sample's rows (ragged batches; p.Lk stays the row stride)
   char* XR = m.XR;
   char* QR = m.QR;
   float* red = m.red;
@@ -276,7 +277,7 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
                                                 return reinterpret_cast<const uint4*>(v1s + (size_t)ch * p.lpadT + ((part + 1) * EPV <= p.lpadT ? part * EPV : 0)); });
     if (p.x)
       cx.store(BM * CPR, tid, 512, [&](int id) { const int r = id / CPR, cc = id - r * CPR; return reinterpret_cast<uint4*>(XR + r * S + cc * 16); },
-               [&](int id) { return m0 + id / CPR < p.Lk; });
+               [&](int id) { return m0 + id / CPR < Ls; });
     if constexpr (!KVLATE) kv_store(kv);
     if constexpr (PLDS) cp.template store<DM>(m.PL, tid);
   }
@@ -502,9 +503,10 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
           }
       }
       lds_barrier();
-      // keys this tile owns: its valid rows; the sample's last tile also zero-fills the padding up to lpadX
+      // keys this tile owns: its valid rows; the sample's last tile also zero-fills the padding up to lpadX (ragged batches: the rest
+      // of this tile, which covers the key piece that holds the sample's end — enc_bc stages no piece that starts past it)
       constexpr int KPP = VPIECE / ES, PPR = BM / KPP;   // keys per piece, pieces per channel row
-      const int klimit = m0 + rows_valid >= p.Lk ? min(BM, p.lpadX - m0) : rows_valid;
+      const int klimit = m0 + rows_valid >= Ls ? min(BM, p.lpadX - m0) : rows_valid;
       for (int id = tid; id < DM * PPR; id += 512) {
         const int ch = id / PPR, part = id - ch * PPR;
         if ((part + 1) * KPP <= klimit) {

@@ -42,7 +42,9 @@ DHW_DEV void enc_a_tile(const P& p, const int b, const int m0, char* smem) {
   m.VT = m.KT + 32 * tile_stride<T>(DM);
   m.VS = smem;   // spans the x2 and q1 tiles: DM * (BM * ES + 16) <= 2 * BM * S
   m.PL = reinterpret_cast<float*>(m.KT + enc_a_text_kv_bytes<T, DM, BM>());
-  enc_a_body<T, DM, BM>(p, m, b, m0, min(BM, p.Lk - m0));
+  const int Ls = sample_len(p.lens, p.lsh, b, p.Lk);   // (ragged batches: a tile past the sample's end leaves before its first barrier)
+  if constexpr (DHW_LENS) { if (m0 >= Ls) return; }
+  enc_a_body<T, DM, BM>(p, m, b, m0, min(BM, Ls - m0));
 }
 
 // Self-attention K / V staging.  bf16: 64-key blocks, DOUBLE buffered when two blocks of K [keys][DM] + V^T [DM][keys] fit
@@ -97,6 +99,9 @@ constexpr size_t lds_a_bytes() { return (size_t)2 * BM * tile_stride<T>(DM) + 2 
 template <typename T, int DM, int BM, int NEXT = 0, typename P, typename X>
 DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, char* smem) {
   constexpr int ES = sizeof(T);
+  // this sample's rows = its keys (ragged batches: p.lens; p.Lk stays the row stride).  A tile past the end leaves before its first barrier.
+  const int Ls = sample_len(p.lens, p.lsh, b, p.Lk);
+  if constexpr (DHW_LENS) { if (m0 >= Ls) return; }
   constexpr int WN = (DM % 128 == 0) ? 8 : (sizeof(T) == 4 ? 6 : DHW_WN192), WM = (DM % 128 == 0 || sizeof(T) == 4) ? 1 : DHW_WM192;   // as in enc_a_body: all rows per wave, channels split over WN waves
   constexpr int MT = BM / WM / 16, NT = DM / WN / 16, H = DM / 64, KC = DM / 32;
   constexpr bool XS = sizeof(T) == 2 && DHW_ENC_XSTREAM && !(DM == 384 && BM >= 32);   // (d = 384 with 32-row tiles: two accumulator rows + the ring spill)   // cross-stage weight stream (gemm_core.h, run_x); the fp32 parity mode keeps run_s + fill_s
@@ -180,7 +185,7 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
     CopyRegs<UK> ck;
     CopyRegs<UV> cv;
     // K rows [kb, kb + KBS) x DM channels and V^T rows [0, DM) x keys [kb, kb + KBS): requested at clamped (valid) addresses;
-    // K rows at or past Lk and V^T pieces past lpadX are zero-filled by the store
+    // K / V rows at or past the sample's end and V^T pieces past lpadX (or starting past the end) are zero-filled by the store
     auto request = [&](int kb) {
       ck.load(KBS * CPR, tid, 512, [&](int id) { const int r = id / CPR, cc = id - r * CPR;
                                                  return reinterpret_cast<const uint4*>(ksrc + (size_t)min(kb + r, p.Lk - 1) * QKS + cc * EPV); });
@@ -193,13 +198,14 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
     };
     auto commit = [&](int kb, char* KT, char* VT) {
       ck.store(KBS * CPR, tid, 512, [&](int id) { const int r = id / CPR, cc = id - r * CPR; return reinterpret_cast<uint4*>(KT + r * SK + cc * 16); },
-               [&](int id) { return kb + id / CPR < p.Lk; });
-      if constexpr (VROW)   // (V rows at or past Lk are zero: their softmax weights are exactly 0, the products must stay finite)
+               [&](int id) { return kb + id / CPR < Ls; });
+      if constexpr (VROW)   // (V rows at or past the end are zero: their softmax weights are exactly 0, the products must stay finite —
+                            // in a ragged batch they hold whatever an earlier, longer call left in the workspace)
         cv.store(KBS * CPR, tid, 512, [&](int id) { const int r = id / CPR, cc = id - r * CPR; return reinterpret_cast<uint4*>(VT + r * SV + cc * 16); },
-                 [&](int id) { return kb + id / CPR < p.Lk; });
-      else
+                 [&](int id) { return kb + id / CPR < Ls; });
+      else   // (a piece that straddles the end was zero-filled past it by enc_a, in this call)
         cv.store_to(DM * PPR, tid, 512, [&](int id, const uint4& v) { const int ch = id / PPR, part = id - ch * PPR; vt_store_piece<T>(VT + ch * SV, part, v); },
-                    [&](int id) { return kb + (id % PPR + 1) * EPV <= p.lpadX; });
+                    [&](int id) { return kb + (id % PPR + 1) * EPV <= p.lpadX && (!DHW_LENS || kb + (id % PPR) * EPV < Ls); });
     };
     Frag<T> qf[UMAX][2];
     float mr[UMAX], lr[UMAX];
@@ -227,7 +233,7 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
     lds_barrier();
     int ib = 0;
     auto key_block = [&](int kb) {
-      const bool more = kb + KBS < p.Lk;
+      const bool more = kb + KBS < Ls;
       char* KT = R2 + (DB && (ib & 1) ? BUFB : 0);
       char* VT = KT + KBS * SK;
       char* KN = R2 + (DB && !(ib & 1) ? BUFB : 0);   // where the next block goes
@@ -240,11 +246,11 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
       }
       if (ib < 3) STAMP(26 + 2 * ib);
       if constexpr (KSPLIT) {
-        if (ks_full) attn_unit_bf16<KBS>(lane, qf[0], KT, SK, VT, SV, hs, 0, kb, p.Lk, mr[0], lr[0], o[0]);
+        if (ks_full) attn_unit_bf16<KBS>(lane, qf[0], KT, SK, VT, SV, hs, 0, kb, Ls, mr[0], lr[0], o[0]);
         const int kh = (KBS / 2) * ks_half;   // (wave-uniform; a half past the end of the sequence is skipped: its state stays empty)
-        if (ks_part && kb + kh < p.Lk) attn_unit_bf16<KBS / 2>(lane, qf[SU], KT, SK, VT, SV, 2, kh, kb + kh, p.Lk, mr[SU], lr[SU], o[SU]);
+        if (ks_part && kb + kh < Ls) attn_unit_bf16<KBS / 2>(lane, qf[SU], KT, SK, VT, SV, 2, kh, kb + kh, Ls, mr[SU], lr[SU], o[SU]);
       } else
-      attn_units<T, KBS, false, UMAX>(lane, qf, KT, SK, VT, SV, hs, HS, H, kb, 0u, p.Lk, mr, lr, o);
+      attn_units<T, KBS, false, UMAX>(lane, qf, KT, SK, VT, SV, hs, HS, H, kb, 0u, Ls, mr, lr, o);
       if (ib < 3) STAMP(27 + 2 * ib);
       if (more) {
         if (!DB) {          // single buffer: every wave must be past its reads before the tiles are rewritten
@@ -261,9 +267,9 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
       // above among them) and waits for all of them — vmcnt(0) in front of the first block's math, i.e. the prefetch hid nothing
       key_block(0);
       ib = 1;
-      for (int kb = KBS; kb < p.Lk; kb += KBS, ++ib) key_block(kb);
+      for (int kb = KBS; kb < Ls; kb += KBS, ++ib) key_block(kb);
     } else {
-      for (int kb = 0; kb < p.Lk; kb += KBS, ++ib) key_block(kb);
+      for (int kb = 0; kb < Ls; kb += KBS, ++ib) key_block(kb);
     }
     if constexpr (PLDS && !PLFIX) {
       // the last block (index ib - 1) was read from buffer (ib - 1) & 1; the other one is free: its readers finished an
@@ -444,7 +450,7 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
     enc_store_tiles<T, NT, MT>(lane, R3, S, row0, n0, acc2);
   }
   lds_barrier();
-  const int rows_valid = min(BM, p.Lk - m0);
+  const int rows_valid = min(BM, Ls - m0);
   if constexpr (DHW_COPY_UNROLL != 0) tile_copy_out_u<T, BM, DM, 512>(R3, S, reinterpret_cast<T*>(p.out) + (size_t)(b * p.Lk + m0) * DM, DM, rows_valid, tid);
   else tile_copy_out<T>(R3, S, reinterpret_cast<T*>(p.out) + (size_t)(b * p.Lk + m0) * DM, DM, rows_valid, DM, tid, 512);
   if (p.pool)

@@ -49,6 +49,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const GemmParams p) 
   const int b = blockIdx.x / tiles;
   const int m0 = (blockIdx.x % tiles) * BM;
   const int nb0 = blockIdx.y * BN;
+  // this sample's rows (ragged batches: a row tile past the sample's end has nothing to compute; the whole workgroup leaves
+  // before its first barrier — except the transposed-V column blocks, which write the zero keys there)
+  const int Ls = sample_len(p.lens, p.lsh, b, p.L);
+  if constexpr (DHW_LENS) { if (m0 >= Ls && nb0 < p.n_store) return; }
 
   // ---- LDS carve: one activation tile per segment, then LN scratch
   int lds_off[2], lds_stride[2];
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const GemmParams p) 
         const int lrow = m0 - halo + r;
         v[u] = make_uint4(0, 0, 0, 0);
         dst[u] = id < total ? lds_off[s] + r * lds_stride[s] + cc * 16 : -1;
-        if (id < total && lrow >= 0 && lrow < p.L)
+        if (id < total && lrow >= 0 && lrow < Ls)
           v[u] = *reinterpret_cast<const uint4*>(src + ((size_t)(b * p.L + lrow) * sg.C) * ES + (size_t)cc * 16);
       }
 #pragma unroll
@@ -185,7 +189,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const GemmParams p) 
     for (int j = 0; j < MT; ++j) {
       const int lrow = m0 + row0 + j * 16 + l15;
       f32x4 v = acc[i][j] + bi;
-      if (lrow < p.L) {
+      if (lrow < Ls) {
         if (p.posb && n < p.posb_cols) v += *reinterpret_cast<const f32x4*>(p.posb + (size_t)lrow * p.posb_cols + n);
         if (p.res1) v += load4(reinterpret_cast<const T*>(p.res1) + (size_t)(b * p.L + lrow) * p.N + n);
       }
@@ -273,7 +277,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const GemmParams p) 
     for (int j = 0; j < MT; ++j) {
       const int rl = row0 + j * 16 + l15;
       const int lrow = m0 + rl;
-      const bool valid = lrow < p.L;
+      const bool valid = lrow < Ls;
       f32x4 v = acc[i][j];
       if (p.film_mode == 1) v = v * ga + be;
       if (p.res2 && valid) {
@@ -300,7 +304,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(const GemmParams p) 
   }
   __syncthreads();
   GSTAMP(4);
-  const int rows_valid = min(BM, p.L - m0);
+  const int rows_valid = min(BM, Ls - m0);
   if (vblock) {
     constexpr int EPV = 16 / ES, PPR = BM / EPV;
     const int NV = p.N - p.n_store;

@@ -143,6 +143,13 @@ __global__ __launch_bounds__(256) void randn_init_kernel(float* xt, long rows, i
   xt[row * 2 + 1] = z1;
 }
 
+// rows at or past their sample's length -> 0 (one thread per row of C floats)
+__global__ __launch_bounds__(256) void zero_tail_kernel(float* x, int L, int C, const int* lens, long rows) {
+  const long row = (long)blockIdx.x * 256 + threadIdx.x;
+  if (row >= rows || (int)(row % L) < lens[row / L]) return;
+  for (int c = 0; c < C; ++c) x[row * C + c] = 0.f;
+}
+
 inline unsigned nblk(long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
@@ -192,6 +199,12 @@ hipError_t launch_input_dense(int prec, const float* strokes, long rows, const f
 }
 hipError_t launch_heads(const HeadsParams& p, hipStream_t st) {
   hipLaunchKernelGGL(heads_kernel, dim3(nblk(p.rows, 16)), dim3(256), 0, st, p);
+  return hipGetLastError();
+}
+hipError_t launch_zero_tail(float* x, int B, int L, int C, const int* lens, hipStream_t st) {
+  if (!lens || B < 1 || L < 1 || C < 1) return hipErrorInvalidValue;
+  const long rows = (long)B * L;
+  hipLaunchKernelGGL(zero_tail_kernel, dim3(nblk(rows, 256)), dim3(256), 0, st, x, L, C, lens, rows);
   return hipGetLastError();
 }
 hipError_t launch_randn_init(float* xt, long rows, int L, const uint64_t* seed_ptr, int sample_off, hipStream_t st, int iter) {

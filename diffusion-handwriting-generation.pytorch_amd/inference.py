@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model import DiffusionModel, check_token_ids
+from .model import DiffusionModel, check_lengths, check_token_ids
 from .tokenizer import Tokenizer, stroke_length
 
 
@@ -25,8 +25,12 @@ def get_alpha_set(T: int = 60) -> torch.Tensor:
 
 def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor, L: int | None = None, T: int = 60,
            diffusion_mode: str = "new", noise: torch.Tensor | None = None, seed: int = 0,
-           first_sample: int = 0) -> torch.Tensor:
+           first_sample: int = 0, lengths=None) -> torch.Tensor:
     """Reverse-sample a batch.  text int [B,Lt] (0 = pad), style_vector [B,S,1280] -> [B,L,3] = (dx, dy, pen).
+
+    ``lengths`` (optional, B ints, multiples of 8 in [8, L]; ``L`` then defaults to max(lengths)): a ragged batch — prompts
+    of different stroke lengths in ONE call.  Row b equals prompt b sampled alone at ``L = lengths[b]`` with
+    ``first_sample + b`` (external noise: ``noise[:, b, :lengths[b]]``); rows past lengths[b] are 0.
 
     ``noise`` (optional, f32 [T+1,B,L,2]): noise[0] = x_T, noise[1+k] = the N(0,1) draw of the k-th loop
     iteration (the reference draws them from torch's global RNG, inference.py:82 / utils/nn.py:86,111).
@@ -36,6 +40,11 @@ def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor
     if diffusion_mode not in ("new", "standard"):
         raise ValueError("diffusion_mode must be 'new' or 'standard'")
     B, Lt = text.shape
+    lens = None
+    if lengths is not None:
+        lens = check_lengths(lengths, B, L)
+        if L is None:
+            L = max(lens)
     if L is None:
         L = stroke_length(Lt)
     if L % 8:
@@ -57,10 +66,15 @@ def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor
             nz = noise.to(dev, torch.float32).contiguous()
         out = torch.empty((B, L, 3), device=dev, dtype=torch.float32)
         stream = torch.cuda.current_stream(dev)
-        _lib.check(_lib.lib().dhw_sample(h, t.data_ptr(), sv.data_ptr(), B, L, Lt, T,
-                                         0 if diffusion_mode == "new" else 1,
-                                         nz.data_ptr() if nz is not None else None, seed, first_sample,
-                                         out.data_ptr(), C.c_void_p(stream.cuda_stream)), h)
+        mode = 0 if diffusion_mode == "new" else 1
+        if lens is None:
+            _lib.check(_lib.lib().dhw_sample(h, t.data_ptr(), sv.data_ptr(), B, L, Lt, T, mode,
+                                             nz.data_ptr() if nz is not None else None, seed, first_sample,
+                                             out.data_ptr(), C.c_void_p(stream.cuda_stream)), h)
+        else:
+            _lib.check(_lib.lib().dhw_sample_ragged(h, t.data_ptr(), sv.data_ptr(), B, L, Lt, (C.c_int32 * B)(*lens), T, mode,
+                                                    nz.data_ptr() if nz is not None else None, seed, first_sample,
+                                                    out.data_ptr(), C.c_void_p(stream.cuda_stream)), h)
         # the library's graph holds raw pointers: pin the inputs to the model so they outlive the launch
         model._last_sample_inputs = (t, sv, nz, out)
     return out.to(ret_dev)
@@ -74,6 +88,35 @@ def infer(prompt: str, style_vector: torch.Tensor, model: DiffusionModel, diffus
     text = torch.tensor([ids], dtype=torch.int64)
     out = sample(model, text, style_vector, L=stroke_length(len(ids)), T=T, diffusion_mode=diffusion_mode, seed=seed)
     return out[0].detach().cpu().numpy()
+
+
+def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diffusion_mode: str = "new", T: int = 60,
+                seed: int = 0, first_sample: int = 0) -> list:
+    """Many prompts in ONE ragged sampler call: prompt i is tokenised, gets its own ``L_i = stroke_length(n_i)`` and is padded
+    with token 0 to the longest prompt.  ``style_vector`` is [1,S,1280] (one writer for every prompt) or [B,S,1280].  Returns a
+    list of [L_i, 3] arrays; entry i equals ``sample(model, text_i, style_i, L=L_i, seed=seed, first_sample=first_sample + i)``."""
+    prompts = list(prompts)
+    if not prompts:
+        raise ValueError("infer_batch: no prompts")
+    tok = Tokenizer()
+    ids = [tok.encode(p) for p in prompts]
+    if any(len(i) == 0 for i in ids):
+        raise ValueError("infer_batch: every prompt needs at least one token")
+    B, Lt = len(ids), max(len(i) for i in ids)
+    text = torch.zeros((B, Lt), dtype=torch.int64)
+    for b, i in enumerate(ids):
+        text[b, :len(i)] = torch.tensor(i, dtype=torch.int64)
+    lens = [stroke_length(len(i)) for i in ids]
+    sv = torch.as_tensor(style_vector)
+    if sv.dim() != 3 or sv.shape[0] not in (1, B):
+        raise ValueError(f"style_vector must be [1,S,1280] or [B={B},S,1280], got {tuple(sv.shape)}")
+    if sv.shape[0] != B:
+        sv = sv.expand(B, -1, -1)
+    if sv.is_cuda:
+        text = text.to(sv.device)
+    out = sample(model, text, sv, L=max(lens), T=T, diffusion_mode=diffusion_mode, seed=seed, first_sample=first_sample, lengths=lens)
+    out = out.detach().cpu().numpy()
+    return [out[b, :lens[b]].copy() for b in range(B)]
 
 
 def remove_whitespace(img: np.ndarray, thresh: float) -> np.ndarray:
@@ -171,4 +214,37 @@ def infer_file(prompt: str, source, config_path: str | None = None, checkpoint_p
     strokes = infer(prompt, style, model, diffusion_mode=diffusion_mode, seed=seed)
     if render:
         show_strokes(strokes, scale=1, name=output, show_output=False)
+    return strokes
+
+
+def _resolve_experiment(config_path, checkpoint_path, experiment_path):
+    from .checkpoint import find_checkpoint
+    if experiment_path:
+        from pathlib import Path
+        if not config_path:
+            config_path = str(Path(experiment_path) / "config.yml")
+        if not checkpoint_path:
+            ckpt = find_checkpoint(experiment_path)
+            checkpoint_path = str(ckpt) if ckpt else None
+    if not config_path or not checkpoint_path:
+        raise ValueError("Both config_path and checkpoint_path must be provided, either directly or via experiment_path.")
+    return config_path, checkpoint_path
+
+
+def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint_path: str | None = None,
+                     experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
+                     precision: str = "bf16", seed: int = 0, render: bool = True, style_weights: str | None = None) -> list:
+    """``infer_file`` for many prompts of one writer: one ragged sampler call (``infer_batch``), ``./<output>_<i>.png`` per
+    prompt.  Returns the list of [L_i, 3] strokes."""
+    from .checkpoint import load_model
+    from .vis import show_strokes
+
+    prompts = list(prompts)
+    config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
+    style = load_style(source, style_weights)
+    model = load_model(config_path, checkpoint_path, precision=precision, max_B=max(1, len(prompts)), style_rows=style.shape[1])
+    strokes = infer_batch(prompts, style, model, diffusion_mode=diffusion_mode, seed=seed)
+    if render:
+        for i, s in enumerate(strokes):
+            show_strokes(s, scale=1, name=f"{output}_{i}", show_output=False)
     return strokes

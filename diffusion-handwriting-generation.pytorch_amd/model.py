@@ -53,6 +53,36 @@ def check_token_ids(text: torch.Tensor, seen: list | None = None) -> None:
         del seen[:-4]
 
 
+def check_lengths(lengths, B: int, L: int | None) -> list:
+    """Per-sample stroke lengths of a ragged batch (``sample(..., lengths=)`` / ``forward(..., lengths=)``) as a list of B
+    Python ints, checked on the host before any device is touched: integers (a sequence of ints or an integer tensor / array),
+    one per sample, each a multiple of 8 in [8, L] (``L`` None: the padded length is still to be chosen, max(lengths))."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+            raise ValueError(f"lengths must hold integers, got a {lengths.dtype} tensor")
+        if lengths.dim() != 1:
+            raise ValueError(f"lengths must be one-dimensional, got shape {tuple(lengths.shape)}")
+        vals = [int(v) for v in lengths.detach().to("cpu").tolist()]
+    else:
+        import numpy as np
+        try:
+            seq = list(lengths)
+        except TypeError:
+            raise ValueError(f"lengths must be a sequence or an integer tensor of B = {B} entries, got {type(lengths).__name__}") from None
+        vals = []
+        for i, v in enumerate(seq):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"lengths[{i}] = {v!r} is not an integer")
+            vals.append(int(v))
+    if len(vals) != B:
+        raise ValueError(f"lengths has {len(vals)} entries, the batch {B}")
+    hi = max(vals) if L is None and vals else L
+    for i, v in enumerate(vals):
+        if v < 8 or v > hi or v % 8:
+            raise ValueError(f"lengths[{i}] = {v}: every length must be a multiple of 8 in [8, L = {hi}]")
+    return vals
+
+
 class _DifferentiableForward(torch.autograd.Function):
     """``DiffusionModel.forward`` under autograd (reference train.py:46-60: ``model(x, text, sigma, style)`` ... ``loss.backward()``):
     the forward and backward passes of ``train_model.TrainModel`` (hand-written fp32 HIP ops, include/dhw_train.h) as ONE autograd
@@ -209,15 +239,26 @@ class DiffusionModel(nn.Module):
         return tm
 
     # ------------------------------------------------------------------ forward == reference model.py:121-182
-    def forward(self, strokes: torch.Tensor, text: torch.Tensor, sigma: torch.Tensor, style_vector: torch.Tensor):
+    def forward(self, strokes: torch.Tensor, text: torch.Tensor, sigma: torch.Tensor, style_vector: torch.Tensor, *, lengths=None):
         """strokes [B,T,2], text int [B,Lt] (0 = pad), sigma [B,1] or [B,1,1], style_vector [B,S,1280]
         -> (eps [B,T,2] fp32, pen_lifts [B,T] fp32 in (0,1), None).
+
+        ``lengths`` (keyword only, B ints, multiples of 8 in [8, T]): a ragged batch.  Row b is the forward of
+        ``strokes[b, :lengths[b]]`` alone; eps / pen past lengths[b] are 0 and the strokes there are ignored.  Inference only:
+        training stays uniform (the reference trains on fixed-length batches), so a train-mode or grad-recording call raises.
 
         With autograd recording and parameters that require gradients (after ``model.train()`` / ``requires_grad_(True)``) the
         outputs carry a graph back to the parameters: the call runs the fp32 training kernels (``train_model.TrainModel``) with
         dropout as ``self.training`` says, and ``loss.backward()`` fills ``p.grad`` as the reference's would (train.py:46-60).
         Gradients with respect to the INPUTS are not produced (the reference's training loop does not use them)."""
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        grad_path = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if lengths is not None:
+            if self.training or grad_path:
+                raise ValueError("lengths: ragged batches are inference-only (eval() and no gradient recording); training stays uniform")
+            if strokes.dim() != 3:
+                raise ValueError("strokes must be [B, T, 2]")
+            lens = check_lengths(lengths, strokes.shape[0], strokes.shape[1])
+        if grad_path:
             if strokes.dim() != 3 or strokes.shape[-1] != 2 or strokes.shape[1] % 8:
                 raise ValueError("strokes must be [B, T, 2] with T a multiple of 8")
             check_token_ids(text)
@@ -248,8 +289,12 @@ class DiffusionModel(nn.Module):
             eps = torch.empty((B, L, 2), device=dev, dtype=torch.float32)
             pen = torch.empty((B, L), device=dev, dtype=torch.float32)
             st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.lib().dhw_forward(h, s.data_ptr(), t.data_ptr(), sg.data_ptr(), sv.data_ptr(), B, L,
-                                              t.shape[1], eps.data_ptr(), pen.data_ptr(), C.c_void_p(st)), h)
+            if lengths is None:
+                _lib.check(_lib.lib().dhw_forward(h, s.data_ptr(), t.data_ptr(), sg.data_ptr(), sv.data_ptr(), B, L,
+                                                  t.shape[1], eps.data_ptr(), pen.data_ptr(), C.c_void_p(st)), h)
+            else:
+                _lib.check(_lib.lib().dhw_forward_ragged(h, s.data_ptr(), t.data_ptr(), sg.data_ptr(), sv.data_ptr(), B, L, t.shape[1],
+                                                         (C.c_int32 * B)(*lens), eps.data_ptr(), pen.data_ptr(), C.c_void_p(st)), h)
             # keep the inputs alive until the stream has consumed them
             for x in (s, t, sg, sv):
                 x.record_stream(torch.cuda.current_stream(dev))

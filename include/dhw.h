@@ -105,6 +105,23 @@ int dhw_sample(dhw_handle*, const int64_t* text, const float* style, int B, int 
                int T, int mode, const float* noise, uint64_t seed, int64_t first_sample,
                float* out, void* hip_stream);
 
+/* Ragged batches: samples of different stroke lengths in one call.  lens is a HOST pointer to B
+ * entries, each a multiple of 8 in [8, L]; L is the padded length (the row stride of every [B,L,..]
+ * tensor).  Row b computes exactly what the uniform call computes for sample b alone at L = lens[b]
+ * (dhw_sample_ragged: with first_sample + b; external noise: noise[:, b, :lens[b], :]).  Outputs past
+ * lens[b] are 0; inputs there (strokes, noise) are ignored, whatever they hold.  With every
+ * lens[b] == L the result is bit-identical to dhw_forward / dhw_sample.  The lengths are copied to a
+ * library-owned device buffer on hip_stream and read by the kernels at run time, so one captured graph
+ * serves every set of lengths of a (B, L, Lt, T, mode).  A bad entry -> DHW_ERR_ARG naming it.
+ * Every launch configuration supports lengths except the off-by-default persistent step:
+ * dhw_sample_ragged on a handle created with DHW_PERSIST=1 -> DHW_ERR_ARG naming the switch. */
+int dhw_forward_ragged(dhw_handle*, const float* strokes, const int64_t* text, const float* sigma,
+                       const float* style, int B, int L, int Lt, const int32_t* lens,
+                       float* eps_out, float* pen_out, void* hip_stream);
+int dhw_sample_ragged(dhw_handle*, const int64_t* text, const float* style, int B, int L, int Lt,
+                      const int32_t* lens, int T, int mode, const float* noise, uint64_t seed,
+                      int64_t first_sample, float* out, void* hip_stream);
+
 /* Host-only: beta_i = 0.02 + exp(linspace(ln 1e-5, ln 0.4, T)), abar = cumprod(1-beta), fp32. */
 int dhw_schedule(int T, float* beta_out, float* alpha_bar_out);
 
