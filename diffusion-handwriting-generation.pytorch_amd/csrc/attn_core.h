@@ -217,9 +217,6 @@ template <typename T> DHW_DEV void vt_store_piece(char* row, int part, const uin
   *reinterpret_cast<uint4*>(row + part * 16) = v;
 }
 
-#ifndef DHW_ATT_ABL
-#define DHW_ATT_ABL 0   // diagnostic builds only: bit0 = no MFMAs, bit1 = no exponentials, bit2 = no LDS operand reads, bit3 = no max / rescale
-#endif
 template <int D, int KB, bool MASKED, int NU, bool TAIL>
 DHW_DEV void attn_block_bf16(int lane, const Frag<bf16_t> (*qf)[(D + 31) / 32], const char* const (&kt)[NU], int SK, const char* const (&vt)[NU], int SV, int kb,
                              unsigned padbits, int Lk, float (&m_run)[NU], float (&l_run)[NU], f32x4 (*o)[D / 16]) {
@@ -233,13 +230,9 @@ DHW_DEV void attn_block_bf16(int lane, const Frag<bf16_t> (*qf)[(D + 31) / 32], 
   const int g = lane >> 4;
   const float c = rsqrtf((float)D) * 1.4426950408889634f;
   f32x4 s[NU][NTILE];
-  // DHW_ATT_KPF (round 5): a unit's NTILE x KCH key fragments are all requested BEFORE its QK^T MFMAs (hipcc otherwise places each
-  // ds_read_b128 directly in front of the MFMA that consumes it: one LDS round trip per MFMA, as in the GEMM main loops — gemm_core.h, run_p);
-  // 2 = both units' fragments before the first MFMA.  Same reads, same MFMAs: bit-identical.
-#ifndef DHW_ATT_KPF
-#define DHW_ATT_KPF 1
-#endif
-  if constexpr (DHW_ATT_KPF != 0 && DHW_ATT_ABL == 0) {
+  // A unit's NTILE x KCH key fragments are all requested BEFORE its QK^T MFMAs, the next unit's under this unit's MFMAs (hipcc otherwise places
+  // each ds_read_b128 directly in front of the MFMA that consumes it: one LDS round trip per MFMA, as in the GEMM main loops — gemm_core.h, run_p).
+  {
     Frag<T> kf[NU][NTILE][KCH];
     auto request = [&](int u) {
 #pragma unroll
@@ -255,35 +248,13 @@ DHW_DEV void attn_block_bf16(int lane, const Frag<bf16_t> (*qf)[(D + 31) / 32], 
         for (int ch = 0; ch < KCH; ++ch) mma32(s[u][t], kf[u][t][ch], qf[u][ch]);
       }
     };
-    if constexpr (DHW_ATT_KPF == 2) {
+    request(0);
 #pragma unroll
-      for (int u = 0; u < NU; ++u) request(u);
+    for (int u = 0; u < NU; ++u) {
+      if (u + 1 < NU) request(u + 1);
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < NU; ++u) multiply(u);
-    } else {
-      request(0);
-#pragma unroll
-      for (int u = 0; u < NU; ++u) {
-        if (u + 1 < NU) request(u + 1);     // the next unit's fragments fly under this unit's MFMAs
-        __builtin_amdgcn_sched_barrier(0);
-        multiply(u);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  } else {
-#pragma unroll
-  for (int u = 0; u < NU; ++u)
-#pragma unroll
-    for (int t = 0; t < NTILE; ++t) {
-      s[u][t] = (f32x4){0, 0, 0, 0};
-#pragma unroll
-      for (int ch = 0; ch < KCH; ++ch)
-      {
-        const Frag<T> kf = (DHW_ATT_ABL & 4) ? qf[u][ch] : frag_load(reinterpret_cast<const T*>(kt[u] + t * 16 * SK) + 32 * ch + 8 * g);
-        if constexpr (DHW_ATT_ABL & 1) { asm volatile("" ::"v"(kf.v)); s[u][t][ch] += (float)kf.v[0]; }
-        else mma32(s[u][t], kf, qf[u][ch]);
-      }
+      multiply(u);
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
 #pragma unroll
@@ -317,7 +288,7 @@ DHW_DEV void attn_block_bf16(int lane, const Frag<bf16_t> (*qf)[(D + 31) / 32], 
     for (int t = 0; t < DT; ++t)
 #pragma unroll
       for (int pp = 0; pp < NPF; ++pp)
-        vf[u][t][pp] = (DHW_ATT_ABL & 4) ? qf[u][0] : frag_load_tr(vt[u] + 32 * t + (32 * pp) * SV, vt[u] + 32 * t + (32 * pp + 16) * SV);
+        vf[u][t][pp] = frag_load_tr(vt[u] + 32 * t + (32 * pp) * SV, vt[u] + 32 * t + (32 * pp + 16) * SV);
   __builtin_amdgcn_sched_barrier(0);
   float m_new[NU], alpha[NU];
 #pragma unroll
@@ -325,7 +296,7 @@ DHW_DEV void attn_block_bf16(int lane, const Frag<bf16_t> (*qf)[(D + 31) / 32], 
     float mx = fmaxf(fmaxf(s[u][0][0], s[u][0][1]), fmaxf(s[u][0][2], s[u][0][3]));
 #pragma unroll
     for (int t = 1; t < NTILE; ++t) mx = fmaxf(fmaxf(mx, fmaxf(s[u][t][0], s[u][t][1])), fmaxf(s[u][t][2], s[u][t][3]));
-    m_new[u] = (DHW_ATT_ABL & 8) ? 0.f : fmaxf(m_run[u], xg_max(mx));   // finite: every block has >= 1 real key
+    m_new[u] = fmaxf(m_run[u], xg_max(mx));   // finite: every block has >= 1 real key
     alpha[u] = __builtin_amdgcn_exp2f(m_run[u] - m_new[u]);   // exp2(-inf) = 0 in the first block
     m_run[u] = m_new[u];
   }
@@ -338,7 +309,7 @@ DHW_DEV void attn_block_bf16(int lane, const Frag<bf16_t> (*qf)[(D + 31) / 32], 
     for (int t = 0; t < NTILE; ++t) {
       s[u][t] = s[u][t] - m_new[u];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) s[u][t][r] = (DHW_ATT_ABL & 2) ? s[u][t][r] : __builtin_amdgcn_exp2f(s[u][t][r]);
+      for (int r = 0; r < 4; ++r) s[u][t][r] = __builtin_amdgcn_exp2f(s[u][t][r]);
       psum += s[u][t];
     }
     l_run[u] = __builtin_fmaf(l_run[u], alpha[u], (psum[0] + psum[1]) + (psum[2] + psum[3]));
@@ -356,41 +327,8 @@ DHW_DEV void attn_block_bf16(int lane, const Frag<bf16_t> (*qf)[(D + 31) / 32], 
 #pragma unroll
     for (int t = 0; t < DT; ++t)
 #pragma unroll
-      for (int pp = 0; pp < NPF; ++pp) {
-        if constexpr (DHW_ATT_ABL & 1) { asm volatile("" ::"v"(vf[u][t][pp].v)); o[u][t][pp] += (float)vf[u][t][pp].v[0]; }
-        else mma32(o[u][t], vf[u][t][pp], pf[u][pp]);
-      }
+      for (int pp = 0; pp < NPF; ++pp) mma32(o[u][t], vf[u][t][pp], pf[u][pp]);
 }
-// One unit — 16 query rows of head h — against KB keys of the staged tiles starting at tile row `krow` (sample key index `kb`): the
-// building block of the key-split wave layout of enc_bc_core.h (DHW_ATT_KSPLIT), where the two waves of a row group share the
-// third head's keys, 32 each.  kt / vt: the staged K / V tiles ([keys][channels], row strides SK / SV bytes).
-template <int KB>
-DHW_DEV void attn_unit_bf16(int lane, const Frag<bf16_t> (&qf)[2], const char* kt, int SK, const char* vt, int SV, int h, int krow, int kb, int Lk,
-                            float& m, float& l, f32x4 (&o)[4]) {
-  const int l15 = lane & 15, g = lane >> 4;
-  const char* const ktu[1] = {kt + (krow + l15) * SK + h * 128};
-  const char* const vtu[1] = {vt + (krow + 4 * g + (l15 >> 2)) * SV + 8 * (l15 & 3) + h * 128};
-  float m1[1] = {m}, l1[1] = {l};
-  if (kb + KB > Lk) attn_block_bf16<64, KB, false, 1, true>(lane, &qf, ktu, SK, vtu, SV, kb, 0u, Lk, m1, l1, &o);
-  else attn_block_bf16<64, KB, false, 1, false>(lane, &qf, ktu, SK, vtu, SV, kb, 0u, Lk, m1, l1, &o);
-  m = m1[0];
-  l = l1[0];
-}
-
-// (m, l, o) <- the running-softmax state over the union of this wave's keys and another wave's (its state at ms: o as 4 x f32x4, then
-// max, then this lane's partial sum; maxima in log2 units as attn_block_bf16 keeps them).  One function, no implicit contraction: every
-// kernel that merges gets the same bits.  exp2(-inf) = 0: an empty partner state leaves this one unchanged (this one is never empty).
-DHW_DEV void attn_merge_state(float& m, float& l, f32x4 (&o)[4], const float* ms) {
-#pragma clang fp contract(off)
-  const float m1 = ms[16], l1 = ms[17];
-  const float mm = fmaxf(m, m1);
-  const float a0 = __builtin_amdgcn_exp2f(m - mm), a1 = __builtin_amdgcn_exp2f(m1 - mm);
-  l = l * a0 + l1 * a1;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) o[t] = o[t] * a0 + *reinterpret_cast<const f32x4*>(ms + 4 * t) * a1;
-  m = mm;
-}
-
 // One KB-key block for the UMAX (1 or 2) units of a wave: unit u = head hs + u * HS, active when that head exists (the
 // second unit of a wave may not).  kt / vt: the staged tiles (row stride SK / SV bytes); head h lies h * 64 channels further:
 // columns of the K tile and of the bf16 V tile ([keys][channels]), rows of the fp32 V^T tile ([channels][keys]).

@@ -109,30 +109,17 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
   constexpr int MT2 = BM / WM2 / 16, NT2 = T2 / WN2;
   static_assert(NT1 * WN1 == T1 && NT2 * WN2 == T2 && MT1 * 16 * WM1 == BM1 && WM1 * WN1 <= NW && WM2 * WN2 <= NW, "unsupported tile / wave layout");
   static_assert(!ASYM || WM1 == 1, "the asymmetric tiling: blocks with one row group in conv1");
-#ifndef DHW_HEADS_PRE
-#define DHW_HEADS_PRE 0   // measured neutral (18.120 vs 18.086 ms on a noisy box, profiles/r05_spread_ab.log r5av): off
-#endif
-#ifndef DHW_CONV_STROKES_ONCE
-#define DHW_CONV_STROKES_ONCE 1
-#endif
-#ifndef DHW_CONV_FCX
-#define DHW_CONV_FCX 1
-#endif
-#ifndef DHW_CONV_SPREAD
-#define DHW_CONV_SPREAD 0   // measured neutral (18.763 vs 18.764 ms, profiles/r05_spread_ab.log): off
-#endif
-  constexpr bool CSPREAD = DHW_CONV_SPREAD != 0 && sizeof(T) == 2;
   constexpr bool PPX = PP != 0;
   static_assert(!PPX || (TALL && WM1 == 2 && WN1 == 4 && CH == 0 && !ASYM && OCC == 1), "ping-pong: the 2 x 4 wave layouts of the tall tiles");
   constexpr int RING = (ES == 2 ? 24 : 12) * (CO == 256 ? 2 : 3) / 3 / (OCC * NW > 8 ? OCC : 1);   // fewer fragments in flight for the widest block / at 2 WGs per CU (VGPR budget)
 
-  // (DHW_UNIFORM_WAVE: the wave index as a scalar — `wave < 6` of the 192-channel blocks, whose layouts leave two waves without channels, is then a
+  // (the wave index as a scalar — `wave < 6` of the 192-channel blocks, whose layouts leave two waves without channels, is then a
   // scalar branch instead of an exec mask)
   // this sample's rows at this level (ragged batches: p.lens; p.L is then the padded length and stays the row stride).  A tile that
   // starts at or past the end has no row to write: the whole workgroup leaves before its first barrier.
   const int Ls = sample_len(p.lens, p.lsh, b, p.L);
   if constexpr (DHW_LENS) { if (m0 >= Ls) return; }
-  const int tid = body_tid(), lane = tid & 63, wave = DHW_UNIFORM_WAVE ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
+  const int tid = body_tid(), lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, g = lane >> 4;
   const int Cin = SK ? CIN : p.Cin;
   // ping-pong: the upper row half (waves NW/2 ..) leads by one phase; a scalar, so the skew barriers sit in scalar branches
@@ -151,13 +138,11 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
   // idle waves only join the barriers / copies.  When a layout uses all NW waves the flag must FOLD to true: a run-time
   // `if (act)` around a stage whose loads are consumed inside it leaves, on the (never taken) skip path, loads that were
   // never waited for, and hipcc's s_waitcnt merge at the join then drains the next stage's weight prefetch (r2, .s).
-  // DHW_CONV_DUP (round 5; gemm_core.h): in the 192-channel blocks (6 channel groups on 8 waves) the two spare waves REPEAT waves 0, 1 — the same tiles,
-  // the same values to the same LDS addresses — so that the flags fold here too: behind a run-time `if (act)` hipcc drained the weight ring in front of
-  // every main loop of these blocks (s_waitcnt vmcnt(2) / (1) / (0) behind their barriers, vmcnt(11 .. 21) in the other blocks).
-  constexpr bool DUP1 = DHW_CONV_DUP != 0 && ES == 2 && NW == 8 && WM1 == 1 && WN1 < NW, DUP2 = DHW_CONV_DUP != 0 && ES == 2 && NW == 8 && WM2 == 1 && WN2 < NW;
-  const bool act1 = DUP1 ? true : (WM1 * WN1 == NW || wave < WM1 * WN1), act2 = DUP2 ? true : (WM2 * WN2 == NW || wave < WM2 * WN2);
-  const int wm1 = DUP1 ? 0 : (act1 ? wave / WN1 : 0), wn1 = DUP1 ? wave % WN1 : (act1 ? wave % WN1 : 0), row01 = wm1 * (BM1 / WM1), nt01 = wn1 * NT1;
-  const int wm2 = DUP2 ? 0 : (act2 ? wave / WN2 : 0), wn2 = DUP2 ? wave % WN2 : (act2 ? wave % WN2 : 0), row02 = wm2 * (BM / WM2), nt02 = wn2 * NT2;
+  // (The 192-channel blocks — 6 channel groups on 8 waves — keep the run-time flag; letting the spare waves repeat waves 0, 1 so that it folds measured
+  // no faster: DESIGN.md 14.3e, 16.)
+  const bool act1 = WM1 * WN1 == NW || wave < WM1 * WN1, act2 = WM2 * WN2 == NW || wave < WM2 * WN2;
+  const int wm1 = act1 ? wave / WN1 : 0, wn1 = act1 ? wave % WN1 : 0, row01 = wm1 * (BM1 / WM1), nt01 = wn1 * NT1;
+  const int wm2 = act2 ? wave / WN2 : 0, wn2 = act2 ? wave % WN2 : 0, row02 = wm2 * (BM / WM2), nt02 = wn2 * NT2;
   const int n1 = nt01 * 16 + 4 * g, n2 = nt02 * 16 + 4 * g;   // this lane's first channel in each layout
   const int KCin = Cin / 32;
 
@@ -226,14 +211,9 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
     acc_zero(acc);
     ringu.template run_s<MTG, 3 * UCH / 32>(acc, HS + (rowu0 + l15) * SHh + g * 8 * ES, SHh, KCh);
     STAMP(11);
-    // conv1's first weight fragments fly during this stage's epilogue.  DHW_CONV_SPREAD (round 5): requested in quarters BETWEEN its pieces — 758 vector
-    // instructions per wave, the block's longest epilogue — instead of as one burst in front of it (a wave sits in instruction issue until the CU's
-    // L1 path has accepted its whole request: enc_bc_core.h, DHW_ENC_SPREAD)
-    constexpr int FC1 = decltype(ring1)::template fill_chunks<KT1>(), FQ1 = (FC1 + 3) / 4;
-    const T* w1p = reinterpret_cast<const T*>(p.w_c1) + ((size_t)nt01 * KCin * 3 * 64 + lane) * 8;
+    // conv1's first weight fragments fly during this stage's epilogue (one burst: spread between its pieces they measured neutral)
     if (act1) {
-      if constexpr (CSPREAD) { ring1.template fill_begin<KT1>(w1p); ring1.template fill_range<KT1, 0, FQ1>(); }
-      else fill1();   // flies during the epilogue
+      fill1();
       ep1.load(p.b_c1, gam + p.f1, bet + p.f1, n1);
     }
     {
@@ -247,17 +227,14 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
           const int r = min(rowu0 + j * 16 + l15, RX - 1);   // (clamped: rows past RX are computed but never stored)
           acc[i][j] = round_to<T>(acc[i][j] + epu.bias[i] + load4(reinterpret_cast<const T*>(XR + r * SX) + nu + 16 * i));
         }
-      if constexpr (CSPREAD) { if (act1) ring1.template fill_range<KT1, FQ1, 2 * FQ1>(); }
       // (a 16-byte store covers the partner lane's `low` values too: its data depends, through the lane swap, on both lanes'
       // loads of the pair, so no store can be issued ahead of them)
       store_tiles<T, NTU, MTG>(lane, XR, SX, rowu0, nu, acc, keep, valid);
-      if constexpr (CSPREAD) { if (act1) ring1.template fill_range<KT1, 2 * FQ1, 3 * FQ1>(); }
       CB_SILU_TILES(NTU, MTG, acc);
-      if constexpr (CSPREAD) { if (act1) ring1.template fill_range<KT1, 3 * FQ1, FC1>(); }
       store_tiles<T, NTU, MTG>(lane, XS, SX, rowu0, nu, acc, keep, valid);
     }
     STAMP(12);
-  } else if (p.strokes && SK && DHW_CONV_STROKES_ONCE && NTHR % (CIN / 4 > 0 ? CIN / 4 : 1) == 0) {
+  } else if (p.strokes && SK && NTHR % (CIN / 4 > 0 ? CIN / 4 : 1) == 0) {
     // enc1: x = input_dense(strokes) = W[:,0]*dx + W[:,1]*dy + b, evaluated in place of a load.  A thread's 4 channels are the same in every pass over
     // the rows (the thread count is a multiple of the items per row), so its 12 weights / biases are requested ONCE and the stroke points of all its
     // rows up front: the loop below then holds no load at all.  (As one loop of load - compute - store per item — the form below — the stage was
@@ -430,8 +407,8 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
   acc_zero(acc);
   if (act2) {
     const T* wsk = reinterpret_cast<const T*>(p.w_skip) + ((size_t)nt02 * KCin * 3 * 64 + lane) * 8;
-    // (DHW_CONV_FCX: conv_skip's first fragments requested under fc's MFMAs — run_n — instead of as one burst behind them)
-    constexpr bool FCX = SK && (DHW_CONV_FCX != 0) && CO / 32 <= decltype(ring2)::D && DHW_ABL == 0;
+    // (FCX: conv_skip's first fragments requested under fc's MFMAs — run_n — instead of as one burst behind them)
+    constexpr bool FCX = SK && CO / 32 <= decltype(ring2)::D && DHW_ABL == 0;
     if constexpr (FCX) ring2.template run_n<MT2, CO / 32, KT1>(acc, H2 + (row02 + l15) * SH2 + g * 8 * ES, SH2, CO / 32, wsk);
     else ring2.template run_s<MT2, CO / 32>(acc, H2 + (row02 + l15) * SH2 + g * 8 * ES, SH2, CO / 32);
     STAMP(6);
@@ -471,11 +448,6 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
       // eps / pen heads (model.py:179-182) + scheduler step straight from the fp32 tile: 4 lanes per stroke row
       const int r = tid >> 2, q = tid & 3;
       float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-      // (DHW_HEADS_PRE: what the scheduler step reads — biases, seed, sampler state, noise — requested, and the Philox draw computed, in front of the
-      // dot products; rows past the tile read row m0's)
-      const long hrow = (long)b * p.L + m0 + (r < rows_valid ? r : 0);
-      HeadsPre hpre;
-      if constexpr (DHW_HEADS_PRE != 0) heads_prefetch(p.hp, hrow, hpre);
       if (r < rows_valid) {
         const float* xr = reinterpret_cast<const float*>(smem + r * SO);
         // (unrolled: the 3 x CO / 16 weight pieces are requested together — rolled, every pass waited for its own three loads: CO / 16 dependent
@@ -496,10 +468,7 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
         a1 += __shfl_xor(a1, o);
         a2 += __shfl_xor(a2, o);
       }
-      if (r < rows_valid && q == 0) {
-        if constexpr (DHW_HEADS_PRE != 0) heads_finish_pre(p.hp, hrow, a0, a1, a2, hpre);
-        else heads_finish(p.hp, (long)b * p.L + m0 + r, a0, a1, a2);
-      }
+      if (r < rows_valid && q == 0) heads_finish(p.hp, (long)b * p.L + m0 + r, a0, a1, a2);
     }
   } else {
     if (act2) {
@@ -511,8 +480,7 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
     }
     CB_BARRIER();
     if constexpr (PPX) { if (pp_lead) CB_BARRIER(); }   // the trailing half stores its rows one slot later
-    if constexpr (DHW_COPY_UNROLL != 0 && !(DHW_ABL & 16)) tile_copy_out_u<T, BM, CO, NTHR>(smem, SH2, reinterpret_cast<T*>(p.out) + (size_t)(b * p.L + m0) * CO, CO, rows_valid, tid);
-    else if constexpr (!(DHW_ABL & 16))
+    if constexpr (!(DHW_ABL & 16))
     tile_copy_out<T>(smem, SH2, reinterpret_cast<T*>(p.out) + (size_t)(b * p.L + m0) * CO, CO, rows_valid, CO, tid, NTHR);
     if (p.pool && !(DHW_ABL & 16))   // AvgPool1d(2) side output (model.py:93); m0 and rows_valid are even
       tile_copy_out_pool<T>(smem, SH2, reinterpret_cast<T*>(p.pool) + ((size_t)b * (p.L / 2) + m0 / 2) * CO, CO, rows_valid, CO, tid, NTHR);

@@ -144,6 +144,10 @@ constexpr size_t enc_a_text_kv_bytes() {
 // row stride (elements) of the layer's [q2 | k2 (| v2)] buffer: the bf16 kernels keep v2 beside q2 / k2, row-major (attn_core.h)
 template <typename T, int DM> constexpr int qkv_stride() { return sizeof(T) == 2 ? 3 * DM : 2 * DM; }
 
+// Waves that own channels in a GEMM stage of the EncoderLayer kernels.  d = 192 has 12 channel tiles of 16: 6 waves x 2 (4 waves x 3, one per SIMD,
+// and 2 row groups x 4 waves measured within +-0.3 %: DESIGN.md 16).
+template <int DM> constexpr int enc_wn() { return DM % 128 == 0 ? 8 : 6; }
+
 // enc_a for the BM-row tile [m0, m0+BM) of sample b, of which the first rows_valid rows are this workgroup's to write.
 // p.x == null: the x tile is already in m.XR (written by the caller's previous stage, behind a barrier) — this is how a
 // ConvBlock or the previous layer's enc_bc continues into the next layer without a launch boundary.  VPIECE = bytes per
@@ -155,18 +159,15 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
   // GEMM stages: every wave covers all BM rows and 1/WN of the channels, so no two waves stream the same weight
   // fragments (row groups would re-fetch them: the L2 -> CU weight stream is what bounds these kernels).  DM = 192 has
   // 12 channel tiles: 6 waves take 2 each, the other 2 waves only join the barriers (and the attention stage).
-  constexpr int WN = (DM % 128 == 0) ? 8 : (sizeof(T) == 4 ? 6 : DHW_WN192), WM = (DM % 128 == 0 || sizeof(T) == 4) ? 1 : DHW_WM192;
+  constexpr int WN = enc_wn<DM>(), WM = 1;
   constexpr int MT = BM / WM / 16, NT = DM / WN / 16, H = DM / 64, KC = DM / 32;
   static_assert(NT * WN * 16 == DM, "channel tiles must divide over the waves");
   const int tid = body_tid(), lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, g = lane >> 4;
-  // DHW_ENC_DUP (round 5): where the layout leaves waves without channels (DM = 192: 6 x 2 tiles on 8 waves), the spare waves REPEAT waves 0, 1 — the
-  // same tiles, the same values, written to the same LDS addresses — instead of skipping the stages.  With a run-time `if (act)` around every stage hipcc's
-  // s_waitcnt bookkeeping loses the weight ring at each join and drains it in front of every main loop (vmcnt(2) / (1) / (0) behind the barriers of the
-  // d = 192 kernels where the others wait vmcnt(15 .. 26)); with `act` folded away the code is the straight line of the 8-wave layouts.
-  constexpr bool DUP = DHW_ENC_DUP != 0 && sizeof(T) == 2 && WM == 1 && WN < 8;
-  const bool act = DUP ? true : (WN * WM == 8 || wave < WN * WM);   // (DM = 192, 6 x 1 without DUP: waves 6, 7 own no channels in the GEMM stages)
-  const int wm = DUP ? 0 : (act ? wave / WN : 0), wn = DUP ? wave % WN : (act ? wave % WN : 0);
+  // (DM = 192: waves 6, 7 own no channels in the GEMM stages.  A run-time `if (act)` around a stage makes hipcc drain the weight ring at the join;
+  // letting the spare waves repeat waves 0, 1 instead removed the drains and measured no faster: DESIGN.md 14.3e, 16)
+  const bool act = WN * WM == 8 || wave < WN * WM;
+  const int wm = act ? wave / WN : 0, wn = act ? wave % WN : 0;
   const int S = tile_stride<T>(DM);
   const int Ls = sample_len(p.lens, p.lsh, b, p.Lk);   // this sample's rows (ragged batches; p.Lk stays the row stride)
   char* XR = m.XR;
@@ -180,36 +181,13 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
   const char* xop = XR + (row0 + l15) * S + g * 8 * ES;
   const char* qop = QR + (row0 + l15) * S + g * 8 * ES;
 
-#ifndef DHW_ENC_XSTREAM
-#define DHW_ENC_XSTREAM 0   // measured: 19.05 vs 18.98 ms per 60-step batch (profiles/r04_xstream_ab.log) -> off
-#endif
-#ifndef DHW_ENC_EARLYFILL
-#define DHW_ENC_EARLYFILL 0   // measured 19.13 vs 19.08 ms (profiles/r04_earlyfill_ab.log): the prefetch queues in front of the K / V block the attention waits for
-#endif
-  // DHW_ENC_EARLYA (round 5): the dense stage's first weight fragments requested in the q1 epilogue, IN FRONT of the cross attention — here, unlike in
-  // enc_bc (DHW_ENC_EARLYFILL, r4: slower), no K / V loads follow them: the text K / V tiles were staged at the top of the kernel, so the request
-  // rides under the attention's LDS / MFMA / softmax work instead of standing as one burst between the attention and its barrier.
-  // MEASURED: 17.466 vs 17.454 ms without (profiles/r05_spread_ab.log, r5am): no gain — the attention's own LDS traffic and the request share the wave's issue.  Off.
-#ifndef DHW_ENC_EARLYA
-#define DHW_ENC_EARLYA 0
-#endif
-  constexpr bool EARLYA = sizeof(T) == 2 && (DHW_ENC_EARLYFILL || (DHW_ENC_EARLYA && !(DM == 384 && BM >= 32)));   // (d = 384 on 32-row tiles: the ring's registers across the attention spill)
-  constexpr bool XS = sizeof(T) == 2 && DHW_ENC_XSTREAM && !(DM == 384 && BM >= 32);   // (d = 384 with 32-row tiles: two accumulator rows + the ring spill)   // cross-stage weight stream with whole-stage rings (gemm_core.h, run_x)
-  constexpr int XDE = KC <= 8 ? KC : 8;   // ring depth (chunks) of the cross-stage stream: a whole stage at d = 192 / 256, 8 of 12 chunks at d = 384
-#ifndef DHW_RINGA384
-#define DHW_RINGA384 24   // fragments in flight per wave in enc_a's d = 384 stages on 16-row tiles (experiments: 30 / 36 = a whole stage)
-#endif
-  constexpr int RINGA = sizeof(T) == 4 ? 12 : (DM == 384 && BM == 16 ? DHW_RINGA384 : 24);
-  typedef WRing<T, NT, (XS ? XDE * NT : RINGA), (XS ? XDE : (RINGA + NT - 1) / NT)> RingT;
+  constexpr int RINGA = sizeof(T) == 4 ? 12 : 24;   // weight fragments in flight per wave (30 / 36, a whole d = 384 stage, measured no faster)
+  typedef WRing<T, NT, RINGA, (RINGA + NT - 1) / NT> RingT;
   RingT ring;
-#ifndef DHW_ENC_QALT
-#define DHW_ENC_QALT 1
-#endif
-#ifndef DHW_ENC_SPREAD
-#define DHW_ENC_SPREAD 11  // bit 0: enc_bc's stages (enc_bc_core.h), bit 1: enc_a's
-#endif
-  constexpr bool SPREADA = sizeof(T) == 2 && (DHW_ENC_SPREAD & 2) != 0 && !XS;
-  constexpr bool SPREADQ = sizeof(T) == 2 && (DHW_ENC_SPREAD & 8) != 0 && !XS && MT > 1;   // bit 3: the q / k / v chunks of the multi-row-tile layouts
+  // a stage's first weight fragments are requested in pieces between the parts of the previous epilogue (enc_bc_core.h, SPREAD); SPREADQ: the
+  // same around the staged copy-out of the q / k / v chunks of the multi-row-tile layouts.  The fp32 parity mode keeps the burst (fill_s).
+  constexpr bool SPREADA = sizeof(T) == 2;
+  constexpr bool SPREADQ = sizeof(T) == 2 && MT > 1;
   constexpr int FCHA = RingT::template fill_chunks<KC>(), FQA = (FCHA + 3) / 4;
   EpiParams<NT> ep;
   ENC_STAMP(0);
@@ -227,19 +205,9 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
   const T* v1s = reinterpret_cast<const T*>(p.vt1) + (VROW ? (size_t)b * p.Lt * DM : (size_t)b * DM * p.lpadT);   // v1 [Lt][DM] / V^T [DM][lpadT]
   constexpr bool PLDS = enc_plds<T>();
   const float* PL = m.PL;   // [b_q1 | b_d1 | gamma1 | beta1 | b_qkv2 x 3], DM floats each
-  // DHW_ENC_KVLATE (round 5, bf16): the text K / V tiles are needed only behind q1, so they are requested BEHIND the q1 weights and written to LDS
-  // behind the q1 stage: the kernel (or, chained behind a ConvBlock / an enc_bc, this half) starts its first GEMM after ONE memory round trip —
-  // parameters + x tile, with the weights right behind them — instead of two (tiles, then weights requested once the tiles had been stored).
-  // MEASURED: 19.284 ms against 19.239 without and 19.270 for the build before (profiles/r05_spread_ab.log, r5an): no gain — the bytes through the CU's L1 path
-  // are the same and that path, not the number of round trips, sets the start-up time.  Off.
-#ifndef DHW_ENC_KVLATE
-#define DHW_ENC_KVLATE 0
-#endif
-  constexpr bool KVLATE = sizeof(T) == 2 && DHW_ENC_KVLATE != 0;
   const int64_t* trow = p.text ? p.text + (size_t)b * p.Lt : nullptr;
   PadMask<KBC> pad;   // key-padding mask of the first block: requested here, used after q1
   struct KVRegs { CopyRegs<UK> ck; CopyRegs<UV> cv; };
-  KVRegs kv_late;   // (KVLATE: alive across the q1 stage)
   auto kv_store = [&](KVRegs& kv) {
     CopyRegs<UK>& ck = kv.ck;
     CopyRegs<UV>& cv = kv.cv;
@@ -254,7 +222,9 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
   };
   {
     KVRegs kv_now;
-    KVRegs& kv = [&]() -> KVRegs& { if constexpr (KVLATE) return kv_late; else return kv_now; }();
+    // (the reference through a call keeps hipcc's register allocation of three fp32 parity kernels — d = 192, and d = 384 on 16 rows — byte-identical
+    // to the build the fp32 figures of DESIGN.md were measured on; a plain `KVRegs& kv = kv_now` renumbers their registers, nothing else)
+    KVRegs& kv = [&]() -> KVRegs& { return kv_now; }();
     CopyRegs<UK>& ck = kv.ck;
     CopyRegs<UV>& cv = kv.cv;
     CopyRegs<UX> cx;
@@ -266,7 +236,6 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
     if (p.x)
       cx.load(BM * CPR, tid, 512, [&](int id) { const int r = id / CPR, cc = id - r * CPR;
                                                 return reinterpret_cast<const uint4*>(xs + (size_t)(b * p.Lk + (m0 + r < p.Lk ? m0 + r : p.Lk - 1)) * DM + cc * EPV); });
-    if constexpr (KVLATE) { if (act) ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_q1) + wlane); }
     ck.load(KBC * CPR, tid, 512, [&](int id) { const int r = id / CPR, cc = id - r * CPR;
                                                return reinterpret_cast<const uint4*>(k1s + (size_t)(r < p.Lt ? r : p.Lt - 1) * DM + cc * EPV); });
     if constexpr (VROW)
@@ -278,14 +247,14 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
     if (p.x)
       cx.store(BM * CPR, tid, 512, [&](int id) { const int r = id / CPR, cc = id - r * CPR; return reinterpret_cast<uint4*>(XR + r * S + cc * 16); },
                [&](int id) { return m0 + id / CPR < Ls; });
-    if constexpr (!KVLATE) kv_store(kv);
+    kv_store(kv);
     if constexpr (PLDS) cp.template store<DM>(m.PL, tid);
   }
   pad.load(lane, trow, 0, p.Lt);
   // the q1 weights are requested BEHIND the staging loads: a wave's loads complete in order and the L1 miss queue is
   // shared, so a 24 KB-per-wave prefetch in front of them delays the tiles everything waits for
   if (act) {
-    if constexpr (!KVLATE) ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_q1) + wlane);
+    ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_q1) + wlane);
     if constexpr (!PLDS) ep.load_bias(p.b_q1, n0);
   }
   lds_barrier();
@@ -303,18 +272,13 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
     ring.template run_s<MT, KC>(acc, xop, S, KC);
     ENC_STAMP(8);
     if constexpr (PLDS) ep.lds_bias(PL, n0);
-    // the dense stage's first weight fragments: requested in front of the cross attention (the vector-memory path is idle during
-    // it), not behind it — in halves around the q1 tile's stores
-    if constexpr (EARLYA) { ring.template fill_begin<KC>(reinterpret_cast<const T*>(p.w_d1) + wlane); ring.template fill_range<KC, 0, 2 * FQA>(); }
 #pragma unroll
     for (int i = 0; i < NT; ++i)
 #pragma unroll
       for (int j = 0; j < MT; ++j) acc[i][j] += ep.bias[i] + pb[i][j];
     enc_store_tiles<T, NT, MT>(lane, QR, S, row0, n0, acc);
     ENC_STAMP(9);
-    if constexpr (EARLYA) ring.template fill_range<KC, 2 * FQA, FCHA>();
   }
-  if constexpr (KVLATE) kv_store(kv_late);
   lds_barrier();
   ENC_STAMP(2);
 
@@ -361,7 +325,8 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
     }
   }
   if (act) {
-    if constexpr (!EARLYA) ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_d1) + wlane);   // in flight across the barrier
+    // behind the cross attention: requested in front of it, the fragments share the wave's issue with the attention's LDS traffic (no gain)
+    ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_d1) + wlane);   // in flight across the barrier
     if constexpr (!PLDS) ep.load(p.b_d1, gam + p.f1, bet + p.f1, n0);
   }
   lds_barrier();
@@ -371,12 +336,11 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
     f32x4 acc[NT][MT];
     acc_zero(acc);
     if (act) {
-      if constexpr (XS) ring.template run_x<MT, KC, 0, KC>(acc, qop, S, KC, reinterpret_cast<const T*>(p.w_qkv2) + wlane);   // + the q2 chunk's weights
-      else ring.template run_s<MT, KC>(acc, qop, S, KC);
+      ring.template run_s<MT, KC>(acc, qop, S, KC);
       ENC_STAMP(10);
-      // the q2 chunk's first fragments: spread through the LayerNorm epilogue (SPREADA, as enc_bc_core.h DHW_ENC_SPREAD) or one burst in front of it
+      // the q2 chunk's first fragments: spread through the LayerNorm epilogue (SPREADA) or one burst in front of it
       if constexpr (SPREADA) { ring.template fill_begin<KC>(reinterpret_cast<const T*>(p.w_qkv2) + wlane); ring.template fill_range<KC, 0, FQA>(); }
-      else if constexpr (!XS) ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_qkv2) + wlane);   // q2 chunk: flies during the LayerNorm epilogue
+      else ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_qkv2) + wlane);
       if constexpr (PLDS) ep.lds(PL + DM, PL + 2 * DM, PL + 3 * DM, n0);
 #pragma unroll
       for (int i = 0; i < NT; ++i)
@@ -397,23 +361,19 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
 #pragma unroll
         for (int j = 0; j < MT; ++j)
           acc[i][j] = acc[i][j] * ep.gam[i] + ep.bet[i] + load4(reinterpret_cast<const T*>(XR + (row0 + j * 16 + l15) * S) + n0 + 16 * i);
-      // (DUP: the spare waves repeat waves 0, 1 — this is the one stage that updates a tile IN PLACE, so every wave's reads of x come before any
-      // wave's stores of x2)
-      if constexpr (DUP) lds_barrier();
       enc_store_tiles<T, NT, MT>(lane, XR, S, row0, n0, acc);
     }
   }
   lds_barrier();
   ENC_STAMP(4);
-  if constexpr (DHW_COPY_UNROLL != 0) tile_copy_out_u<T, BM, DM, 512>(XR, S, reinterpret_cast<T*>(p.x2) + (size_t)(b * p.Lk + m0) * DM, DM, rows_valid, tid);
-  else tile_copy_out<T>(XR, S, reinterpret_cast<T*>(p.x2) + (size_t)(b * p.Lk + m0) * DM, DM, rows_valid, DM, tid, 512);
+  tile_copy_out<T>(XR, S, reinterpret_cast<T*>(p.x2) + (size_t)(b * p.Lk + m0) * DM, DM, rows_valid, DM, tid, 512);
 
   // ---- [q2 | k2 | v2] = W x2 + b (+ PE·W for q, k), one DM-wide chunk at a time.  The opaque zero keeps hipcc
   // from treating the x2 fragment reads / store addresses as chunk-invariant and hoisting (then spilling) them.
   // bf16: all three chunks are rows of the [.., 3 DM] buffer; fp32: v2 goes out transposed (V^T [DM][lpadX]).
-  // (three calls of one body with compile-time chunk index and ring rotation: at d = 384 the rotation alternates, gemm_core.h)
-  auto qkv_chunk = [&](auto CHUNK_, auto ROT_) __attribute__((always_inline)) {
-    constexpr int chunk = decltype(CHUNK_)::value, ROTC = decltype(ROT_)::value;
+  // (three calls of one body with a compile-time chunk index)
+  auto qkv_chunk = [&](auto CHUNK_) __attribute__((always_inline)) {
+    constexpr int chunk = decltype(CHUNK_)::value;
     int opaque = 0;
     asm volatile("" : "+v"(opaque));
     f32x4 acc[NT][MT];
@@ -434,12 +394,7 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
 #pragma unroll
           for (int j = 0; j < MT; ++j) pb[i][j] = (f32x4){0, 0, 0, 0};
       }
-      if constexpr (XS) {
-        if constexpr (chunk < 2) ring.template run_x<MT, KC, ROTC, KC>(acc, xop + opaque, S, KC, reinterpret_cast<const T*>(p.w_qkv2) + (size_t)(chunk + 1) * DM * DM + wlane);
-        else ring.template run_x<MT, KC, ROTC, 0>(acc, xop + opaque, S, KC);
-      } else {
-        ring.template run_s<MT, KC>(acc, xop + opaque, S, KC);
-      }
+      ring.template run_s<MT, KC>(acc, xop + opaque, S, KC);
       ENC_STAMP(12 + chunk);
       if constexpr (PLDS) ep.lds_bias(PL + (4 + chunk) * DM, n0 + opaque);
       if constexpr (SPREADA && MT == 1) {
@@ -447,9 +402,9 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
         if (chunk < 2) { ring.template fill_begin<KC>(reinterpret_cast<const T*>(p.w_qkv2) + (size_t)(chunk + 1) * DM * DM + wlane); ring.template fill_range<KC, 0, 2 * FQA>(); }
       } else if constexpr (SPREADQ) {
         // (several row tiles per wave — the 64- / 32-row tiles of d = 192 / 256: the chunk goes out through the LDS staging tile; the next chunk's
-        // request in quarters around the pieces of that path, DHW_ENC_SPREAD bit 3)
+        // request in quarters around the pieces of that path)
         if (chunk < 2) { ring.template fill_begin<KC>(reinterpret_cast<const T*>(p.w_qkv2) + (size_t)(chunk + 1) * DM * DM + wlane); ring.template fill_range<KC, 0, FQA>(); }
-      } else if constexpr (!XS) { if (chunk < 2) ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_qkv2) + (size_t)(chunk + 1) * DM * DM + wlane); }
+      } else { if (chunk < 2) ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_qkv2) + (size_t)(chunk + 1) * DM * DM + wlane); }
     }
     if (rows_out && MT == 1) {
       // one row tile per wave (3 store instructions per chunk): straight from the accumulators, no LDS round trip
@@ -463,11 +418,11 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
       ENC_STAMP(5 + chunk);
       return;
     }
-    // DHW_ENC_QALT (round 5, bf16): the chunks alternate between TWO staging tiles — q and v through the q1 / a1 tile, k through the text K tile
+    // bf16: the chunks alternate between TWO staging tiles — q and v through the q1 / a1 tile, k through the text K tile
     // (dead since the cross-attention) — so the only barrier a chunk needs is the one between its LDS stores and its copy-out: the tile a chunk
     // writes was last read two chunks (one barrier) earlier; q's tile by dense1's main loop, in front of the LayerNorm's barriers.  3 barriers
     // instead of 6 for the three chunks.
-    constexpr bool QALT = sizeof(T) == 2 && DHW_ENC_QALT != 0 && VROW;
+    constexpr bool QALT = sizeof(T) == 2;
     char* const QT = QALT && chunk == 1 ? m.KT : QR;
     static_assert(!QALT || (size_t)BM * tile_stride<T>(DM) <= enc_a_text_kv_bytes<T, DM, BM>(), "a staging tile inside the text K / V tiles");
     if constexpr (!QALT) lds_barrier();   // the staging tile (q1/a1 region, or x2+q1 regions for V^T) is free: every wave is past its readers
@@ -483,8 +438,7 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
         if constexpr (SPREADQ) { if (chunk < 2) ring.template fill_range<KC, 2 * FQA, 3 * FQA>(); }
       }
       lds_barrier();
-      if constexpr (DHW_COPY_UNROLL != 0) tile_copy_out_u<T, BM, DM, 512>(QT, S, reinterpret_cast<T*>(p.qk2) + (size_t)(b * p.Lk + m0) * QKS + chunk * DM, QKS, rows_valid, tid);
-      else tile_copy_out<T>(QT, S, reinterpret_cast<T*>(p.qk2) + (size_t)(b * p.Lk + m0) * QKS + chunk * DM, QKS, rows_valid, DM, tid, 512);
+      tile_copy_out<T>(QT, S, reinterpret_cast<T*>(p.qk2) + (size_t)(b * p.Lk + m0) * QKS + chunk * DM, QKS, rows_valid, DM, tid, 512);
       if constexpr (SPREADQ) { if (act && chunk < 2) ring.template fill_range<KC, 3 * FQA, FCHA>(); }
     } else if constexpr (!VROW) {
       // v2 chunk -> LDS tile [channel][key] (key-contiguous, zero past the valid rows) -> coalesced rows of vt2
@@ -519,8 +473,7 @@ DHW_DEV void enc_a_body(const P& p, const EncALds& m, int b, int m0, int rows_va
     }
     ENC_STAMP(5 + chunk);
   };
-  constexpr int RC0 = XS ? RingT::template next_rot<KC, 0>() : 0, RC1 = XS ? RingT::template next_rot<KC, RC0>() : 0, RC2 = XS ? RingT::template next_rot<KC, RC1>() : 0;
-  qkv_chunk(std::integral_constant<int, 0>{}, std::integral_constant<int, RC0>{});
-  qkv_chunk(std::integral_constant<int, 1>{}, std::integral_constant<int, RC1>{});
-  qkv_chunk(std::integral_constant<int, 2>{}, std::integral_constant<int, RC2>{});
+  qkv_chunk(std::integral_constant<int, 0>{});
+  qkv_chunk(std::integral_constant<int, 1>{});
+  qkv_chunk(std::integral_constant<int, 2>{});
 }

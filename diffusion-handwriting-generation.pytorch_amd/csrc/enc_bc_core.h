@@ -5,22 +5,6 @@
 
 namespace {
 
-// -DDHW_ENC_XSTREAM=1: the weight stream of the bf16 EncoderLayer stages refilled ACROSS stage boundaries (WRing::run_x: a stage's
-// first chunks are requested chunk by chunk during the previous stage's main loop, rings of a whole stage at d = 192 / 256 and
-// of 8 of the 12 chunks at d = 384) instead of as one burst behind the main loop.  Bit-identical; built on the per-wave
-// timelines' "fill" segments (0.9-1.9 kcycles per stage) and measured no faster: the burst is not additive.
-#ifndef DHW_RING384
-#define DHW_RING384 24   // weight fragments in flight per wave in enc_bc's d = 384 stages on 16-row tiles (15 in round 3; 30 / 36 = a whole stage: experiments)
-#endif
-#ifndef DHW_ENC_EARLYFILL
-#define DHW_ENC_EARLYFILL 0   // measured 19.13 vs 19.08 ms (profiles/r04_earlyfill_ab.log): the prefetch queues in front of the K / V block the attention waits for
-#endif
-#ifndef DHW_ENC_XSTREAM
-#define DHW_ENC_XSTREAM 0   // measured: 19.05 vs 18.98 ms per 60-step batch (profiles/r04_xstream_ab.log) -> off
-#endif
-
-
-
 #define STAMP(slot) ENC_STAMP(slot)
 // per-wave stamps of enc_bc (diagnostic builds, tools/bench_encw.cpp): shader-clock time of every wave of workgroup 0 at the
 // phase boundaries inside the stages -> p.stamps[64 + wave * 32 + slot]
@@ -79,9 +63,6 @@ constexpr bool bc_params_fixed() { return lds_bc_tiles<T, DM, BM>() + enc_bc_par
 template <typename T, int DM, int BM>
 constexpr size_t lds_bc_bytes() { return lds_bc_tiles<T, DM, BM>() + (bc_params_fixed<T, DM, BM>() ? enc_bc_param_bytes<T, DM>() : 0); }
 
-#ifndef DHW_RING192
-#define DHW_RING192 12   // weight-ring fragments of the d = 192, 64-row variant (4 waves x 3 tiles: 12 accumulators twice in the FFN stages)
-#endif
 // NEXT: 0, or the EncChain mode compiled into this variant (DN = width of the chained layer)
 template <typename T, int DM, int BM, int NEXT>
 constexpr size_t lds_bc_chain_bytes() {
@@ -102,20 +83,17 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
   // this sample's rows = its keys (ragged batches: p.lens; p.Lk stays the row stride).  A tile past the end leaves before its first barrier.
   const int Ls = sample_len(p.lens, p.lsh, b, p.Lk);
   if constexpr (DHW_LENS) { if (m0 >= Ls) return; }
-  constexpr int WN = (DM % 128 == 0) ? 8 : (sizeof(T) == 4 ? 6 : DHW_WN192), WM = (DM % 128 == 0 || sizeof(T) == 4) ? 1 : DHW_WM192;   // as in enc_a_body: all rows per wave, channels split over WN waves
+  constexpr int WN = enc_wn<DM>(), WM = 1;   // as in enc_a_body: all rows per wave, channels split over WN waves
   constexpr int MT = BM / WM / 16, NT = DM / WN / 16, H = DM / 64, KC = DM / 32;
-  constexpr bool XS = sizeof(T) == 2 && DHW_ENC_XSTREAM && !(DM == 384 && BM >= 32);   // (d = 384 with 32-row tiles: two accumulator rows + the ring spill)   // cross-stage weight stream (gemm_core.h, run_x); the fp32 parity mode keeps run_s + fill_s
-  constexpr int XDE = KC <= 8 ? KC : 8;   // ring depth (chunks) of the cross-stage stream
-  constexpr int RING = sizeof(T) == 4 ? 12 : (XS ? XDE * NT : (DM == 384 ? (BM >= 32 ? 15 : DHW_RING384) : (DM == 192 && NT == 3 && BM == 64 ? DHW_RING192 : 24))), RDMAX = XS ? XDE : (RING + NT - 1) / NT;   // (d = 384, 32 rows: two accumulator rows, 24 fragments spill; d = 192 as 4 waves x 3 tiles on 64 rows: the whole stage, 6 chunks — 8 slots spill)
+  // weight fragments in flight per wave (d = 384: 24 on 16-row tiles — 30 / 36, a whole stage, measured no faster —, 15 on 32-row tiles, whose
+  // two accumulator rows spill with 24)
+  constexpr int RING = sizeof(T) == 4 ? 12 : (DM == 384 && BM >= 32 ? 15 : 24), RDMAX = (RING + NT - 1) / NT;
   const int tid = body_tid(), lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, g = lane >> 4;
-  // DHW_ENC_DUP (round 5): where the layout leaves waves without channels (DM = 192: 6 x 2 tiles on 8 waves), the spare waves REPEAT waves 0, 1 — the
-  // same tiles, the same values, written to the same LDS addresses — instead of skipping the stages.  With a run-time `if (act)` around every stage hipcc's
-  // s_waitcnt bookkeeping loses the weight ring at each join and drains it in front of every main loop (vmcnt(2) / (1) / (0) behind the barriers of the
-  // d = 192 kernels where the others wait vmcnt(15 .. 26)); with `act` folded away the code is the straight line of the 8-wave layouts.
-  constexpr bool DUP = DHW_ENC_DUP != 0 && sizeof(T) == 2 && WM == 1 && WN < 8;
-  const bool act = DUP ? true : (WN * WM == 8 || wave < WN * WM);   // (DM = 192, 6 x 1 without DUP: waves 6, 7 own no channels in the GEMM stages)
-  const int wm = DUP ? 0 : (act ? wave / WN : 0), wn = DUP ? wave % WN : (act ? wave % WN : 0);
+  // (DM = 192: waves 6, 7 own no channels in the GEMM stages.  A run-time `if (act)` around a stage makes hipcc drain the weight ring at the join;
+  // letting the spare waves repeat waves 0, 1 instead removed the drains and measured no faster: DESIGN.md 14.3e, 16)
+  const bool act = WN * WM == 8 || wave < WN * WM;
+  const int wm = act ? wave / WN : 0, wn = act ? wave % WN : 0;
   const int S = tile_stride<T>(DM);
   char* R1 = smem;               // a2, later SiLU(x3)
   char* R2 = R1 + BM * S;        // x3
@@ -130,20 +108,13 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
   const char* op3 = R3 + (row0 + l15) * S + g * 8 * ES;
 
   WRing<T, NT, RING, RDMAX> ring;
-#ifndef DHW_ENC_SPREAD
-#define DHW_ENC_SPREAD 11  // bit 0: this kernel's stages, bit 1: enc_a's (enc_a_core.h)
-#endif
-  constexpr bool SPREAD = sizeof(T) == 2 && (DHW_ENC_SPREAD & 1) != 0;
-  constexpr bool SPREAD_ATT = sizeof(T) == 2 && (DHW_ENC_SPREAD & 4) != 0 && !DHW_ENC_EARLYFILL && !DHW_ENC_XSTREAM;   // bit 2: the dense stage's request around the last key block
+  // A stage's first weight fragments are requested a few chunks at a time BETWEEN the pieces of the previous epilogue, not as one burst in front
+  // of it: a wave that requests its whole ring at once sits in instruction issue until the CU's L1 path has accepted all of it (1.2-2.9 kcycles
+  // per stage, profiles/r05_encbc_wave_timeline_d384.log).  The fp32 parity mode keeps the burst (fill_s).
+  constexpr bool SPREAD = sizeof(T) == 2;
   constexpr int FCH = WRing<T, NT, RING, RDMAX>::template fill_chunks<KC>(), FQ = (FCH + 3) / 4;   // ring slots a stage's first request fills, and a quarter of them
-  // slot rotation of the stages (gemm_core.h): dense 0, FFN first halves ROT1, second halves ROT2 — and back to ROT1, so the loop over the
-  // two halves of the hidden layer stays rolled
-  typedef WRing<T, NT, RING, RDMAX> RingT;
-  constexpr int ROT1 = XS ? RingT::template next_rot<KC, 0>() : 0, ROT2 = XS ? RingT::template next_rot<KC, ROT1>() : 0;
-  static_assert(!XS || RingT::template next_rot<KC, ROT2>() == ROT1, "FFN loop rotation");
   EpiParams<NT> ep;
   constexpr bool PLDS = enc_plds<T>(), PLFIX = bc_params_fixed<T, DM, BM>();
-  constexpr bool EARLY = sizeof(T) == 2 && DHW_ENC_EARLYFILL;   // the post-attention stage's weight prefetch issued in front of the attention
   float* PL = reinterpret_cast<float*>(smem + lds_bc_tiles<T, DM, BM>());   // (PLFIX; else chosen behind the attention loop)
   ParamStage<8> cp;
   // (a macro, not a lambda: with `cp` captured by a closure hipcc kept it in scratch memory)
@@ -159,24 +130,7 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
     constexpr int BUFB = KBS * SK + (VROW ? KBS * SV : DM * SV);   // one staged block: K tile, then V tile
     constexpr int QKS = qkv_stride<T, DM>();
     const int rg = wave % RG, hs = wave / RG;
-    // DHW_ATT_KSPLIT (round 5).  d = 192 with 64-row tiles: 4 row groups x 3 heads = 12 units on 8 waves — waves 0-3 ran heads 0 and 2, waves 4-7
-    // head 1 alone, and every key block lasted two units.  Here the two waves of a row group SHARE the third head's keys: wave (rg, 0) takes
-    // head 0 and keys [0, 32) of head 2 of every block, wave (rg, 1) head 1 and keys [32, 64) of head 2 — 1.5 units each — and the two
-    // partial (max, sum, output) states of head 2 are merged once behind the last block (the split-key combination of the running softmax).
-    // The 32-row tiles (2 row groups x 4 head slots, one of them idle) compute head 2 the same way — slot 2 the first halves, slot 3 the
-    // second — so that a row's arithmetic stays independent of the tile the launcher picks (a shard of a batch == the same samples inside
-    // it, bit for bit).  Against DHW_ATT_KSPLIT=0 the summation order of head 2's softmax differs: equal to fp32 rounding, not bit for bit.
-    // MEASURED NEUTRAL (17.959 vs 17.964 ms same-box, profiles/r05_spread_ab.log r5ad_ks; parity suite green with it on): the stage is bound by
-    // the SIMD's total softmax VALU work — 3 units per SIMD and block either way, ~1 kcycle of vector issue each — not by the longest wave.  Off.
-#ifndef DHW_ATT_KSPLIT
-#define DHW_ATT_KSPLIT 0
-#endif
-    constexpr bool KSPLIT = sizeof(T) == 2 && DHW_ATT_KSPLIT != 0 && H == 3 && (HS == 2 || HS == 4) && KBS == 64 && DB && PLFIX;
-    constexpr int SU = HS == 2 ? 1 : 0;                       // the state slot of a wave's share of head 2
-    const bool ks_full = HS == 2 || hs < 2;                   // this wave runs a whole head (slot 0: head hs)
-    const bool ks_part = HS == 2 || hs >= 2;                  // this wave runs one half of head 2's keys ..
-    const int ks_half = HS == 2 ? hs : hs - 2;                // .. this one
-    auto unit_head = [&](int u) { return !KSPLIT ? hs + u * HS : (HS == 2 ? (u == 1 ? 2 : hs) : (hs >= 2 ? 2 : hs)); };
+    auto unit_head = [&](int u) { return hs + u * HS; };   // the head of a wave's unit u (>= H: none)
     const T* qk = reinterpret_cast<const T*>(p.qk2);
     const T* ksrc = qk + (size_t)b * p.Lk * QKS + DM;
     const T* vsrc = VROW ? ksrc + DM : reinterpret_cast<const T*>(p.vt2) + (size_t)b * DM * p.lpadX;
@@ -223,11 +177,6 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
     }
     if constexpr (PLDS) BC_PARAMS_REQUEST();   // (!PLFIX: held in registers across the key blocks, 8 VGPRs)
     request(0);   // (one round trip together with the q fragments)
-    // The dense stage's first weight fragments are requested HERE, behind the first K / V block, not behind the attention: the
-    // wave waits for that block anyway, the vector-memory path is idle during the attention's LDS / MFMA work, and the stage
-    // then starts on a full ring instead of paying the request burst between the attention and its barrier (per-wave
-    // timelines: 1.6-2.3 kcycles from "att.end" to the barrier, profiles/r04_encbc_wave_timeline_*.log).  DHW_ENC_EARLYFILL=0: as before.
-    if constexpr (EARLY) { if (act) ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_d2) + wlane); }
     if constexpr (PLDS && PLFIX) cp.template store<DM>(PL, tid);
     commit(0, R2, R2 + KBS * SK);
     lds_barrier();
@@ -238,18 +187,7 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
       char* VT = KT + KBS * SK;
       char* KN = R2 + (DB && !(ib & 1) ? BUFB : 0);   // where the next block goes
       if (DB && more) request(kb + KBS);
-      if constexpr (SPREAD_ATT) {
-        // the post-attention stage's first weight fragments: half of them in front of the LAST key block's math (no K / V request follows them,
-        // so nothing the attention waits for queues behind them — the r4 EARLYFILL form put all of them in front of the FIRST block), the
-        // other half behind the a2 stores below
-        if (!more && act) { ring.template fill_begin<KC>(reinterpret_cast<const T*>(p.w_d2) + wlane); ring.template fill_range<KC, 0, 2 * FQ>(); }
-      }
       if (ib < 3) STAMP(26 + 2 * ib);
-      if constexpr (KSPLIT) {
-        if (ks_full) attn_unit_bf16<KBS>(lane, qf[0], KT, SK, VT, SV, hs, 0, kb, Ls, mr[0], lr[0], o[0]);
-        const int kh = (KBS / 2) * ks_half;   // (wave-uniform; a half past the end of the sequence is skipped: its state stays empty)
-        if (ks_part && kb + kh < Ls) attn_unit_bf16<KBS / 2>(lane, qf[SU], KT, SK, VT, SV, 2, kh, kb + kh, Ls, mr[SU], lr[SU], o[SU]);
-      } else
       attn_units<T, KBS, false, UMAX>(lane, qf, KT, SK, VT, SV, hs, HS, H, kb, 0u, Ls, mr, lr, o);
       if (ib < 3) STAMP(27 + 2 * ib);
       if (more) {
@@ -262,15 +200,7 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
       }
       // (after the last block the barrier behind the a2 store below separates the staging tiles from their next use)
     };
-    if constexpr (EARLY) {
-      // the first block straight-line, outside the loop: inside it hipcc cannot count the loads in flight (the weight prefetch
-      // above among them) and waits for all of them — vmcnt(0) in front of the first block's math, i.e. the prefetch hid nothing
-      key_block(0);
-      ib = 1;
-      for (int kb = KBS; kb < Ls; kb += KBS, ++ib) key_block(kb);
-    } else {
-      for (int kb = 0; kb < Ls; kb += KBS, ++ib) key_block(kb);
-    }
+    for (int kb = 0; kb < Ls; kb += KBS, ++ib) key_block(kb);
     if constexpr (PLDS && !PLFIX) {
       // the last block (index ib - 1) was read from buffer (ib - 1) & 1; the other one is free: its readers finished an
       // iteration ago, behind a barrier.  In buffer 0 the block goes behind the stage tiles and the LayerNorm scratch.
@@ -279,24 +209,10 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
       PL = reinterpret_cast<float*>(((ib - 1) & 1) ? R2 + 2 * BM * S + 2 * 8 * BM * sizeof(float) : R2 + BUFB);
       cp.template store<DM>(PL, tid);
     }
-    if constexpr (KSPLIT) {
-      // head 2: the wave with the second halves hands its partial state to the one with the first halves through the staging buffer the last
-      // block did not use (free since the previous iteration's barrier; the parameter block sits behind both buffers: PLFIX)
-      float* MS = reinterpret_cast<float*>(R2 + (((ib - 1) & 1) ? 0 : BUFB)) + (rg * 64 + lane) * 20;
-      static_assert((size_t)RG * 64 * 20 * sizeof(float) <= (size_t)BUFB, "merge scratch inside a staging buffer");
-      if (ks_part && ks_half == 1) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) *reinterpret_cast<f32x4*>(MS + 4 * t) = o[SU][t];
-        MS[16] = mr[SU];
-        MS[17] = lr[SU];
-      }
-      lds_barrier();
-      if (ks_part && ks_half == 0) attn_merge_state(mr[SU], lr[SU], o[SU], MS);
-    }
     WST(1);
 #pragma unroll
     for (int u = 0; u < UMAX; ++u) {
-      const int h = !KSPLIT ? hs + u * HS : (u == SU && ks_part) ? (ks_half == 0 ? 2 : H) : hs;   // (H: nothing to store)
+      const int h = unit_head(u);   // (>= H: nothing to store)
       float l = lr[u];
       l = xg_sum(l);
       const float inv = 1.0f / l;
@@ -313,10 +229,9 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
     cp.template store<DM>(PL, tid);
   }
   if (act) {
-    if constexpr (SPREAD_ATT) {
-      if (p.dbg & 1) ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_d2) + wlane);
-      else ring.template fill_range<KC, 2 * FQ, FCH>();
-    } else if (!EARLY || (p.dbg & 1)) ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_d2) + wlane);   // in flight across the barrier
+    // behind the attention, not in front of it or around its last key block: there the request queues in front of the K / V block the attention
+    // waits for
+    ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_d2) + wlane);   // in flight across the barrier
     if constexpr (!PLDS) ep.load(p.b_d2, gam + p.f2, bet + p.f2, n0);
   }
   WST(2);
@@ -339,30 +254,22 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
           const int r = m0 + row0 + j * 16 + l15;
           res[i][j] = load4(reinterpret_cast<const T*>(p.x2) + (unsigned)((b * p.Lk + r) * DM + n0 + 16 * i));
         }
-      if constexpr (XS) {
-        ring.template run_x<MT, KC, 0, KC>(acc, op1, S, KC, reinterpret_cast<const T*>(p.w_f1) + wlane);   // + FFN half 0's first chunks
-        WST(4);
-      } else {
-        ring.template run_s<MT, KC>(acc, op1, S, KC);
-        WST(4);
-        // FFN half 0's first fragments.  DHW_ENC_SPREAD (round 5): requested a few chunks at a time BETWEEN the pieces of the epilogue below
-        // instead of as one burst in front of it — a wave that requests its whole ring at once sits in instruction issue until the CU's L1
-        // path has accepted all of it (per-wave timelines at HEAD, profiles/r05_encbc_wave_timeline_d384.log: "f1.fill" 1.2-2.9 kcycles
-        // per stage, during which no wave of the workgroup executes the LayerNorm / FiLM / SiLU work that follows)
-        if constexpr (SPREAD) { ring.template fill_begin<KC>(reinterpret_cast<const T*>(p.w_f1) + wlane); ring.template fill_range<KC, 0, FQ>(); }
-        else ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_f1) + wlane);   // FFN half 0: flies during the LayerNorm epilogue
-      }
+      ring.template run_s<MT, KC>(acc, op1, S, KC);
+      WST(4);
+      // FFN half 0's first fragments: fly during the LayerNorm epilogue
+      if constexpr (SPREAD) { ring.template fill_begin<KC>(reinterpret_cast<const T*>(p.w_f1) + wlane); ring.template fill_range<KC, 0, FQ>(); }
+      else ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_f1) + wlane);
       WST(5);
       if constexpr (PLDS) ep.lds(PL, PL + DM, PL + 2 * DM, n0);
 #pragma unroll
       for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int j = 0; j < MT; ++j) acc[i][j] += ep.bias[i] + res[i][j];
-      if constexpr (SPREAD && !XS) ring.template fill_range<KC, FQ, 2 * FQ>();
+      if constexpr (SPREAD) ring.template fill_range<KC, FQ, 2 * FQ>();
     }
     STAMP(18);
     WST(6);
-    if constexpr (SPREAD && !XS) ln_rows<T, MT, NT, WN, BM>(acc, red, wn, row0, lane, DM, act, [&]() { if (act) ring.template fill_range<KC, 2 * FQ, 3 * FQ>(); });
+    if constexpr (SPREAD) ln_rows<T, MT, NT, WN, BM>(acc, red, wn, row0, lane, DM, act, [&]() { if (act) ring.template fill_range<KC, 2 * FQ, 3 * FQ>(); });
     else ln_rows<T, MT, NT, WN, BM>(acc, red, wn, row0, lane, DM, act);   // its barriers also fence the a2 reads above
     WST(7);
     if (act) {
@@ -372,7 +279,7 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
 #pragma unroll
         for (int j = 0; j < MT; ++j) acc[i][j] = acc[i][j] * ep.gam[i] + ep.bet[i];
       enc_store_tiles<T, NT, MT>(lane, R2, S, row0, n0, acc);
-      if constexpr (SPREAD && !XS) ring.template fill_range<KC, 3 * FQ, FCH>();
+      if constexpr (SPREAD) ring.template fill_range<KC, 3 * FQ, FCH>();
       silu_tiles2<T, NT, MT>(acc);
       enc_store_tiles<T, NT, MT>(lane, R1, S, row0, n0, acc);
     }
@@ -393,37 +300,30 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
       if constexpr (!PLDS) ep.load_bias(p.b_f1 + hh * DM, n0);
       // K-slice [hh*DM, (hh+1)*DM) of W2 [DM][2*DM]: the next stage's weights
       const T* w2 = reinterpret_cast<const T*>(p.w_f2) + (((size_t)ntile0 * 2 * KC + hh * KC) * 64 + lane) * 8;
-      if constexpr (XS) ring.template run_x<MT, KC, ROT1, KC>(acc, op1, S, KC, w2, 2 * KC);
-      else ring.template run_s<MT, KC>(acc, op1, S, KC);
+      ring.template run_s<MT, KC>(acc, op1, S, KC);
       WST(10 + 6 * hh);
       if constexpr (PLDS) ep.lds_bias(PL + (3 + hh) * DM, n0);
-      if constexpr (SPREAD && !XS) { ring.template fill_begin<KC>(w2, 2 * KC); ring.template fill_range<KC, 0, FQ>(); }
-      else if constexpr (!XS) ring.template fill_s<KC>(w2, 2 * KC);   // flies during the SiLU epilogue and the barrier
+      if constexpr (SPREAD) { ring.template fill_begin<KC>(w2, 2 * KC); ring.template fill_range<KC, 0, FQ>(); }
+      else ring.template fill_s<KC>(w2, 2 * KC);   // flies during the SiLU epilogue and the barrier
       WST(11 + 6 * hh);
 #pragma unroll
       for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int j = 0; j < MT; ++j) acc[i][j] += ep.bias[i];
-      if constexpr (SPREAD && !XS) ring.template fill_range<KC, FQ, 2 * FQ>();
+      if constexpr (SPREAD) ring.template fill_range<KC, FQ, 2 * FQ>();
       silu_tiles2<T, NT, MT>(acc);
-      if constexpr (SPREAD && !XS) ring.template fill_range<KC, 2 * FQ, 3 * FQ>();
+      if constexpr (SPREAD) ring.template fill_range<KC, 2 * FQ, 3 * FQ>();
       enc_store_tiles<T, NT, MT>(lane, R3, S, row0, n0, acc);
-      if constexpr (SPREAD && !XS) ring.template fill_range<KC, 3 * FQ, FCH>();
+      if constexpr (SPREAD) ring.template fill_range<KC, 3 * FQ, FCH>();
     }
     WST(12 + 6 * hh);
     lds_barrier();
     WST(13 + 6 * hh);
     STAMP(20 + 2 * hh);
     if (act) {
-      if constexpr (XS) {
-        if (hh == 0) ring.template run_x<MT, KC, ROT2, KC>(acc2, op3, S, KC, reinterpret_cast<const T*>(p.w_f1) + (size_t)DM * DM + wlane);   // + FFN half 1
-        else ring.template run_x<MT, KC, ROT2, 0>(acc2, op3, S, KC);
-        WST(14 + 6 * hh);
-      } else {
-        ring.template run_s<MT, KC>(acc2, op3, S, KC);
-        WST(14 + 6 * hh);
-        if (hh == 0) ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_f1) + (size_t)DM * DM + wlane);   // FFN half 1
-      }
+      ring.template run_s<MT, KC>(acc2, op3, S, KC);
+      WST(14 + 6 * hh);
+      if (hh == 0) ring.template fill_s<KC>(reinterpret_cast<const T*>(p.w_f1) + (size_t)DM * DM + wlane);   // FFN half 1
     }
     if (hh == 0) lds_barrier();   // R3 is rewritten by the next half (after the last one the LayerNorm barrier below does)
     WST(15 + 6 * hh);
@@ -451,8 +351,7 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
   }
   lds_barrier();
   const int rows_valid = min(BM, Ls - m0);
-  if constexpr (DHW_COPY_UNROLL != 0) tile_copy_out_u<T, BM, DM, 512>(R3, S, reinterpret_cast<T*>(p.out) + (size_t)(b * p.Lk + m0) * DM, DM, rows_valid, tid);
-  else tile_copy_out<T>(R3, S, reinterpret_cast<T*>(p.out) + (size_t)(b * p.Lk + m0) * DM, DM, rows_valid, DM, tid, 512);
+  tile_copy_out<T>(R3, S, reinterpret_cast<T*>(p.out) + (size_t)(b * p.Lk + m0) * DM, DM, rows_valid, DM, tid, 512);
   if (p.pool)
     tile_copy_out_pool<T>(R3, S, reinterpret_cast<T*>(p.pool) + ((size_t)b * (p.Lk / 2) + m0 / 2) * DM, DM, rows_valid, DM, tid, 512);
   STAMP(24);

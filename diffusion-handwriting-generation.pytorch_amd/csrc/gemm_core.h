@@ -21,9 +21,6 @@ DHW_DEV void keep_alive(const Frag<float>& f) { asm volatile("" ::"v"(f.lo), "v"
 // ISSUES the first D k-chunks' loads, so a caller can start the NEXT stage's weight stream before it runs the
 // current stage's epilogue / barrier (the loads fly during the epilogue); run() consumes the ring.
 // ABL (diagnostic builds only, tools/bench_stage.cpp): bit0 = no MFMA, bit1 = no weight re-loads, bit2 = no LDS reads
-#ifndef DHW_EPI_PRIO
-#define DHW_EPI_PRIO 0   // experiment: wave priority between the end of a weight request and the next main loop (0 = off)
-#endif
 #ifndef DHW_ABL
 #define DHW_ABL 0   // diagnostic builds only (-DDHW_ABL=n): default ablation mask of every main loop
 #endif
@@ -135,11 +132,7 @@ struct WRing {
 #pragma unroll
     for (int d = 0; d < (D < KT_ ? D : KT_); ++d) {
       load_chunk(d, d);
-#ifdef DHW_ORDERED_FILL
-      asm volatile("" ::: "memory");
-#endif
     }
-    if constexpr (DHW_EPI_PRIO != 0) __builtin_amdgcn_s_setprio(DHW_EPI_PRIO);
   }
   // ---- activation fragments requested AHEAD of their MFMAs (round 5).  In the loops above hipcc places a step's ds_read_b128
   // directly in front of the MFMA that consumes it (`ds_read x2; s_waitcnt lgkmcnt(1); v_mfma`, in the .s of every fused kernel):
@@ -148,27 +141,12 @@ struct WRing {
   // profiles/r05_conv_pp_wave_stamps.log: conv1 of enc1 takes a lone wave 1.0 us for 0.32 us of MFMA issue) — and the kernels
   // lean on the SIMD's second wave to fill the gaps.  Here chunk s + PF's MT fragments are requested BEFORE chunk s's MFMAs, into a
   // ring of PF + 1 register sets (PF = 1: +MT x 4 VGPRs), and scheduling barriers keep hipcc from sinking the reads back.
-  // Same reads, same MFMA order per accumulator: bit-identical results.  DHW_APF = chunks ahead (0 = off).
-#ifndef DHW_APF
-#define DHW_APF 3
-#endif
-#ifndef DHW_ENC_DUP
-#define DHW_ENC_DUP 0   // enc_a_core.h / enc_bc_core.h: spare waves repeat waves 0, 1 instead of idling
-#endif
-#ifndef DHW_CONV_DUP
-#define DHW_CONV_DUP 0   // convblock_core.h: the same in the 192-channel blocks
-#endif
-#ifndef DHW_WM192
-#define DHW_WM192 1   // row groups of the d = 192 layout (experiment: 2 with DHW_WN192=4: 2 x 4 waves of 3 channel tiles x half the rows, weights fetched twice)
-#endif
-#ifndef DHW_WN192
-#define DHW_WN192 6   // waves that own channels of a d = 192 EncoderLayer stage: 12 tiles of 16 as 6 waves x 2.  4 waves x 3 (one per SIMD; every channel wave
-                      // reads the whole activation tile from LDS, and 6 x 2 puts two channel waves on SIMDs 0 / 1, one on 2 / 3) measured -0.11 %, -0.28 %
-                      // and +0.1 % on three boxes: not adopted; 2 row groups x 4 (-DDHW_WM192=2, weights fetched twice) -0.05 % (profiles/r05_spread_ab.log)
-#endif
+  // Same reads, same MFMA order per accumulator: bit-identical results.
+  // Chunks ahead: three in the single-row-tile loops (MT = 1: the 16-row EncoderLayer tiles, 4 VGPRs per chunk), one elsewhere; three ahead
+  // everywhere costs more registers than it hides.
+  template <int MT> static constexpr int act_ahead() { return MT == 1 ? 3 : 1; }
   template <int MT, int KT_, int PF>
   DHW_DEV void run_p(f32x4 (&acc)[NT][MT], const char* abase, int stride, int KC) {
-    if constexpr (DHW_EPI_PRIO != 0) __builtin_amdgcn_s_setprio(0);
     constexpr int ES = sizeof(T), NB = PF + 1;
     static_assert(D % NB == 0, "the rolled part of the loop needs static fragment-ring indices");
     constexpr int NR = KT_ > D ? KT_ - D : 0, G = NR / D;
@@ -206,15 +184,11 @@ struct WRing {
   }
   template <int MT, int KT_, int ABL = DHW_ABL>
   DHW_DEV void run_s(f32x4 (&acc)[NT][MT], const char* abase, int stride, int KC) {
-    // DHW_APF: 1 = one chunk ahead everywhere; 2 = three chunks ahead where a chunk is fewer than 8 MFMAs (< 128 cycles of matrix work:
-    // one chunk does not cover an LDS round trip), one elsewhere
-    // 3 = three chunks ahead only for single-row-tile loops (MT = 1: the 16-row EncoderLayer tiles, 4 VGPRs per chunk), one elsewhere
-    constexpr int PF = DHW_APF == 2 ? (NT * MT >= 8 ? 1 : 3) : DHW_APF == 3 ? (MT == 1 ? 3 : 1) : DHW_APF;
-    if constexpr (PF > 0 && ABL == 0 && D % (PF + 1) == 0 && PF < D) {
+    constexpr int PF = act_ahead<MT>();
+    if constexpr (ABL == 0 && D % (PF + 1) == 0 && PF < D) {
       run_p<MT, KT_, PF>(acc, abase, stride, KC);
       return;
     }
-    if constexpr (DHW_EPI_PRIO != 0) __builtin_amdgcn_s_setprio(0);
     constexpr int ES = sizeof(T);
     constexpr int NR = KT_ > D ? KT_ - D : 0;   // steps that re-load their slot (chunk s + D exists)
     constexpr int G = NR / D;                   // of which whole groups of D run as a loop
@@ -251,65 +225,13 @@ struct WRing {
     for (int j = 0; j < KT_ - G * D; ++j) step(j % D, G * D + j + D < KT_, G * D + j + D);
   }
 
-  // ---- the stream across a stage boundary (the EncoderLayer kernels' short stages: KT_ <= 12 chunks, fully unrolled).
-  // run_s + fill_s issue the next stage's first fragments only AFTER the main loop, as one burst: a wave is blocked while its
-  // vector-memory instructions queue for the CU's L1 return path (64 B/clk for all 8 waves), so stage time = main loop + burst
-  // (0.9-1.9 kcycles of a 4-7 kcycle stage: profiles/r04_encbc_wave_timeline_*.log, "fill") + epilogue.  Here every ring slot
-  // is refilled the moment its chunk is consumed, with the stream's NEXT chunk whichever stage that belongs to: this stage's
-  // chunk s + DE while there is one, then chunks 0 .. of the next stage (nbase / nkts).  The path then carries one continuous
-  // stream under the MFMAs and the burst disappears; the next stage finds its first chunks exactly where fill_s would have
-  // put them, rotated by ROT: chunk c of a stage sits in slot (c + ROT) mod DE, DE = min(D, KT_), and the next stage's
-  // rotation is next_rot<KT_, ROT>().  Same loads, same MFMA order per accumulator: bit-identical results.
   template <int KT_> static constexpr int eff_depth() { return D < KT_ ? D : KT_; }
-  template <int KT_, int ROT> static constexpr int next_rot() { return (ROT + KT_) % eff_depth<KT_>(); }
-  // KTN_: the next stage's chunk count (0 = none: the ring drains).  Requires eff_depth<KTN_>() == eff_depth<KT_>() (or KTN_ == 0).
-  template <int MT, int KT_, int ROT, int KTN_>
-  DHW_DEV void run_x(f32x4 (&acc)[NT][MT], const char* abase, int stride, int KC, const T* __restrict__ nbase = nullptr, int nkts = 0) {
-    constexpr int ES = sizeof(T), DE = eff_depth<KT_>();
-    static_assert(KTN_ == 0 || eff_depth<KTN_>() == DE, "the next stage must use the same ring depth");
-    const int nKTS = nkts ? nkts : KTN_;
-    int aoff = 0, kc = 0;   // of the NEXT chunk of activation fragments to request
-    const int tap_step = stride - (KC - 1) * 32 * ES;
-    // (round 5: the activation fragments are requested PF chunks ahead of their MFMAs, as in run_p)
-    constexpr int PF = DHW_APF == 0 ? 0 : (MT == 1 && DHW_APF == 3 ? 3 : 1), NB = PF + 1;
-    Frag<T> a[NB][MT];
-    auto request = [&](int slot) {
-#pragma unroll
-      for (int j = 0; j < MT; ++j) a[slot][j] = frag_load(reinterpret_cast<const T*>(abase + j * 16 * stride + aoff));
-      const bool wrap = ++kc == KC;
-      aoff += wrap ? tap_step : 32 * ES;
-      kc = wrap ? 0 : kc;
-    };
-#pragma unroll
-    for (int c = 0; c < PF; ++c)
-      if (c < KT_) request(c);
-#pragma unroll
-    for (int s = 0; s < KT_; ++s) {
-      const int d = (s + ROT) % DE;
-      if (PF == 0) request(0);
-      else if (s + PF < KT_) request((s + PF) % NB);
-      if (PF != 0) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < NT; ++i)
-#pragma unroll
-        for (int j = 0; j < MT; ++j) mma32(acc[i][j], q[d][i], a[s % NB][j]);
-      const int nx = s + DE;   // position in the concatenated stream that goes into the freed slot
-      if (nx < KT_) {
-        load_chunk(d, nx);
-      } else if (KTN_ != 0 && nx - KT_ < DE) {
-#pragma unroll
-        for (int i = 0; i < NT; ++i) q[d][i] = frag_load(nbase + ((size_t)i * nKTS + (nx - KT_)) * 512);
-      }
-      if (PF != 0) __builtin_amdgcn_sched_barrier(0);
-    }
-    if (KTN_ != 0) { base = nbase; KT = KTN_; KTS = nKTS; }
-  }
 
   // ---- a SHORT stage (KT_ <= D chunks, no refills of its own) followed by a long one: the next stage's fill rides under this
   // stage's MFMAs instead of standing as one burst between the two main loops (the ConvBlock's fc -> conv_skip: KT_ = CO / 32 = 4-8
   // chunks against 12-36).  Slot s takes the next stage's chunk s the moment this stage's chunk s is consumed; the slots this
   // stage never used (KT_ .. ) take theirs alongside, spread over the steps.  The next stage then starts as after fill_s<KTN_>
-  // (chunk c in slot c, no rotation).  Same requests, same MFMA order: bit-identical.
+  // (chunk c in slot c).  Same requests, same MFMA order: bit-identical.
   template <int MT, int KT_, int KTN_>
   DHW_DEV void run_n(f32x4 (&acc)[NT][MT], const char* abase, int stride, int KC, const T* __restrict__ nbase, int nkts = 0) {
     static_assert(KT_ <= D, "run_n: the stage must fit the ring");
@@ -318,7 +240,7 @@ struct WRing {
     const int nKTS = nkts ? nkts : KTN_;
     int aoff = 0, kc = 0;
     const int tap_step = stride - (KC - 1) * 32 * ES;
-    constexpr int PF = DHW_APF == 0 ? 0 : (MT == 1 && DHW_APF == 3 ? 3 : 1), NB = PF + 1;
+    constexpr int PF = act_ahead<MT>(), NB = PF + 1;
     Frag<T> a[NB][MT];
     auto request = [&](int slot) {
 #pragma unroll
@@ -336,9 +258,8 @@ struct WRing {
       if (c < KT_) request(c);
 #pragma unroll
     for (int s = 0; s < KT_; ++s) {
-      if (PF == 0) request(0);
-      else if (s + PF < KT_) request((s + PF) % NB);
-      if (PF != 0) __builtin_amdgcn_sched_barrier(0);
+      if (s + PF < KT_) request((s + PF) % NB);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -347,7 +268,7 @@ struct WRing {
 #pragma unroll
       for (int e = 0; e < PER; ++e)
         if (KT_ + s * PER + e < DN) next_chunk(KT_ + s * PER + e);
-      if (PF != 0) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
     }
     base = nbase; KT = KTN_; KTS = nKTS;
   }
@@ -366,30 +287,8 @@ DHW_DEV void mainloop(f32x4 (&acc)[NT][MT], const T* __restrict__ wbase, const c
 // `gs` elements): 16 bytes per lane, consecutive lanes on consecutive addresses.  Per-lane 8-byte stores straight from
 // the MFMA accumulators touch 16 rows per instruction and are store-issue bound (measured 5 us for a 64x384 tile vs
 // <1 us through LDS).
-// The same with the trip count known (ROWS = rows of the tile, CC = its channels, NTH threads): every piece is read from LDS BEFORE the first store, so
-// a thread pays the LDS latency once per tile instead of once per piece (the rolled loop below is read - wait - store per pass).  DHW_COPY_UNROLL.
-// MEASURED SLOWER: 17.539 vs 17.428 ms same-box (profiles/r05_spread_ab.log, r5aw) — the rolled loop's stores start behind the first read, and the
-// per-piece `if (id < total)` of the unrolled form is a join per store.  Off.
-#ifndef DHW_COPY_UNROLL
-#define DHW_COPY_UNROLL 0
-#endif
-template <typename T, int ROWS, int CC, int NTH>
-DHW_DEV void tile_copy_out_u(const char* lds, int S, T* gdst, int gs, int rows_valid, int tid) {
-  constexpr int ES = sizeof(T), EPV = 16 / ES, CPR = CC / EPV, IT = (ROWS * CPR + NTH - 1) / NTH;
-  const int total = rows_valid * CPR;
-  uint4 v[IT];
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int id = min(tid + it * NTH, ROWS * CPR - 1), r = id / CPR, cc = id - r * CPR;   // (clamped: inside the tile)
-    v[it] = *reinterpret_cast<const uint4*>(lds + r * S + cc * 16);
-  }
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int id = tid + it * NTH, r = id / CPR, cc = id - r * CPR;
-    if (id < total) *reinterpret_cast<uint4*>(gdst + (size_t)r * gs + cc * EPV) = v[it];
-  }
-}
-
+// The loop stays rolled: with every piece read from LDS before the first store the stores start later and each carries its own bounds join
+// (measured slower).
 template <typename T>
 DHW_DEV void tile_copy_out(const char* lds, int S, T* gdst, int gs, int rows_valid, int C, int tid, int nthreads) {
   constexpr int ES = sizeof(T), EPV = 16 / ES;

@@ -22,30 +22,24 @@ DHW_DEV unsigned add_agent(unsigned* p, unsigned v) { return __hip_atomic_fetch_
 // host gave the plan a trace buffer (DHW_PERSIST_TRACE=1 at dhw_create; tools/persist_trace.py).  Outside the block bodies.
 #define PTRACE(slot) do { if (trace && tid == 0) trace[((size_t)blockIdx.x * STEP_MAX_PHASES + ph) * 4 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 
-// One phase body = one real function (not inlined): inlined into one kernel the eleven bodies shared a register allocation
-// that spilled 836 VGPRs.  Arguments of a device function travel in vector registers; the callee makes the (uniform) ones
-// scalar again, so the plan is read with scalar loads exactly as kernel arguments are.
-#ifdef DHW_PERSIST_CALLS
-#define PHASE_FN __device__ __attribute__((noinline))
-#else
-#define PHASE_FN __device__ __forceinline__
-#endif
+// One phase body = one inlined function.  Its arguments arrive as (possibly vector) values; the body makes the uniform ones scalar
+// again, so the plan is read with scalar loads exactly as kernel arguments are.
 DHW_DEV const AS4 StepPhase& phase_ref(unsigned long long pp) {
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)pp), hi = __builtin_amdgcn_readfirstlane((unsigned)(pp >> 32));
   return *(const AS4 StepPhase*)(((unsigned long long)hi << 32) | lo);
 }
 template <int BM, int CO, int UPC, int CH, int CIN>
-PHASE_FN void phase_conv(unsigned long long pp, int b, int m0, char* smem) {
+DHW_DEV void phase_conv(unsigned long long pp, int b, int m0, char* smem) {
   const AS4 StepPhase& P = phase_ref(pp);
   convblock_body<bf16_t, BM, CO, 8, 1, UPC, CH, CIN>(P.cb, P.nx, __builtin_amdgcn_readfirstlane(b), __builtin_amdgcn_readfirstlane(m0), smem);
 }
 template <int DM, int BM>
-PHASE_FN void phase_a(unsigned long long pp, int b, int m0, char* smem) {
+DHW_DEV void phase_a(unsigned long long pp, int b, int m0, char* smem) {
   const AS4 StepPhase& P = phase_ref(pp);
   enc_a_tile<bf16_t, DM, BM>(P.el, __builtin_amdgcn_readfirstlane(b), __builtin_amdgcn_readfirstlane(m0), smem);
 }
 template <int DM, int BM, int NEXT>
-PHASE_FN void phase_bc(unsigned long long pp, int b, int m0, char* smem) {
+DHW_DEV void phase_bc(unsigned long long pp, int b, int m0, char* smem) {
   const AS4 StepPhase& P = phase_ref(pp);
   enc_bc_body<bf16_t, DM, BM, NEXT>(P.el, P.nx, __builtin_amdgcn_readfirstlane(b), __builtin_amdgcn_readfirstlane(m0), smem);
 }
@@ -107,9 +101,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           PTRACE(0);
           if (ph > 0) {
             // L1 first: from here to the tile's loads this workgroup touches no activation (persist.h)
-#ifndef DHW_PERSIST_NOFENCE   // (timing experiment only: without the L1 invalidate the tile's loads may return stale rows)
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
             const int t = gt - c.ns * plan->cum_tps[ph];
             const unsigned need = (unsigned)plan->ph[ph - 1].tps;
             const unsigned* cnt = c.done + (size_t)(ph - 1) * c.B + c.s0 + t / plan->ph[ph].tps;
@@ -139,24 +131,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       pp = (unsigned long long)(const AS4 void*)&P;
       PTRACE(1);
     }
-#ifdef DHW_PERSIST_ONLY   // diagnostics: a kernel that holds ONLY the bodies in this bit mask (the other phases complete at once):
-                          // what a body costs inside the launch when it is not compiled together with the ten others
-#define PK_ON(k) (((DHW_PERSIST_ONLY) >> (k)) & 1)
-#else
-#define PK_ON(k) 1
-#endif
     switch (kind) {
-      case PK_CONV_ENC1: if constexpr (PK_ON(PK_CONV_ENC1)) phase_conv<128, 128, 0, 0, 128>(pp, b, m0, smem); break;
-      case PK_CONV_ENC2A: if constexpr (PK_ON(PK_CONV_ENC2A)) phase_conv<64, 192, 0, 1, 128>(pp, b, m0, smem); break;
-      case PK_BC192: if constexpr (PK_ON(PK_BC192)) phase_bc<192, 64, 0>(pp, b, m0, smem); break;
-      case PK_CONV_ENC4: if constexpr (PK_ON(PK_CONV_ENC4)) phase_conv<48, 256, 0, 0, 192>(pp, b, m0, smem); break;
-      case PK_A256: if constexpr (PK_ON(PK_A256)) phase_a<256, 32>(pp, b, m0, smem); break;
-      case PK_BC256_N2: if constexpr (PK_ON(PK_BC256_N2)) phase_bc<256, 32, 2>(pp, b, m0, smem); break;
-      case PK_BC384_N1: if constexpr (PK_ON(PK_BC384_N1)) phase_bc<384, 16, 1>(pp, b, m0, smem); break;
-      case PK_BC384: if constexpr (PK_ON(PK_BC384)) phase_bc<384, 16, 0>(pp, b, m0, smem); break;
-      case PK_CONV_DEC3: if constexpr (PK_ON(PK_CONV_DEC3)) phase_conv<48, 256, 384, 0, 384>(pp, b, m0, smem); break;
-      case PK_CONV_DEC2: if constexpr (PK_ON(PK_CONV_DEC2)) phase_conv<64, 192, 256, 0, 256>(pp, b, m0, smem); break;
-      case PK_CONV_DEC1: if constexpr (PK_ON(PK_CONV_DEC1)) phase_conv<128, 128, 192, 0, 192>(pp, b, m0, smem); break;
+      case PK_CONV_ENC1: phase_conv<128, 128, 0, 0, 128>(pp, b, m0, smem); break;
+      case PK_CONV_ENC2A: phase_conv<64, 192, 0, 1, 128>(pp, b, m0, smem); break;
+      case PK_BC192: phase_bc<192, 64, 0>(pp, b, m0, smem); break;
+      case PK_CONV_ENC4: phase_conv<48, 256, 0, 0, 192>(pp, b, m0, smem); break;
+      case PK_A256: phase_a<256, 32>(pp, b, m0, smem); break;
+      case PK_BC256_N2: phase_bc<256, 32, 2>(pp, b, m0, smem); break;
+      case PK_BC384_N1: phase_bc<384, 16, 1>(pp, b, m0, smem); break;
+      case PK_BC384: phase_bc<384, 16, 0>(pp, b, m0, smem); break;
+      case PK_CONV_DEC3: phase_conv<48, 256, 384, 0, 384>(pp, b, m0, smem); break;
+      case PK_CONV_DEC2: phase_conv<64, 192, 256, 0, 256>(pp, b, m0, smem); break;
+      case PK_CONV_DEC1: phase_conv<128, 128, 192, 0, 192>(pp, b, m0, smem); break;
       default: break;
     }
     {

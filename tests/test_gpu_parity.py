@@ -437,9 +437,7 @@ def test_three_head_layer_on_both_row_tiles_matches_oracle(L, monkeypatch):
     """enc3 (d = 192, three heads: 12 (row group, head) units on 8 waves) on 64-row and on 32-row tiles.  The bench batch picks 64 rows by itself
     (B * ceil(L/2 / 64) >= 256); here the tile is forced at B = 2 so that the oracle finishes in seconds.  Key counts: 244 (four blocks, the last
     one partial), 84 (20 keys in the last block), 24 (a single partial block), 132 (the last block holds 4 keys).  The enc3 tap isolates the layer;
-    eps / pen bound what reaches the output.  Also the test of -DDHW_ATT_KSPLIT=1 (enc_bc_core.h: the two waves of a row group share the third
-    head's keys, 32 of every 64-key block each, and merge their partial softmax states; measured neutral, off by default): the key counts are the
-    cases of its skip / merge paths, and it passed with the switch on (gpurun_out/r5ad_ks)."""
+    eps / pen bound what reaches the output."""
     B, Lt = 2, 9
     inp = spec.synthetic_inputs(B, L, Lt, seed=900 + L, pad=1)
     sg = torch.tensor([[0.3], [0.8]])

@@ -2,6 +2,7 @@
 """ISA census of the fused kernels: per kernel, per basic block, instruction counts by class.
 
 usage: isa_census.py file.s [kernel-substring] [--blocks]
+       isa_census.py --identity DIR_A DIR_B     compare the <unit>.s files of two trees kernel by kernel (JSON on stdout, exit 1 on a difference)
 Static counts from hipcc's -S output; loop blocks (a label that is the target of a backward branch) are marked so that
 their counts can be weighted by trip counts by the reader.  Classes:
   mfma, valu_cvt (conversions/packs), valu_trans (exp/rcp/rsq/...), valu_addr (64-bit address arithmetic: v_add_co/v_addc_co,
@@ -9,6 +10,9 @@ their counts can be weighted by trip counts by the reader.  Classes:
   valu_cmp (v_cmp/v_cndmask), valu_pk (packed f32 math), valu_f32 (other float math), valu_int (other integer),
   vmem_ld, vmem_st, lds_rd, lds_wr, salu, smem, wait, branch, other
 """
+import hashlib
+import json
+import os
 import re
 import sys
 from collections import Counter, OrderedDict
@@ -90,7 +94,43 @@ def parse(path):
     return kernels
 
 
+def kernel_texts(path):
+    """name -> normalised text of every function of a .s (body + .amdhsa descriptor); "<rest>" = everything else (metadata, globals).
+    Dropped: what assembles to nothing or names the source text — .ident / .file lines, whole-line compiler comments (`; implicit-def: ..`,
+    `; %bb.N:`: their order follows the IR's value order, not the code), the __hip_cuid_<hash of the source text> object — and the per-file
+    function index in local labels."""
+    out, cur = {"<rest>": []}, "<rest>"
+    with open(path) as f:
+        for line in f:
+            s = line.rstrip()
+            if not s.strip() or s.lstrip().startswith((".ident", ".file", ";")) or "__hip_cuid_" in s:
+                continue
+            s = re.sub(r"\.L(BB|func_end|func_begin|JTI|tmp)\d+", r".L\1", s)
+            m = re.match(r"^(_Z[\w.$]*):", s) or re.match(r"^\s*\.amdhsa_kernel\s+(\S+)", s)
+            if m:
+                cur = m.group(1)
+            out.setdefault(cur, []).append(s)
+            if s.startswith(".Lfunc_end") or s.strip() == ".end_amdhsa_kernel":
+                cur = "<rest>"
+    return {k: hashlib.sha256("\n".join(v).encode()).hexdigest()[:16] for k, v in out.items()}
+
+
+def identity(dir_a, dir_b):
+    res, bad = {}, 0
+    for fn in sorted(os.listdir(dir_a)):
+        if not fn.endswith(".s"):
+            continue
+        a, b = kernel_texts(os.path.join(dir_a, fn)), kernel_texts(os.path.join(dir_b, fn))
+        res[fn[:-2]] = {k: {"a": a.get(k), "b": b.get(k)} for k in sorted(set(a) | set(b))}
+        bad += sum(v["a"] != v["b"] for v in res[fn[:-2]].values())
+    json.dump({"differing": bad, "units": res}, sys.stdout, indent=1)
+    return 1 if bad else 0
+
+
 def main():
+    if "--identity" in sys.argv:
+        i = sys.argv.index("--identity")
+        sys.exit(identity(sys.argv[i + 1], sys.argv[i + 2]))
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     path = args[0]
     sub = args[1] if len(args) > 1 else ""
