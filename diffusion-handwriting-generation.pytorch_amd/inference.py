@@ -191,14 +191,25 @@ def load_style(source, style_weights=None) -> torch.Tensor:
     return sv
 
 
+RENDERERS = ("matplotlib", "gpu")
+
+
+def _check_renderer(renderer: str) -> None:
+    if renderer not in RENDERERS:
+        raise ValueError(f"renderer must be one of {RENDERERS}, got {renderer!r}")
+
+
 def infer_file(prompt: str, source, config_path: str | None = None, checkpoint_path: str | None = None,
                experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *, precision: str = "bf16",
-               seed: int = 0, render: bool = True, style_weights: str | None = None) -> np.ndarray:
+               seed: int = 0, render: bool = True, style_weights: str | None = None, renderer: str = "matplotlib") -> np.ndarray:
     """The reference's command-line entry (inference.py:19-27) around this build's sampler: resolve config / checkpoint
-    (directly or inside ``experiment_path``), load the model, sample one prompt, write ``./<output>.png``.
+    (directly or inside ``experiment_path``), load the model, sample one prompt, write ``./<output>.png`` (``renderer``:
+    "matplotlib" = the reference's figure, "gpu" = the 96-row grey line image of ``render_strokes``).
     Returns the [L,3] strokes."""
     from .checkpoint import find_checkpoint, load_model
-    from .vis import show_strokes
+    from .vis import render_lines_png, show_strokes
+
+    _check_renderer(renderer)
 
     if experiment_path:
         from pathlib import Path
@@ -212,7 +223,9 @@ def infer_file(prompt: str, source, config_path: str | None = None, checkpoint_p
     style = load_style(source, style_weights)
     model = load_model(config_path, checkpoint_path, precision=precision, max_B=1, style_rows=style.shape[1])
     strokes = infer(prompt, style, model, diffusion_mode=diffusion_mode, seed=seed)
-    if render:
+    if render and renderer == "gpu":
+        render_lines_png([strokes], [output])
+    elif render:
         show_strokes(strokes, scale=1, name=output, show_output=False)
     return strokes
 
@@ -233,18 +246,22 @@ def _resolve_experiment(config_path, checkpoint_path, experiment_path):
 
 def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint_path: str | None = None,
                      experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
-                     precision: str = "bf16", seed: int = 0, render: bool = True, style_weights: str | None = None) -> list:
+                     precision: str = "bf16", seed: int = 0, render: bool = True, style_weights: str | None = None,
+                     renderer: str = "matplotlib") -> list:
     """``infer_file`` for many prompts of one writer: one ragged sampler call (``infer_batch``), ``./<output>_<i>.png`` per
-    prompt.  Returns the list of [L_i, 3] strokes."""
+    prompt (``renderer="gpu"``: every line rasterised in one ``render_strokes`` call).  Returns the list of [L_i, 3] strokes."""
     from .checkpoint import load_model
-    from .vis import show_strokes
+    from .vis import render_lines_png, show_strokes
 
+    _check_renderer(renderer)
     prompts = list(prompts)
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
     model = load_model(config_path, checkpoint_path, precision=precision, max_B=max(1, len(prompts)), style_rows=style.shape[1])
     strokes = infer_batch(prompts, style, model, diffusion_mode=diffusion_mode, seed=seed)
-    if render:
+    if render and renderer == "gpu":
+        render_lines_png(strokes, [f"{output}_{i}" for i in range(len(strokes))])
+    elif render:
         for i, s in enumerate(strokes):
             show_strokes(s, scale=1, name=f"{output}_{i}", show_output=False)
     return strokes

@@ -122,6 +122,44 @@ int dhw_sample_ragged(dhw_handle*, const int64_t* text, const float* style, int 
                       const int32_t* lens, int T, int mode, const float* noise, uint64_t seed,
                       int64_t first_sample, float* out, void* hip_stream);
 
+/* Stroke rasteriser: sampled strokes -> grey-level line images in the layout dhw_style_forward consumes (ink
+ * left-aligned, white to the right).  No handle: errors are read through dhw_last_error(NULL).  The call allocates
+ * nothing, synchronises nothing and can be captured into a graph.  All argument checks run before the first HIP call
+ * (DHW_ERR_ARG names the argument): B >= 1, 1 <= L <= 4096, H >= 8, W >= 8 and W % 4 == 0, 0.5 <= line_width <= 16
+ * with 2m < H and 2m < W (m below), non-NULL strokes / img_out / workspace (both 16-byte aligned),
+ * workspace_bytes >= dhw_render_workspace_bytes(B, L) (0 for a B or L outside the ranges above).
+ *
+ * The picture of row b, with n = lens[b] (L when lens is NULL) and (dx, dy, pen)[i] its strokes for i < n (rows at or
+ * past n are never read, whatever they hold):
+ *    1. pos[i] = sum_{j<=i} (dx_j, dy_j).
+ *    2. lift[i] = (rintf(pen[i]) != 0): round-half-to-even, 0.5 is not a lift.
+ *    3. last = the largest i with lift[i].
+ *    4. Segment i runs from pos[i-1] to pos[i]; it is drawn iff 1 <= i < last and !lift[i]  (nothing after the last lift
+ *       is drawn, a row without a lift draws nothing: the consecutive point pairs inside the polylines of the
+ *       reference's show_strokes).
+ *    5. (xmin, xmax, ymin, ymax) = the box of the endpoints of drawn segments.  No drawn segment: the image is all 255
+ *       and widths_out[b] = 0.
+ *    6. m = line_width/2 + 1.
+ *    7. s = (H - 2m)/(ymax - ymin); if (xmax - xmin) s > W - 2m then s = (W - 2m)/(xmax - xmin).  Both extents 0: s = 1.
+ *       Only the height 0: s from the width rule, but never above H - 2m.
+ *    8. px = m + (x - xmin) s.
+ *    9. py = m + voff + (ymax - y) s, voff = (H - 2m - (ymax - ymin) s)/2  (the stroke y axis points up, image rows go
+ *       down; the ink is centred vertically when the width limits the scale).
+ *   10. Pixel (r, c) has its centre at (c + 0.5, r + 0.5).
+ *   11. d = the smallest Euclidean distance from that centre to a drawn segment (a zero-length segment is a point).
+ *   12. value = 255 (1 - clamp(line_width/2 + 0.5 - d, 0, 1)).
+ *   13. widths_out[b] = min(W, ceil((xmax - xmin) s + 2m)).
+ * The minimum is exact and commutative and no float atomics are used: the image is bit-deterministic, and row b of a
+ * batch equals the same strokes rendered alone at L = lens[b], bit for bit. */
+size_t dhw_render_workspace_bytes(int B, int L);
+int dhw_render(const float* strokes,      /* device f32 [B,L,3]                        */
+               const int32_t* lens,       /* DEVICE int32 [B] or NULL, any 1 <= n <= L (unlike the sampler's host lens:
+                                             the call chains behind dhw_sample_ragged without a host read) */
+               int B, int L, int H, int W, float line_width,
+               float* img_out,            /* device f32 [B,1,H,W], 0..255              */
+               int32_t* widths_out,       /* device [B] or NULL                        */
+               void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Host-only: beta_i = 0.02 + exp(linspace(ln 1e-5, ln 0.4, T)), abar = cumprod(1-beta), fp32. */
 int dhw_schedule(int T, float* beta_out, float* alpha_bar_out);
 

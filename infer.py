@@ -28,6 +28,8 @@ def main(argv=None):
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--style-weights", help="torchvision mobilenet_v2 state_dict (.pth) for the StyleExtractor")
+    ap.add_argument("--renderer", default="matplotlib", choices=list(dhg_amd.inference.RENDERERS),
+                    help="how the PNGs are drawn: the reference's matplotlib figure, or the 96-row grey line image rasterised on the GPU")
     a = ap.parse_args(argv)
     if a.prompts_file:
         if a.prompt is not None and a.source is not None:
@@ -40,14 +42,14 @@ def main(argv=None):
         if not prompts:
             ap.error(f"{a.prompts_file} holds no prompt")
         out = dhg_amd.infer_file_batch(prompts, source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
-                                       a.diffusion_mode, precision=a.precision, seed=a.seed, style_weights=a.style_weights)
+                                       a.diffusion_mode, precision=a.precision, seed=a.seed, style_weights=a.style_weights, renderer=a.renderer)
         for i, s in enumerate(out):
             print(f"{s.shape[0]} stroke points -> ./{a.output}_{i}.png")
         return
     if a.prompt is None or a.source is None:
         ap.error("the following arguments are required: prompt, source")
     strokes = dhg_amd.infer_file(a.prompt, a.source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
-                                 a.diffusion_mode, precision=a.precision, seed=a.seed, style_weights=a.style_weights)
+                                 a.diffusion_mode, precision=a.precision, seed=a.seed, style_weights=a.style_weights, renderer=a.renderer)
     print(f"{strokes.shape[0]} stroke points -> ./{a.output}.png")
 
 
