@@ -14,10 +14,10 @@
 #include "../../include/dhw_style.h"
 #include "abi_guard.h"
 #include "dhw_kernels.h"
+#include "host/device_arena.h"
+#include "host/weight_store.h"
 
 namespace {
-
-struct SKey { std::string key; std::vector<int64_t> shape; };
 
 // torchvision.models.mobilenet_v2 inverted_residual_setting: expansion t, output channels c, repeats n, first stride s
 struct Setting { int t, c, n, s; };
@@ -39,12 +39,12 @@ std::vector<BlockDesc> block_descs() {
   return v;
 }
 
-void add_bn(std::vector<SKey>& k, const std::string& n, int c) {
+void add_bn(std::vector<KeySpec>& k, const std::string& n, int c) {
   for (const char* s : {"weight", "bias", "running_mean", "running_var"}) k.push_back({n + "." + s, {c}});
 }
 
-std::vector<SKey> build_keys() {
-  std::vector<SKey> k;
+std::vector<KeySpec> build_keys() {
+  std::vector<KeySpec> k;
   k.push_back({"features.0.0.weight", {kStem, 3, 3, 3}});
   add_bn(k, "features.0.1", kStem);
   for (const BlockDesc& b : block_descs()) {
@@ -68,19 +68,6 @@ std::vector<SKey> build_keys() {
 // channel padding: what the generic GEMM's column tiles (64 / 96 / 128 / 192 / 256 / 384) divide
 int padc(int c) { return c <= 64 ? 64 : (c == 96 ? 96 : ((c + 63) / 64) * 64); }
 
-uint16_t f2bf(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-float bf2f(uint16_t h) {
-  uint32_t u = (uint32_t)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
 ErrBuf g_err;
 
 }  // namespace
@@ -88,13 +75,9 @@ ErrBuf g_err;
 struct dhw_style {
   int device = 0, prec = PREC_BF16, es = 2;
   ErrBuf err;
-  bool lookup_fail = false;   // the packing code asked for a key build_keys does not declare
-  std::vector<SKey> spec;
-  std::map<std::string, int> key_index;
-  std::vector<std::vector<float>> host_w;
-  std::vector<char> loaded;
+  WeightStore store;   // torchvision's MobileNetV2 `features` state_dict (build_keys)
   bool packed = false;
-  std::vector<void*> allocs;
+  DeviceArena arena;
 
   float *stem_w = nullptr, *stem_b = nullptr;
   struct Block {
@@ -132,49 +115,33 @@ int fail(dhw_style* h, int code, const char* fmt, ...) noexcept {
     if (e_ != hipSuccess) return fail(h, DHW_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));               \
   } while (0)
 
+// a DeviceArena call of the handle: the message names the HIP call that failed, as SHIP does
+#define SARENA(h, call)                                                                                      \
+  do {                                                                                                       \
+    hipError_t e_ = (h)->arena.call;                                                                         \
+    if (e_ != hipSuccess) return fail(h, DHW_ERR_HIP, "%s: %s", (h)->arena.failed, hipGetErrorString(e_));   \
+  } while (0)
+
 int dev_alloc(dhw_style* h, void** p, size_t bytes) {
-  SHIP(h, hipMalloc(p, bytes ? bytes : 16));
-  h->allocs.push_back(*p);
-  SHIP(h, hipMemset(*p, 0, bytes ? bytes : 16));
+  SARENA(h, alloc(p, bytes));
   return 0;
 }
 int upload_f32(dhw_style* h, const std::vector<float>& v, float** out) {
-  int rc = dev_alloc(h, (void**)out, v.size() * 4);
-  if (rc) return rc;
-  SHIP(h, hipMemcpy(*out, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+  SARENA(h, upload_f32(v, out));
   return 0;
 }
-// row-major Wf[N][K] -> MFMA-fragment order [N/16][K/32][64 lanes][8] in the handle's element type (as dhw_api.cpp)
+// row-major Wf[N][K] -> MFMA-fragment order (host/convert.h pack_mfma) in the handle's element type
 int upload_packed(dhw_style* h, const std::vector<float>& wf, int N, int K, void** out) {
-  const size_t n = (size_t)N * K;
-  std::vector<float> pk(n);
-  size_t o = 0;
-  for (int nt = 0; nt < N / 16; ++nt)
-    for (int kc = 0; kc < K / 32; ++kc)
-      for (int l = 0; l < 64; ++l)
-        for (int j = 0; j < 8; ++j) pk[o++] = wf[(size_t)(nt * 16 + (l & 15)) * K + kc * 32 + 8 * (l >> 4) + j];
-  int rc = dev_alloc(h, out, n * h->es);
-  if (rc) return rc;
-  if (h->prec == PREC_F32) {
-    SHIP(h, hipMemcpy(*out, pk.data(), n * 4, hipMemcpyHostToDevice));
-  } else {
-    std::vector<uint16_t> b(n);
-    for (size_t i = 0; i < n; ++i) b[i] = f2bf(pk[i]);
-    SHIP(h, hipMemcpy(*out, b.data(), n * 2, hipMemcpyHostToDevice));
-  }
+  SARENA(h, upload_packed(wf, N, K, h->prec != PREC_F32, out));
   return 0;
 }
 
 // (finalize-time only; a miss is a programming error: recorded, finalize returns DHW_ERR_INTERNAL, nothing throws)
 const std::vector<float>& W(dhw_style* h, const std::string& k) {
-  static const std::vector<float> none(4096, 0.f);   // (long enough for every per-channel read of the packing loops)
-  auto it = h->key_index.find(k);
-  if (it == h->key_index.end()) {
-    if (!h->lookup_fail) fail(h, DHW_ERR_INTERNAL, "internal: the packing code asked for an unknown weight '%s'", k.c_str());
-    h->lookup_fail = true;
-    return none;
-  }
-  return h->host_w[it->second];
+  bool first = false;
+  const std::vector<float>& w = h->store.get(k, &first);
+  if (first) fail(h, DHW_ERR_INTERNAL, "internal: the packing code asked for an unknown weight '%s'", k.c_str());
+  return w;
 }
 
 // eval-mode BatchNorm2d as a per-channel affine: y = x * scale + shift
@@ -274,10 +241,7 @@ int dhw_style_create(dhw_style** out, int precision, int device) {
     h->device = device;
     h->prec = precision == DHW_PREC_F32 ? PREC_F32 : PREC_BF16;
     h->es = h->prec == PREC_F32 ? 4 : 2;
-    h->spec = build_keys();
-    for (size_t i = 0; i < h->spec.size(); ++i) h->key_index[h->spec[i].key] = (int)i;
-    h->host_w.resize(h->spec.size());
-    h->loaded.assign(h->spec.size(), 0);
+    h->store.init(build_keys());
     if (hipSetDevice(device) != hipSuccess || gemm_init() != hipSuccess)
       return fail(nullptr, DHW_ERR_HIP, "device setup failed: %s", hipGetErrorString(hipGetLastError()));
     hold.p = nullptr;
@@ -291,21 +255,21 @@ void dhw_style_destroy(dhw_style* h) {
   try {
     hipSetDevice(h->device);
     hipDeviceSynchronize();
-    for (void* p : h->allocs) hipFree(p);
+    h->arena.free_all();
     delete h;
   } catch (...) {
   }
 }
 
-int dhw_style_num_keys(dhw_style* h) { return h ? (int)h->spec.size() : DHW_ERR_ARG; }
+int dhw_style_num_keys(dhw_style* h) { return h ? (int)h->store.spec.size() : DHW_ERR_ARG; }
 
 int dhw_style_key_info(dhw_style* h, int i, const char** key, int64_t shape[4], int* ndim) {
   STYLE_GUARD(h, "dhw_style_key_info", int, {
-    if (!h || i < 0 || i >= (int)h->spec.size()) return DHW_ERR_ARG;
-    if (key) *key = h->spec[i].key.c_str();
-    if (ndim) *ndim = (int)h->spec[i].shape.size();
+    if (!h || i < 0 || i >= (int)h->store.spec.size()) return DHW_ERR_ARG;
+    if (key) *key = h->store.spec[i].key.c_str();
+    if (ndim) *ndim = (int)h->store.spec[i].shape.size();
     if (shape)
-      for (size_t k = 0; k < h->spec[i].shape.size(); ++k) shape[k] = h->spec[i].shape[k];
+      for (size_t k = 0; k < h->store.spec[i].shape.size(); ++k) shape[k] = h->store.spec[i].shape[k];
     return 0;
   });
 }
@@ -316,22 +280,12 @@ int dhw_style_load(dhw_style* h, const char* key, const void* host_ptr, int dtyp
     const std::string k = key;
     // the parts of torchvision's MobileNetV2 state_dict the feature extractor does not use
     if (k.rfind("classifier.", 0) == 0 || (k.size() > 19 && k.compare(k.size() - 19, 19, "num_batches_tracked") == 0)) return 0;
-    auto it = h->key_index.find(k);
-    if (it == h->key_index.end()) return fail(h, DHW_ERR_KEY, "unexpected key in MobileNetV2 state_dict: %s", key);
-    const SKey& s = h->spec[it->second];
-    bool ok = ndim == (int)s.shape.size();
-    size_t n = 1;
-    for (int i = 0; ok && i < ndim; ++i) { ok = shape[i] == s.shape[i]; n *= (size_t)s.shape[i]; }
-    if (!ok) return fail(h, DHW_ERR_KEY, "size mismatch for %s", key);
-    std::vector<float>& dst = h->host_w[it->second];
-    dst.resize(n);
-    switch (dtype) {
-      case DHW_F32: std::memcpy(dst.data(), host_ptr, n * 4); break;
-      case DHW_F64: for (size_t i = 0; i < n; ++i) dst[i] = (float)((const double*)host_ptr)[i]; break;
-      case DHW_BF16: for (size_t i = 0; i < n; ++i) dst[i] = bf2f(((const uint16_t*)host_ptr)[i]); break;
-      default: return fail(h, DHW_ERR_ARG, "dhw_style_load: unsupported dtype %d", dtype);
+    switch (h->store.load(key, host_ptr, dtype, shape, ndim, /*f16_ok=*/false)) {
+      case WeightStore::UNKNOWN_KEY: return fail(h, DHW_ERR_KEY, "unexpected key in MobileNetV2 state_dict: %s", key);
+      case WeightStore::SIZE_MISMATCH: return fail(h, DHW_ERR_KEY, "size mismatch for %s", key);
+      case WeightStore::BAD_DTYPE: return fail(h, DHW_ERR_ARG, "dhw_style_load: unsupported dtype %d", dtype);
+      case WeightStore::LOADED: break;
     }
-    h->loaded[it->second] = 1;
     h->packed = false;
     return 0;
   });
@@ -341,8 +295,7 @@ int dhw_style_finalize(dhw_style* h) {
   STYLE_GUARD(h, "dhw_style_finalize", int, {
     if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
     if (h->packed) return 0;
-    for (size_t i = 0; i < h->spec.size(); ++i)
-      if (!h->loaded[i]) return fail(h, DHW_ERR_KEY, "missing key in MobileNetV2 state_dict: %s", h->spec[i].key.c_str());
+    if (const int m = h->store.first_missing(); m >= 0) return fail(h, DHW_ERR_KEY, "missing key in MobileNetV2 state_dict: %s", h->store.spec[m].key.c_str());
     SHIP(h, hipSetDevice(h->device));
     SHIP(h, hipDeviceSynchronize());
     int rc;
@@ -380,7 +333,7 @@ int dhw_style_finalize(dhw_style* h) {
       h->blocks.push_back(b);
     }
     if ((rc = pack_pointwise(h, "features.18.0.weight", "features.18.1", kLast, 320, kLast, padc(320), &h->w_last, &h->b_last))) return rc;
-    if (h->lookup_fail) return DHW_ERR_INTERNAL;
+    if (h->store.lookup_fail) return DHW_ERR_INTERNAL;
     h->packed = true;
     return 0;
   });

@@ -14,6 +14,7 @@
 #include "../../include/dhw_train.h"
 #include "abi_guard.h"
 #include "dhw_kernels.h"
+#include "host/device_arena.h"
 
 namespace {
 
@@ -37,32 +38,23 @@ int tfail(int code, const char* fmt, ...) noexcept {
 
 // scratch allocations of one dhw_train_convblock call, released on every exit path
 struct Scratch {
-  std::vector<void*> ptrs;
+  DeviceArena arena;
   ~Scratch() {
     hipDeviceSynchronize();
-    for (void* p : ptrs) hipFree(p);
+    arena.free_all();
   }
   float* f32(size_t n) {
     void* p = nullptr;
-    if (hipMalloc(&p, (n ? n : 4) * sizeof(float)) != hipSuccess) return nullptr;
-    hipMemset(p, 0, (n ? n : 4) * sizeof(float));
-    ptrs.push_back(p);
-    return (float*)p;
+    return arena.alloc(&p, n * sizeof(float)) == hipSuccess ? (float*)p : nullptr;
   }
   float* upload(const std::vector<float>& v) {
-    float* p = f32(v.size());
-    if (p && hipMemcpy(p, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return p;
+    float* p = nullptr;
+    return arena.upload_f32(v, &p) == hipSuccess ? p : nullptr;
   }
-  // row-major Wf[N][K] -> MFMA-fragment order [N/16][K/32][64 lanes][8], fp32 (as dhw_api.cpp upload_packed)
+  // row-major Wf[N][K] -> MFMA-fragment order, fp32 (host/convert.h pack_mfma)
   float* packed(const std::vector<float>& wf, int N, int K) {
-    std::vector<float> pk((size_t)N * K);
-    size_t o = 0;
-    for (int nt = 0; nt < N / 16; ++nt)
-      for (int kc = 0; kc < K / 32; ++kc)
-        for (int l = 0; l < 64; ++l)
-          for (int j = 0; j < 8; ++j) pk[o++] = wf[(size_t)(nt * 16 + (l & 15)) * K + kc * 32 + 8 * (l >> 4) + j];
-    return upload(pk);
+    void* p = nullptr;
+    return arena.upload_packed(wf, N, K, false, &p) == hipSuccess ? (float*)p : nullptr;
   }
 };
 

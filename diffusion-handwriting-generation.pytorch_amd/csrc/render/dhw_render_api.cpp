@@ -9,17 +9,16 @@
 
 #include "../../../include/dhw.h"
 #include "../abi_guard.h"
+#include "../host/error.h"
 #include "render.h"
 
 namespace {
 
-// Errors without a handle are read through dhw_last_error(NULL), whose buffer (a non-const ErrBuf of dhw_api.cpp) is the
-// library's one global message slot: the rasteriser writes its message into that slot.
+// Errors without a handle are read through dhw_last_error(NULL): the library's one global message slot (host/error.h).
 int rfail(int code, const char* fmt, ...) noexcept {
-  char* slot = const_cast<char*>(dhw_last_error(nullptr));
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(slot, sizeof(ErrBuf::s), fmt, ap);
+  set_global_error(fmt, ap);
   va_end(ap);
   return code;
 }

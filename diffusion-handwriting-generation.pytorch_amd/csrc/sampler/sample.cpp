@@ -1,0 +1,437 @@
+// sampler/sample.cpp — dhw_forward and the T-step sampler (== inference.py:80-96): the noise schedule, the per-T FiLM tables,
+// ragged-length staging, the sampling loop with its hipGraph cache and persistent step plans, and dhw_work's operation count.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "denoiser.h"
+
+static int check_shapes(dhw_handle* h, int B, int L, int Lt) {
+  const dhw_dims& d = h->dims;
+  if (B < 1 || B > d.max_B || L < 8 || L > d.max_L || L % 8 || Lt < 1 || Lt > d.max_Lt)
+    return fail(h, DHW_ERR_ARG, "shape out of range: B=%d (max %d) L=%d (max %d, multiple of 8) Lt=%d (max %d)", B, d.max_B, L, d.max_L, Lt, d.max_Lt);
+  return 0;
+}
+
+static int ensure_film_T(dhw_handle* h, int T, dhw_handle::FilmT** out) {
+  dhw_handle::FilmT& ft = h->film_T[T];
+  *out = &ft;
+  if (ft.d_film) return 0;
+  int rc;
+  if ((rc = dev_alloc(h, (void**)&ft.d_sigma, (size_t)T * 4))) return rc;
+  if ((rc = dev_alloc(h, (void**)&ft.d_sig32, (size_t)T * SIG * 4))) return rc;
+  if ((rc = dev_alloc(h, (void**)&ft.d_film, (size_t)T * 2 * h->film_tot * 4))) return rc;
+  return 0;
+}
+
+void schedule_host(int T, std::vector<float>& beta, std::vector<float>& alpha) {
+  // utils/nn.py:19-39 in fp32: torch.linspace evaluates fma(step, i, start) below the midpoint and
+  // fma(-step, n-1-i, end) above it (probed against torch 2.10 CPU); then exp, + 0.02,
+  // cumprod(1 - beta) (inference.py:81).
+  beta.resize(T);
+  alpha.resize(T);
+  const float lo = (float)std::log(1e-5), hi = (float)std::log(0.4);
+  const float step = T > 1 ? (hi - lo) / (float)(T - 1) : 0.f;
+  const int half = T / 2;
+  double a = 1.0;   // torch's CPU cumprod accumulates float inputs in double (acc_type) and rounds each output
+  for (int i = 0; i < T; ++i) {
+    // (a one-point linspace is its START: torch.linspace(a, b, 1) = [a]; the symmetric form alone gave the end point for T = 1)
+    const float x = T == 1 ? lo : i < half ? fmaf(step, (float)i, lo) : fmaf(-step, (float)(T - 1 - i), hi);
+    beta[i] = 0.02f + expf(x);
+    a = a * (double)(1.0f - beta[i]);
+    alpha[i] = (float)a;
+  }
+}
+
+// Ragged calls: check the caller's lengths (host pointer, B entries), refuse the diagnostic configurations that have no per-sample
+// ends, and copy the lengths into h->d_lens on the caller's stream.  The copy's source is the handle's pinned buffer, rewritten only
+// once the previous call's copy has read it (an event on that copy, not a device-wide synchronize).
+static int stage_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling, hipStream_t st) {
+  if (!lens) return fail(h, DHW_ERR_ARG, "%s: lens is NULL (B = %d entries expected)", fn, B);
+  for (int b = 0; b < B; ++b)
+    if (lens[b] < 8 || lens[b] > L || lens[b] % 8)
+      return fail(h, DHW_ERR_ARG, "%s: lens[%d] = %d: every length must be a multiple of 8 in [8, L = %d]", fn, b, (int)lens[b], L);
+  if (sampling && h->persist) return fail(h, DHW_ERR_ARG, "%s: the persistent step kernel (DHW_PERSIST=1) does not support per-sample lengths", fn);
+  HIPCK(h, hipEventSynchronize(h->lens_ev));
+  memcpy(h->h_lens_pin, lens, (size_t)B * 4);
+  HIPCK(h, hipMemcpyAsync(h->d_lens, h->h_lens_pin, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  HIPCK(h, hipEventRecord(h->lens_ev, st));
+  return 0;
+}
+
+int forward_impl(dhw_handle* h, const char* fn, const float* strokes, const int64_t* text, const float* sigma, const float* style,
+                 int B, int L, int Lt, float* eps_out, float* pen_out, void* hip_stream, const int32_t* lens_host, bool ragged) {
+  {
+    if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
+    if (!strokes || !text || !sigma || !style || !eps_out || !pen_out) return fail(h, DHW_ERR_ARG, "%s: null pointer", fn);
+    int rc = check_shapes(h, B, L, Lt);
+    if (rc) return rc;
+    if ((rc = dhw_finalize(h))) return rc;
+    HIPCK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (ragged && (rc = stage_lens(h, fn, lens_host, B, L, false, st))) return rc;
+    Ctx c{h, &h->ws[0], st, B, L, Lt, h->dims.S * 5, h->d_film, 2L * h->film_tot};
+    c.lens = ragged ? h->d_lens : nullptr;
+    taps_clear(h);
+    RUN_SMALL(c, "sigma_ffn", launch_sigma_ffn(sigma, B, h->sg_w1, h->sg_b1, h->sg_w2, h->sg_b2, h->d_sig32, st));
+    RUN_SMALL(c, "film_table", launch_film(h->d_sig32, B, h->d_film_w, h->d_film_b, 2 * h->film_tot, h->d_film, st));
+    tap(c, TAP_SIGMA_FFN, h->d_sig32, 1, SIG, true);
+    text_style_static(c, text, style);
+    text_style_dynamic(c);
+    stroke_path(c, strokes, text);
+    HeadsParams hp{};
+    hp.eps = eps_out;
+    hp.pen = pen_out;
+    launch_heads_for(c, hp);
+    if (c.lens) {   // ragged: eps / pen past each sample's end are 0
+      RUN_SMALL(c, "zero_tail", launch_zero_tail(eps_out, B, L, 2, c.lens, st));
+      RUN_SMALL(c, "zero_tail", launch_zero_tail(pen_out, B, L, 1, c.lens, st));
+    }
+    h->last_B = B; h->last_L = L; h->last_Lt = Lt;
+    return c.err;
+  }
+}
+
+// sampler steps whose text side is precomputed together (bounds the plane's memory for long schedules)
+static int plane_chunk(int T) { return std::min(T, 64); }
+
+// What is constant over one dhw_sample call: the shape, the library-owned staging buffers the call reads and writes, the
+// schedule (T entries each), and the device lengths of a ragged call (or null).
+struct SampleCall {
+  int B, L, Lt, T, mode;
+  const int64_t* text;
+  const float *style, *noise;
+  float* out;
+  const float *beta, *alpha;
+  const int* lens;
+};
+
+// One prompt sub-batch [b0, b0+Bs) of a B-prompt batch, enqueued on `st` with workspace `w`.
+// d_plans: device array of T StepPlans (persist.h) -> every denoiser call is ONE persistent launch; rec_out: record mode —
+// nothing is launched, the T plans are built on the host (rec_out->size() != T afterwards: this shape has no persistent form).
+static int sample_enqueue(dhw_handle* h, const SampleCall& sc, Workspace* w, int b0, int Bs, hipStream_t st, const StepPlan* d_plans = nullptr,
+                          std::vector<StepPlan>* rec_out = nullptr) {
+  const int B = sc.B, L = sc.L, Lt = sc.Lt, T = sc.T, mode = sc.mode;
+  const int64_t* text = sc.text;
+  const float *style = sc.style, *noise = sc.noise, *alpha = sc.alpha, *beta = sc.beta;
+  float* out = sc.out;
+  const int* lens = sc.lens;
+  const long rows = (long)Bs * L;
+  const size_t step_stride = (size_t)B * L * 2;   // one noise draw for the whole batch
+  text += (size_t)b0 * Lt;
+  style += (size_t)b0 * h->dims.S * 1280;
+  out += (size_t)b0 * L * 3;
+  if (noise) noise += (size_t)b0 * L * 2;
+  Ctx c{h, w, st, Bs, L, Lt, h->dims.S * 5, h->d_film_T, 0};
+  c.fuse_input = true;
+  c.lens = lens ? lens + b0 : nullptr;
+  // x_T
+  if (rec_out) {
+  } else if (noise) {
+    hipError_t e = hipMemcpyAsync(w->d_xt, noise, rows * 2 * 4, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return fail(h, DHW_ERR_HIP, "memcpy x_T: %s", hipGetErrorString(e));
+  } else {
+    RUN_SMALL(c, "randn_init", launch_randn_init(w->d_xt, rows, L, h->d_seed, b0, st));
+  }
+  // ragged: the padding rows of the sampler state start (and stay) 0 — nothing of a valid row reads them
+  if (!rec_out && c.lens) RUN_SMALL(c, "zero_tail", launch_zero_tail(w->d_xt, Bs, L, 2, c.lens, st));
+  if (!rec_out) text_style_static(c, text, style);   // sigma-independent: once per sample batch, not per step
+  const int TC = plane_chunk(T);
+  for (int step = 0, i = T - 1; i >= 0; --i, ++step) {
+    if (!rec_out && h->teach_every > 0 && step > 0 && step % h->teach_every == 0) {
+      // teacher forcing (tests only): x after `step` steps -> capture[k], x := reset[k]
+      const size_t k = (size_t)(step / h->teach_every - 1), off = (k * B + b0) * (size_t)L * 2;
+      hipError_t e = hipMemcpyAsync(h->teach_capture + off, w->d_xt, rows * 2 * 4, hipMemcpyDeviceToDevice, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(w->d_xt, h->teach_reset + off, rows * 2 * 4, hipMemcpyDeviceToDevice, st);
+      if (e != hipSuccess) return fail(h, DHW_ERR_HIP, "teacher copy: %s", hipGetErrorString(e));
+    }
+    if (!rec_out && h->plane && step % TC == 0) {
+      // The text side (TextStyleEncoder + every layer's text K/V, text_style.py:91-104, model.py:38-42) depends on
+      // (text, style, sigma_i) only and the sigma schedule is known: evaluate it for the next `ns` steps in ONE
+      // batched pass (ns*Bs "samples", FiLM row per step) instead of 16 small launches inside every step.
+      const int ns = std::min(TC, T - step);
+      Ctx cp = c;
+      cp.B = ns * Bs;
+      cp.in_B = Bs;
+      cp.film = h->d_film_T + (size_t)i * 2 * h->film_tot;   // step `step + k` uses schedule index i - k
+      cp.film_bs = -2L * h->film_tot;
+      cp.film_div = Bs;
+      cp.planeT = true;
+      text_style_dynamic(cp);
+      if (cp.err) return cp.err;
+    }
+    c.film = h->d_film_T + (size_t)i * 2 * h->film_tot;
+    c.use_plane = h->plane;
+    c.plane_step = step % TC;
+    if (!h->plane) {
+      if (rec_out) return 0;   // (the persistent form reads the text K/V from the all-steps plane)
+      text_style_dynamic(c);
+    }
+    HeadsParams hp{};
+    hp.eps = nullptr;
+    hp.pen = nullptr;
+    hp.xt = w->d_xt;
+    hp.z = noise ? noise + (size_t)(1 + step) * step_stride : nullptr;
+    hp.mode = mode;
+    hp.seed_ptr = h->d_seed;
+    hp.sample_off = b0;
+    hp.iter = step;
+    const float a = alpha[i], b = beta[i];
+    const float a_next = i > 1 ? alpha[i - 1] : 1.0f;   // inference.py:87
+    hp.k0 = sqrtf(1.0f - a);
+    if (mode == 0) {
+      hp.k1 = sqrtf(1.0f - b);
+      hp.k2 = sqrtf(1.0f - a_next);
+      hp.add_noise = 1;
+    } else {
+      hp.k1 = 1.0f / sqrtf(1.0f - b);
+      hp.k2 = sqrtf(b);
+      hp.k3 = b;
+      hp.add_noise = i != 0;   // inference.py:92
+    }
+    if (i == 0) hp.out3 = out;
+    const bool fh = h->fuse && h->fuse_heads;
+    c.fhp = fh ? &hp : nullptr;
+    if (rec_out) {
+      if (!fh) return 0;
+      std::vector<StepPhase> phases;
+      c.rec = &phases;
+      c.rec_fail = false;
+      stroke_path(c, w->d_xt, text);
+      c.rec = nullptr;
+      if (c.rec_fail || c.err || phases.empty()) return c.err;
+      StepPlan sp{};
+      sp.nphase = (int)phases.size();
+      sp.B = Bs;
+      sp.spx = (Bs + STEP_XCDS - 1) / STEP_XCDS;
+      sp.sync = h->d_step_sync;
+      sp.err = h->d_step_err;
+      for (size_t k = 0; k < phases.size(); ++k) { sp.ph[k] = phases[k]; sp.cum_tps[k + 1] = sp.cum_tps[k] + phases[k].tps; }
+      rec_out->push_back(sp);
+      continue;
+    }
+    if (d_plans) {
+      Launch l(h, st, "step.persistent");
+      hipError_t e = launch_step(d_plans + step, h->persist_grid, st);
+      if (e != hipSuccess) return fail(h, DHW_ERR_HIP, "persistent step %d: %s", step, hipGetErrorString(e));
+      continue;
+    }
+    stroke_path(c, w->d_xt, text);
+    if (!fh) launch_heads_for(c, hp);
+    if (!fh && c.lens) RUN_SMALL(c, "zero_tail", launch_zero_tail(w->d_xt, Bs, L, 2, c.lens, st));   // (the stand-alone heads step every row)
+    if (c.err) return c.err;
+  }
+  // ragged: the output rows past each sample's end (the last step's tiles there exited without writing) are 0
+  if (!rec_out && c.lens) RUN_SMALL(c, "zero_tail", launch_zero_tail(out, Bs, L, 3, c.lens, st));
+  return c.err;
+}
+
+// The StepPlans of one dhw_sample shape (cached like the graphs): built by running the enqueue in record mode, uploaded once.
+// Returns null when this shape / configuration has no persistent form (the caller then launches kernel by kernel).
+// (only calls without per-sample lengths get here: sc.lens is null)
+static const StepPlan* ensure_step_plans(dhw_handle* h, const std::vector<uint64_t>& key, const SampleCall& sc) {
+  if (!h->persist || h->nstreams != 1 || h->prec != PREC_BF16 || !h->fuse || !h->plane || !h->fuse_heads || !h->fuse_up || !h->chain) return nullptr;
+  auto it = h->plans.find(key);
+  if (it != h->plans.end()) return it->second.ok ? it->second.dev : nullptr;
+  dhw_handle::StepPlans& sp = h->plans[key];
+  const size_t need = step_sync_words(sc.B);
+  if (need > h->step_sync_words) {   // (earlier plans keep the smaller buffer: it is never freed before destroy)
+    if (dev_alloc(h, (void**)&h->d_step_sync, need * sizeof(unsigned))) return nullptr;
+    h->step_sync_words = need;
+  }
+  std::vector<StepPlan> host;
+  if (sample_enqueue(h, sc, &h->ws[0], 0, sc.B, nullptr, nullptr, &host) || (int)host.size() != sc.T)
+    return nullptr;
+  if (getenv("DHW_PERSIST_TRACE") && atoi(getenv("DHW_PERSIST_TRACE"))) {
+    if (!h->d_step_trace && dev_alloc(h, (void**)&h->d_step_trace, (size_t)h->persist_grid * STEP_MAX_PHASES * 4 * 8)) return nullptr;
+    host.back().trace = h->d_step_trace;
+  }
+  if (dev_alloc(h, (void**)&sp.dev, host.size() * sizeof(StepPlan), false)) return nullptr;
+  if (hipMemcpy(sp.dev, host.data(), host.size() * sizeof(StepPlan), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+  sp.ok = true;
+  return sp.dev;
+}
+
+// All sub-batches of one dhw_sample call.  On a capturing stream the sub-batches fork onto the handle's
+// side streams (parallel graph branches) and join back; eagerly (profiling) they run one after another.
+static int sample_enqueue_all(dhw_handle* h, const SampleCall& sc, bool fork, hipStream_t st, const StepPlan* d_plans = nullptr) {
+  const int B = sc.B;
+  const int ns = std::min(h->nstreams, B);
+  const int per = (B + ns - 1) / ns;
+  taps_clear(h);
+  if (!fork || ns == 1) {
+    for (int s = 0, b0 = 0; b0 < B; ++s, b0 += per) {
+      int rc = sample_enqueue(h, sc, &h->ws[s], b0, std::min(per, B - b0), st, ns == 1 ? d_plans : nullptr);
+      if (rc) return rc;
+    }
+    return 0;
+  }
+  hipEvent_t fork_ev, join_ev[MAX_STREAMS] = {};
+  if (hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming) != hipSuccess) return fail(h, DHW_ERR_HIP, "event create failed");
+  int rc = 0;
+  if (hipEventRecord(fork_ev, st) != hipSuccess) rc = fail(h, DHW_ERR_HIP, "fork record failed");
+  for (int s = 1, b0 = per; !rc && b0 < B; ++s, b0 += per) {
+    hipStream_t ss = h->sub_streams[s];
+    if (hipStreamWaitEvent(ss, fork_ev, 0) != hipSuccess) { rc = fail(h, DHW_ERR_HIP, "fork wait failed"); break; }
+    rc = sample_enqueue(h, sc, &h->ws[s], b0, std::min(per, B - b0), ss);
+    if (rc) break;
+    if (hipEventCreateWithFlags(&join_ev[s], hipEventDisableTiming) != hipSuccess || hipEventRecord(join_ev[s], ss) != hipSuccess)
+      rc = fail(h, DHW_ERR_HIP, "join record failed");
+  }
+  if (!rc) rc = sample_enqueue(h, sc, &h->ws[0], 0, std::min(per, B), st);
+  for (int s = 1; s < MAX_STREAMS; ++s)
+    if (join_ev[s]) {
+      if (!rc && hipStreamWaitEvent(st, join_ev[s], 0) != hipSuccess) rc = fail(h, DHW_ERR_HIP, "join wait failed");
+      hipEventDestroy(join_ev[s]);
+    }
+  hipEventDestroy(fork_ev);
+  return rc;
+}
+
+int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float* style, int B, int L, int Lt, int T, int mode,
+                const float* noise, uint64_t seed, int64_t first_sample, float* out, void* hip_stream, const int32_t* lens_host, bool ragged) {
+  {
+    if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
+    if (!text || !style || !out) return fail(h, DHW_ERR_ARG, "%s: null pointer", fn);
+    if (T < 1 || (mode != 0 && mode != 1)) return fail(h, DHW_ERR_ARG, "%s: bad T/mode", fn);
+    int rc = check_shapes(h, B, L, Lt);
+    if (rc) return rc;
+    if ((rc = dhw_finalize(h))) return rc;
+    HIPCK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (ragged && (rc = stage_lens(h, fn, lens_host, B, L, true, st))) return rc;
+    const int* lens = ragged ? h->d_lens : nullptr;
+    if (h->h_step_err && *(volatile unsigned*)h->h_step_err) {
+      // a persistent step kernel gave up waiting (bounded spin, persist.h): its results were wrong; say so and fall back for good
+      const unsigned code = *(volatile unsigned*)h->h_step_err;
+      *(volatile unsigned*)h->h_step_err = 0;
+      h->persist = false;
+      hipDeviceSynchronize();
+      for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
+      h->graphs.clear();
+      if (h->d_step_sync) hipMemset(h->d_step_sync, 0, h->step_sync_words * sizeof(unsigned));
+      if (code >= 0x100u)
+        return fail(h, DHW_ERR_HIP, "persistent step kernel: XCD %u owns samples but no workgroup of the launch ran there in an EARLIER call (partitioned / "
+                    "CU-masked device?): those samples were never computed; persistent launches are now disabled for this handle", code - 0x100u);
+      return fail(h, DHW_ERR_HIP, "persistent step kernel timed out waiting for phase %u in an EARLIER call (its samples were invalid); "
+                  "persistent launches are now disabled for this handle", code - 1);
+    }
+    dhw_handle::FilmT* ft = nullptr;
+    if ((rc = ensure_film_T(h, T, &ft))) return rc;
+    h->d_film_T = ft->d_film;
+    if (h->plane) {
+      const int ns = std::min(h->nstreams, B), per = (B + ns - 1) / ns;
+      for (int s = 0; s < ns; ++s)
+        if ((rc = ensure_plane(h, h->ws[s], plane_chunk(T), per))) return rc;
+    }
+    std::vector<float> beta, alpha;
+    schedule_host(T, beta, alpha);
+    if (!ft->ready) {
+      // once per (weights, T): sigma_i = sqrt(abar_i) -> sigma MLP -> FiLM table [T, 2*TOT]; uploaded on the caller's
+      // stream from a buffer the handle owns, so it is ordered against everything else this call enqueues
+      ft->h_sigma.resize(T);
+      for (int i = 0; i < T; ++i) ft->h_sigma[i] = sqrtf(alpha[i]);   // inference.py:89
+      HIPCK(h, hipMemcpyAsync(ft->d_sigma, ft->h_sigma.data(), T * 4, hipMemcpyHostToDevice, st));
+      Ctx c{h, &h->ws[0], st, B, L, Lt, h->dims.S * 5, ft->d_film, 0};
+      RUN_SMALL(c, "sigma_ffn", launch_sigma_ffn(ft->d_sigma, T, h->sg_w1, h->sg_b1, h->sg_w2, h->sg_b2, ft->d_sig32, st));
+      RUN_SMALL(c, "film_table", launch_film(ft->d_sig32, T, h->d_film_w, h->d_film_b, 2 * h->film_tot, ft->d_film, st));
+      if (c.err) return c.err;
+      ft->ready = true;
+    }
+    {
+      hipError_t e = launch_set_seed(h->d_seed, seed, first_sample, st);
+      if (e != hipSuccess) return fail(h, DHW_ERR_HIP, "set_seed: %s", hipGetErrorString(e));
+    }
+
+    // stage the caller's tensors into library-owned buffers (tiny D2D copies, outside the graph)
+    const size_t rows = (size_t)B * L;
+    HIPCK(h, hipMemcpyAsync(h->d_text_stage, text, (size_t)B * Lt * 8, hipMemcpyDeviceToDevice, st));
+    HIPCK(h, hipMemcpyAsync(h->d_style_stage, style, (size_t)B * h->dims.S * 1280 * 4, hipMemcpyDeviceToDevice, st));
+    const float* nz = nullptr;
+    if (noise) {
+      const size_t need = (size_t)(T + 1) * rows * 2;
+      if (need > h->noise_stage_cap) {
+        HIPCK(h, hipDeviceSynchronize());
+        for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // they captured the old staging pointer
+        h->graphs.clear();
+        h->plans.clear();   // (so did the step plans)
+        if ((rc = dev_alloc(h, (void**)&h->d_noise_stage, need * 4, false))) return rc;
+        h->noise_stage_cap = need;
+      }
+      HIPCK(h, hipMemcpyAsync(h->d_noise_stage, noise, need * 4, hipMemcpyDeviceToDevice, st));
+      nz = h->d_noise_stage;
+    }
+
+    const SampleCall sc{B, L, Lt, T, mode, h->d_text_stage, h->d_style_stage, nz, h->d_out_stage, beta.data(), alpha.data(), lens};
+    const bool graph = h->use_graph && !h->prof && !h->teach_every;
+    if (!graph) {
+      // eager launches: sub-batches still fork onto the side streams (concurrent kernels of different sub-batches);
+      // profiling keeps one stream so the per-launch events bracket one kernel each
+      rc = sample_enqueue_all(h, sc, !h->prof, st);
+    } else {
+      const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)Lt, (uint64_t)T, (uint64_t)mode, (uint64_t)(nz != nullptr), (uint64_t)h->nstreams, (uint64_t)h->plane, (uint64_t)h->fuse_heads, (uint64_t)h->fuse_up, (uint64_t)h->chain, (uint64_t)h->persist,
+                                           (uint64_t)ragged};   // (ragged: the kernels read the lengths from h->d_lens at replay)
+      auto it = h->graphs.find(key);
+      if (it == h->graphs.end()) {
+        const StepPlan* d_plans = ragged ? nullptr : ensure_step_plans(h, key, sc);   // (before the capture: it uploads)
+        hipStream_t cs;
+        HIPCK(h, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+        hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+        if (e != hipSuccess) { hipStreamDestroy(cs); return fail(h, DHW_ERR_HIP, "begin capture: %s", hipGetErrorString(e)); }
+        rc = sample_enqueue_all(h, sc, true, cs, d_plans);
+        hipGraph_t g = nullptr;
+        e = hipStreamEndCapture(cs, &g);
+        if (rc == 0 && e != hipSuccess) rc = fail(h, DHW_ERR_HIP, "graph capture failed: %s", hipGetErrorString(e));
+        hipGraphExec_t ex = nullptr;
+        if (rc == 0) {
+          e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+          if (e != hipSuccess) rc = fail(h, DHW_ERR_HIP, "graph instantiate failed: %s", hipGetErrorString(e));
+        }
+        if (g) hipGraphDestroy(g);
+        hipStreamDestroy(cs);
+        if (rc) return rc;
+        it = h->graphs.emplace(key, ex).first;
+      }
+      HIPCK(h, hipGraphLaunch(it->second, st));
+    }
+    if (rc == 0) HIPCK(h, hipMemcpyAsync(out, h->d_out_stage, rows * 3 * 4, hipMemcpyDeviceToDevice, st));
+    h->last_B = B; h->last_L = L; h->last_Lt = Lt;
+    return rc;
+  }
+}
+
+int work_impl(dhw_handle* h, int L, int Lt, double* flops_out, double* bytes_out) {
+  if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
+  const dhw_dims& d = h->ldims;   // the model's own widths: zero padding (pad_weights) is not algorithmic work
+  const double c1 = d.c1, c2 = d.c2, c3 = d.c3, dt = 2 * c2, S5 = d.S * 5;
+  auto cb = [](double L_, double ci, double co) { return 2 * L_ * (3 * ci * co + 1.5 * ci * co + 1.5 * co * co + co * co); };
+  auto el = [&](double Lk, double dm, double heads) {
+    double f = 2 * Lt * dt * dm + 2 * Lt * dm * dm * 2;            // text_dense, k1, v1
+    f += 2 * Lk * dm * dm * 2 + 2 * Lk * dm * dm * 4;              // q1, dense1, qkv2, dense2
+    f += 2 * Lk * dm * 2 * dm * 2;                                 // ffn
+    f += 4 * Lk * Lt * dm + 4 * Lk * Lk * dm;                      // SDPA cross + self
+    (void)heads;
+    return f;
+  };
+  double f = 0;
+  f += 2 * S5 * (STYLE_CH * 4 * c2 + 4 * c2 * dt) + 2 * Lt * dt * dt * 2 + 2 * S5 * dt * dt * 2 + 4 * Lt * S5 * dt + 2 * Lt * dt * 2 * dt * 2;
+  f += 2 * L * 2 * c1;
+  f += cb(L, c1, c1) + cb(L / 2, c1, c2) + cb(L / 4, c2, c3) + cb(L / 4, dt, c3) + cb(L / 2, c3, c2) + cb(L, c2, c1);
+  f += el(L / 2, c2, 3) + el(L / 4, c3, 4) + d.num_layers * el(L / 8, dt, 6);
+  f += 2 * (L / 8) * c3 * dt;
+  f += 2 * 3 * ((L / 4) * c3 * dt + (L / 2) * c2 * c3 + L * c1 * c2);
+  f += 2 * L * c1 * 3;
+  // block-boundary activation bytes: every top-level block reads its inputs and writes its outputs once
+  const double es = (double)h->es;
+  double by = 0;
+  by += L * 2 * 4 + L * 3 * 4;                                                  // strokes in, eps+pen out (fp32)
+  by += es * (L * c1 * 2 + (L / 2) * (c1 + c2) + (L / 4) * (c2 + c3) + (L / 4) * (dt + c3) + (L / 2) * (c3 + c2) + L * (c2 + c1));   // ConvBlocks
+  by += es * 2 * ((L / 2) * c2 + (L / 4) * c3 + d.num_layers * (L / 8) * dt);   // EncoderLayers
+  by += es * ((L / 8) * (c3 + dt));                                             // att_dense
+  by += es * ((L / 4) * (c3 + dt + dt) + (L / 2) * (c2 + c3 + c3) + L * (c1 + c2 + c2));   // skip convs + upsample add
+  by += es * (S5 * STYLE_CH + Lt * dt * (2 + 2 * (2 + d.num_layers)));          // text/style encoder + per-layer text reads
+  if (flops_out) *flops_out = f;
+  if (bytes_out) *bytes_out = by;
+  return 0;
+}

@@ -8,7 +8,7 @@ round-4 review) mix four different launches.  Here every dispatch is attributed 
 enc_bc launches: enc3.bc | enc5.bc -> pool -> att_dense -> att0.a | att0.bc -> att1.a | att1.bc; the six ConvBlocks; enc5.a) and
 compared with a prediction made of two parts:
 
-  activations : every tensor the launch reads or writes, once (bf16): the algorithmic count of dhw_api.cpp;
+  activations : every tensor the launch reads or writes, once (bf16): the algorithmic count of csrc/sampler/denoiser.cpp;
   weights x 8 : the launch's packed weights, fetched once PER XCD.  The eight XCDs have private 4 MiB L2s (MI355X_MICROARCH.md,
                 "L2 (per XCD)": not shared, not coherent), every kernel here has workgroups on all eight, and each of them needs the
                 whole layer's weights — so the fabric delivers eight copies per launch whatever the kernel does.  FETCH_SIZE counts
