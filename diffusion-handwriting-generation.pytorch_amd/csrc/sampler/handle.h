@@ -153,6 +153,12 @@ struct dhw_handle {
   float* d_out_stage = nullptr;
   float* d_noise_stage = nullptr;
   size_t noise_stage_cap = 0;
+  // conditioned calls (dhw_sample_cond): known [max_B*max_L, 3] and keep [max_B*max_L] are allocated once, at the first such
+  // call, and never move; the conditioning noise [T, B, L, 2] grows like the noise stage (cached graphs and plans dropped first)
+  float* d_known_stage = nullptr;
+  unsigned char* d_keep_stage = nullptr;
+  float* d_cond_noise_stage = nullptr;
+  size_t cond_noise_stage_cap = 0;
   uint64_t* d_seed = nullptr;   // [seed, first_sample] read by the noise kernels
   // ragged calls (dhw_forward_ragged / dhw_sample_ragged): the per-sample lengths, copied on the caller's stream from a pinned host
   // buffer the handle owns.  The kernels read them at run time, so one captured graph serves every set of lengths of a shape.
@@ -178,6 +184,14 @@ struct dhw_handle {
 };
 
 int fail(dhw_handle* h, int code, const char* fmt, ...) noexcept;   // (dhw_api.cpp) records the message, returns code
+
+// The conditioning block of dhw_sample_cond (include/dhw.h), as the caller passed it: device pointers or null.
+struct CondArgs {
+  const float* known;
+  const uint8_t* keep;
+  int t_start;
+  const float* cond_noise;
+};
 
 // The body of every extern "C" entry point runs inside this: no exception leaves the library (abi_guard.h).
 #define DHW_GUARD(h, fn, R, ...) \
@@ -217,7 +231,8 @@ void schedule_host(int T, std::vector<float>& beta, std::vector<float>& alpha);
 int forward_impl(dhw_handle* h, const char* fn, const float* strokes, const int64_t* text, const float* sigma, const float* style,
                  int B, int L, int Lt, float* eps_out, float* pen_out, void* hip_stream, const int32_t* lens_host, bool ragged);
 int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float* style, int B, int L, int Lt, int T, int mode,
-                const float* noise, uint64_t seed, int64_t first_sample, float* out, void* hip_stream, const int32_t* lens_host, bool ragged);
+                const float* noise, uint64_t seed, int64_t first_sample, float* out, void* hip_stream, const int32_t* lens_host, bool ragged,
+                const CondArgs* cond = nullptr);
 int work_impl(dhw_handle* h, int L, int Lt, double* flops_out, double* bytes_out);
 
 // ---------------------------------------------------------------- sampler/debug.cpp

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../cond/cond.h"
 #include "denoiser.h"
 
 static int check_shapes(dhw_handle* h, int B, int L, int Lt) {
@@ -47,12 +48,17 @@ void schedule_host(int T, std::vector<float>& beta, std::vector<float>& alpha) {
 // Ragged calls: check the caller's lengths (host pointer, B entries), refuse the diagnostic configurations that have no per-sample
 // ends, and copy the lengths into h->d_lens on the caller's stream.  The copy's source is the handle's pinned buffer, rewritten only
 // once the previous call's copy has read it (an event on that copy, not a device-wide synchronize).
-static int stage_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling, hipStream_t st) {
+static int check_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling) {
   if (!lens) return fail(h, DHW_ERR_ARG, "%s: lens is NULL (B = %d entries expected)", fn, B);
   for (int b = 0; b < B; ++b)
     if (lens[b] < 8 || lens[b] > L || lens[b] % 8)
       return fail(h, DHW_ERR_ARG, "%s: lens[%d] = %d: every length must be a multiple of 8 in [8, L = %d]", fn, b, (int)lens[b], L);
   if (sampling && h->persist) return fail(h, DHW_ERR_ARG, "%s: the persistent step kernel (DHW_PERSIST=1) does not support per-sample lengths", fn);
+  return 0;
+}
+
+static int stage_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling, hipStream_t st) {
+  if (int rc = check_lens(h, fn, lens, B, L, sampling)) return rc;
   HIPCK(h, hipEventSynchronize(h->lens_ev));
   memcpy(h->h_lens_pin, lens, (size_t)B * 4);
   HIPCK(h, hipMemcpyAsync(h->d_lens, h->h_lens_pin, (size_t)B * 4, hipMemcpyHostToDevice, st));
@@ -97,7 +103,9 @@ int forward_impl(dhw_handle* h, const char* fn, const float* strokes, const int6
 static int plane_chunk(int T) { return std::min(T, 64); }
 
 // What is constant over one dhw_sample call: the shape, the library-owned staging buffers the call reads and writes, the
-// schedule (T entries each), and the device lengths of a ragged call (or null).
+// schedule (T entries each), and the device lengths of a ragged call (or null).  A conditioned call (dhw_sample_cond) adds the
+// staged known strokes (null = unconditioned), the keep mask and the conditioning noise (either may be null) and the number of
+// iterations that run (t_start = T: all of them).
 struct SampleCall {
   int B, L, Lt, T, mode;
   const int64_t* text;
@@ -105,6 +113,10 @@ struct SampleCall {
   float* out;
   const float *beta, *alpha;
   const int* lens;
+  const float* known;
+  const unsigned char* keep;
+  const float* cond_noise;
+  int t_start;
 };
 
 // One prompt sub-batch [b0, b0+Bs) of a B-prompt batch, enqueued on `st` with workspace `w`.
@@ -136,17 +148,36 @@ static int sample_enqueue(dhw_handle* h, const SampleCall& sc, Workspace* w, int
   }
   // ragged: the padding rows of the sampler state start (and stay) 0 — nothing of a valid row reads them
   if (!rec_out && c.lens) RUN_SMALL(c, "zero_tail", launch_zero_tail(w->d_xt, Bs, L, 2, c.lens, st));
+  // conditioned call: iterations [first, T) run; seeded rows start from the known strokes noised to schedule index t_start - 1
+  const int first = T - sc.t_start;
+  CondParams cp0{};
+  if (sc.known) {
+    cp0.x = w->d_xt;
+    cp0.known = sc.known + (size_t)b0 * L * 3;
+    cp0.keep = sc.keep ? sc.keep + (size_t)b0 * L : nullptr;
+    cp0.lens = c.lens;
+    cp0.rows = rows;
+    cp0.L = L;
+    cp0.seed_ptr = h->d_seed;
+    cp0.sample_off = b0;
+    if (!rec_out && (sc.keep || first > 0)) {
+      CondParams cp = cp0;
+      cp.ka = sqrtf(alpha[sc.t_start - 1]);
+      cp.kb = sqrtf(1.0f - alpha[sc.t_start - 1]);
+      RUN_SMALL(c, "cond_start", launch_cond_start(cp, first > 0, st));
+    }
+  }
   if (!rec_out) text_style_static(c, text, style);   // sigma-independent: once per sample batch, not per step
   const int TC = plane_chunk(T);
-  for (int step = 0, i = T - 1; i >= 0; --i, ++step) {
-    if (!rec_out && h->teach_every > 0 && step > 0 && step % h->teach_every == 0) {
+  for (int step = first, i = T - 1 - first; i >= 0; --i, ++step) {
+    if (!rec_out && h->teach_every > 0 && step > first && step % h->teach_every == 0) {
       // teacher forcing (tests only): x after `step` steps -> capture[k], x := reset[k]
       const size_t k = (size_t)(step / h->teach_every - 1), off = (k * B + b0) * (size_t)L * 2;
       hipError_t e = hipMemcpyAsync(h->teach_capture + off, w->d_xt, rows * 2 * 4, hipMemcpyDeviceToDevice, st);
       if (e == hipSuccess) e = hipMemcpyAsync(w->d_xt, h->teach_reset + off, rows * 2 * 4, hipMemcpyDeviceToDevice, st);
       if (e != hipSuccess) return fail(h, DHW_ERR_HIP, "teacher copy: %s", hipGetErrorString(e));
     }
-    if (!rec_out && h->plane && step % TC == 0) {
+    if (!rec_out && h->plane && (step - first) % TC == 0) {   // (chunks are counted from the first iteration that runs)
       // The text side (TextStyleEncoder + every layer's text K/V, text_style.py:91-104, model.py:38-42) depends on
       // (text, style, sigma_i) only and the sigma schedule is known: evaluate it for the next `ns` steps in ONE
       // batched pass (ns*Bs "samples", FiLM row per step) instead of 16 small launches inside every step.
@@ -163,7 +194,7 @@ static int sample_enqueue(dhw_handle* h, const SampleCall& sc, Workspace* w, int
     }
     c.film = h->d_film_T + (size_t)i * 2 * h->film_tot;
     c.use_plane = h->plane;
-    c.plane_step = step % TC;
+    c.plane_step = (step - first) % TC;
     if (!h->plane) {
       if (rec_out) return 0;   // (the persistent form reads the text K/V from the all-steps plane)
       text_style_dynamic(c);
@@ -220,10 +251,21 @@ static int sample_enqueue(dhw_handle* h, const SampleCall& sc, Workspace* w, int
     stroke_path(c, w->d_xt, text);
     if (!fh) launch_heads_for(c, hp);
     if (!fh && c.lens) RUN_SMALL(c, "zero_tail", launch_zero_tail(w->d_xt, Bs, L, 2, c.lens, st));   // (the stand-alone heads step every row)
+    if (sc.keep) {
+      // replacement conditioning: kept rows := the known strokes noised to the level this step arrived at, with the
+      // conditioning stream's own draw (cond_noise[step], or the generator at iteration COND_ITER0 + step)
+      CondParams cp = cp0;
+      cp.ka = sqrtf(a_next);
+      cp.kb = sqrtf(1.0f - a_next);
+      cp.z = sc.cond_noise ? sc.cond_noise + (size_t)step * step_stride + (size_t)b0 * L * 2 : nullptr;
+      cp.iter = COND_ITER0 + step;
+      RUN_SMALL(c, "cond_replace", launch_cond_replace(cp, st));
+    }
     if (c.err) return c.err;
   }
   // ragged: the output rows past each sample's end (the last step's tiles there exited without writing) are 0
   if (!rec_out && c.lens) RUN_SMALL(c, "zero_tail", launch_zero_tail(out, Bs, L, 3, c.lens, st));
+  if (!rec_out && sc.keep) RUN_SMALL(c, "cond_finish", launch_cond_finish(out, cp0, st));   // kept rows of the output are `known`, pen included
   return c.err;
 }
 
@@ -290,13 +332,26 @@ static int sample_enqueue_all(dhw_handle* h, const SampleCall& sc, bool fork, hi
 }
 
 int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float* style, int B, int L, int Lt, int T, int mode,
-                const float* noise, uint64_t seed, int64_t first_sample, float* out, void* hip_stream, const int32_t* lens_host, bool ragged) {
+                const float* noise, uint64_t seed, int64_t first_sample, float* out, void* hip_stream, const int32_t* lens_host, bool ragged,
+                const CondArgs* cond) {
   {
     if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
     if (!text || !style || !out) return fail(h, DHW_ERR_ARG, "%s: null pointer", fn);
     if (T < 1 || (mode != 0 && mode != 1)) return fail(h, DHW_ERR_ARG, "%s: bad T/mode", fn);
     int rc = check_shapes(h, B, L, Lt);
     if (rc) return rc;
+    if (cond) {
+      // every check of the conditioned entry answers before the first HIP call (include/dhw.h, rules 5-7)
+      if (ragged && (rc = check_lens(h, fn, lens_host, B, L, false))) return rc;
+      if (h->persist) return fail(h, DHW_ERR_ARG, "%s: the persistent step kernel (DHW_PERSIST=1) does not support conditioned sampling", fn);
+      if (cond->t_start < 1 || cond->t_start > T) return fail(h, DHW_ERR_ARG, "%s: t_start = %d must lie in [1, T = %d]", fn, cond->t_start, T);
+      if (!cond->known && cond->keep) return fail(h, DHW_ERR_ARG, "%s: keep needs known (known is NULL)", fn);
+      if (!cond->known && cond->t_start != T) return fail(h, DHW_ERR_ARG, "%s: t_start = %d < T = %d needs known (known is NULL)", fn, cond->t_start, T);
+      if (cond->cond_noise && !(noise && cond->keep))
+        return fail(h, DHW_ERR_ARG, "%s: cond_noise is given but %s: it belongs to calls with external noise and a keep mask", fn, noise ? "keep is NULL" : "noise is NULL");
+      if (!cond->cond_noise && noise && cond->keep) return fail(h, DHW_ERR_ARG, "%s: cond_noise is NULL: a call with external noise and a keep mask needs it", fn);
+      if (!cond->known) cond = nullptr;   // nothing is conditioned: the plain call, bit for bit (same graphs)
+    }
     if ((rc = dhw_finalize(h))) return rc;
     HIPCK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
@@ -362,8 +417,37 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
       HIPCK(h, hipMemcpyAsync(h->d_noise_stage, noise, need * 4, hipMemcpyDeviceToDevice, st));
       nz = h->d_noise_stage;
     }
+    const float *kn = nullptr, *cz = nullptr;
+    const unsigned char* kp = nullptr;
+    if (cond) {
+      if (!h->d_known_stage) {   // (no cached graph reads these yet: only conditioned graphs do, and they are keyed apart)
+        const size_t cap = (size_t)h->dims.max_B * h->dims.max_L;
+        if ((rc = dev_alloc(h, (void**)&h->d_known_stage, cap * 3 * 4, false))) return rc;
+        if ((rc = dev_alloc(h, (void**)&h->d_keep_stage, cap, false))) return rc;
+      }
+      HIPCK(h, hipMemcpyAsync(h->d_known_stage, cond->known, rows * 3 * 4, hipMemcpyDeviceToDevice, st));
+      kn = h->d_known_stage;
+      if (cond->keep) {
+        HIPCK(h, hipMemcpyAsync(h->d_keep_stage, cond->keep, rows, hipMemcpyDeviceToDevice, st));
+        kp = h->d_keep_stage;
+      }
+      if (cond->cond_noise) {
+        const size_t need = (size_t)T * rows * 2;
+        if (need > h->cond_noise_stage_cap) {
+          HIPCK(h, hipDeviceSynchronize());
+          for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // they captured the old staging pointer
+          h->graphs.clear();
+          h->plans.clear();
+          if ((rc = dev_alloc(h, (void**)&h->d_cond_noise_stage, need * 4, false))) return rc;
+          h->cond_noise_stage_cap = need;
+        }
+        HIPCK(h, hipMemcpyAsync(h->d_cond_noise_stage, cond->cond_noise, need * 4, hipMemcpyDeviceToDevice, st));
+        cz = h->d_cond_noise_stage;
+      }
+    }
 
-    const SampleCall sc{B, L, Lt, T, mode, h->d_text_stage, h->d_style_stage, nz, h->d_out_stage, beta.data(), alpha.data(), lens};
+    const SampleCall sc{B, L, Lt, T, mode, h->d_text_stage, h->d_style_stage, nz, h->d_out_stage, beta.data(), alpha.data(), lens,
+                        kn, kp, cz, cond ? cond->t_start : T};
     const bool graph = h->use_graph && !h->prof && !h->teach_every;
     if (!graph) {
       // eager launches: sub-batches still fork onto the side streams (concurrent kernels of different sub-batches);
@@ -371,10 +455,13 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
       rc = sample_enqueue_all(h, sc, !h->prof, st);
     } else {
       const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)Lt, (uint64_t)T, (uint64_t)mode, (uint64_t)(nz != nullptr), (uint64_t)h->nstreams, (uint64_t)h->plane, (uint64_t)h->fuse_heads, (uint64_t)h->fuse_up, (uint64_t)h->chain, (uint64_t)h->persist,
-                                           (uint64_t)ragged};   // (ragged: the kernels read the lengths from h->d_lens at replay)
+                                           (uint64_t)ragged,   // (ragged: the kernels read the lengths from h->d_lens at replay)
+                                           // conditioned calls: known / keep / cond_noise are read from the staging buffers at replay,
+                                           // so one graph serves every mask; the iterations it holds depend on t_start
+                                           (uint64_t)(kn != nullptr), (uint64_t)sc.t_start, (uint64_t)(kp != nullptr), (uint64_t)(cz != nullptr)};
       auto it = h->graphs.find(key);
       if (it == h->graphs.end()) {
-        const StepPlan* d_plans = ragged ? nullptr : ensure_step_plans(h, key, sc);   // (before the capture: it uploads)
+        const StepPlan* d_plans = ragged || kn ? nullptr : ensure_step_plans(h, key, sc);   // (before the capture: it uploads)
         hipStream_t cs;
         HIPCK(h, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
         hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);

@@ -25,7 +25,8 @@ def get_alpha_set(T: int = 60) -> torch.Tensor:
 
 def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor, L: int | None = None, T: int = 60,
            diffusion_mode: str = "new", noise: torch.Tensor | None = None, seed: int = 0,
-           first_sample: int = 0, lengths=None) -> torch.Tensor:
+           first_sample: int = 0, lengths=None, known: torch.Tensor | None = None, keep: torch.Tensor | None = None,
+           t_start: int | None = None, cond_noise: torch.Tensor | None = None) -> torch.Tensor:
     """Reverse-sample a batch.  text int [B,Lt] (0 = pad), style_vector [B,S,1280] -> [B,L,3] = (dx, dy, pen).
 
     ``lengths`` (optional, B ints, multiples of 8 in [8, L]; ``L`` then defaults to max(lengths)): a ragged batch — prompts
@@ -36,6 +37,13 @@ def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor
     iteration (the reference draws them from torch's global RNG, inference.py:82 / utils/nn.py:86,111).
     Without it the library draws from a counter-based generator keyed by (seed, first_sample + b,
     iteration, position), so any sharding of a prompt batch over GPUs yields the same samples.
+
+    Conditioned sampling (include/dhw.h dhw_sample_cond).  ``known`` f32 [B,L,3] = (dx, dy, pen): strokes
+    that exist already.  ``keep`` bool / uint8 [B,L]: rows whose strokes stay exactly as ``known`` gives them (in-painting,
+    completion); the model writes the others around them.  ``t_start`` in [1, T] (default T): only the last ``t_start``
+    iterations run, from ``known`` noised to that level (restyling: the line keeps its layout, ``style_vector`` decides the
+    hand; see ``restyle``).  ``cond_noise`` f32 [T,B,L,2]: the draws that re-noise the kept rows, required exactly when both
+    ``noise`` and ``keep`` are given.  Rows of ``known`` that are neither kept nor (``t_start`` < T) seeded are never read.
     """
     if diffusion_mode not in ("new", "standard"):
         raise ValueError("diffusion_mode must be 'new' or 'standard'")
@@ -49,6 +57,9 @@ def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor
         L = stroke_length(Lt)
     if L % 8:
         raise ValueError("L must be a multiple of 8")
+    conditioned = known is not None or keep is not None or t_start is not None or cond_noise is not None
+    if conditioned:
+        t_start = _check_cond(B, L, T, noise, known, keep, t_start, cond_noise)
     if not hasattr(model, "_validated_text"):
         model._validated_text = []
     check_token_ids(text, model._validated_text)   # (once per prompt tensor: the check is a host read)
@@ -67,6 +78,16 @@ def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor
         out = torch.empty((B, L, 3), device=dev, dtype=torch.float32)
         stream = torch.cuda.current_stream(dev)
         mode = 0 if diffusion_mode == "new" else 1
+        if conditioned:
+            kn = known.to(dev, torch.float32).contiguous() if known is not None else None
+            kp = keep.to(dev, torch.uint8).contiguous() if keep is not None else None
+            cz = cond_noise.to(dev, torch.float32).contiguous() if cond_noise is not None else None
+            ptr = lambda x: x.data_ptr() if x is not None else None   # noqa: E731
+            _lib.check(_lib.lib().dhw_sample_cond(h, t.data_ptr(), sv.data_ptr(), B, L, Lt, (C.c_int32 * B)(*lens) if lens is not None else None,
+                                                  T, mode, ptr(nz), seed, first_sample, ptr(kn), ptr(kp), t_start, ptr(cz),
+                                                  out.data_ptr(), C.c_void_p(stream.cuda_stream)), h)
+            model._last_sample_inputs = (t, sv, nz, out, kn, kp, cz)
+            return out.to(ret_dev)
         if lens is None:
             _lib.check(_lib.lib().dhw_sample(h, t.data_ptr(), sv.data_ptr(), B, L, Lt, T, mode,
                                              nz.data_ptr() if nz is not None else None, seed, first_sample,
@@ -80,6 +101,57 @@ def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor
     return out.to(ret_dev)
 
 
+def _check_cond(B: int, L: int, T: int, noise, known, keep, t_start, cond_noise) -> int:
+    """The conditioning arguments of ``sample``, checked on the host before any device is touched; returns t_start."""
+    if t_start is None:
+        t_start = T
+    if isinstance(t_start, bool) or not isinstance(t_start, (int, np.integer)):
+        raise ValueError(f"t_start = {t_start!r} is not an integer")
+    t_start = int(t_start)
+    if t_start < 1 or t_start > T:
+        raise ValueError(f"t_start = {t_start} must lie in [1, T = {T}]")
+    if known is not None:
+        if not isinstance(known, torch.Tensor) or not known.dtype.is_floating_point:
+            raise ValueError("known must be a floating-point tensor [B,L,3]")
+        if tuple(known.shape) != (B, L, 3):
+            raise ValueError(f"known must be [B,L,3] = {(B, L, 3)}, got {tuple(known.shape)}")
+    if keep is not None:
+        if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("keep must be a bool or uint8 tensor [B,L]")
+        if tuple(keep.shape) != (B, L):
+            raise ValueError(f"keep must be [B,L] = {(B, L)}, got {tuple(keep.shape)}")
+        if known is None:
+            raise ValueError("keep needs known: the strokes of the kept rows")
+    if known is None and t_start != T:
+        raise ValueError(f"t_start = {t_start} < T = {T} needs known: the line to start from")
+    if cond_noise is not None:
+        if not isinstance(cond_noise, torch.Tensor) or not cond_noise.dtype.is_floating_point:
+            raise ValueError("cond_noise must be a floating-point tensor [T,B,L,2]")
+        if tuple(cond_noise.shape) != (T, B, L, 2):
+            raise ValueError(f"cond_noise must be [T,B,L,2] = {(T, B, L, 2)}, got {tuple(cond_noise.shape)}")
+        if noise is None or keep is None:
+            raise ValueError("cond_noise belongs to calls with external noise and a keep mask (" + ("noise" if noise is None else "keep") + " is missing)")
+    elif noise is not None and keep is not None:
+        raise ValueError("cond_noise is required when both noise and keep are given ([T,B,L,2])")
+    return t_start
+
+
+def restyle(strokes: torch.Tensor, text: torch.Tensor, style_vector: torch.Tensor, model: DiffusionModel, lengths=None,
+            strength: float = 0.5, keep: torch.Tensor | None = None, **sample_kwargs) -> torch.Tensor:
+    """Rewrite an existing line in another hand: ``strokes`` [B,L,3] (sampled earlier, or pen data) are noised
+    ``strength`` of the way up the schedule, ``t_start = clamp(round(strength * T), 1, T)``, and denoised under
+    ``style_vector``.  A small strength keeps the layout and changes details; 1 keeps nothing but the kept rows.  ``keep``
+    [B,L] pins rows exactly; the other keywords are ``sample``'s (T, diffusion_mode, seed, ...).  Returns [B,L,3]."""
+    if not 0.0 <= float(strength) <= 1.0:
+        raise ValueError(f"strength = {strength!r} must lie in [0, 1]")
+    if strokes.dim() != 3 or strokes.shape[2] != 3:
+        raise ValueError(f"strokes must be [B,L,3], got {tuple(strokes.shape)}")
+    T = int(sample_kwargs.pop("T", 60))
+    t_start = min(T, max(1, int(round(float(strength) * T))))
+    return sample(model, text, style_vector, L=int(strokes.shape[1]), T=T, lengths=lengths, known=strokes, keep=keep, t_start=t_start,
+                  **sample_kwargs)
+
+
 def infer(prompt: str, style_vector: torch.Tensor, model: DiffusionModel, diffusion_mode: str = "new", T: int = 60,
           seed: int = 0) -> np.ndarray:
     """Single-prompt convenience wrapper with the reference's front end: tokenise, L = 16 per token rounded up
@@ -90,18 +162,15 @@ def infer(prompt: str, style_vector: torch.Tensor, model: DiffusionModel, diffus
     return out[0].detach().cpu().numpy()
 
 
-def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diffusion_mode: str = "new", T: int = 60,
-                seed: int = 0, first_sample: int = 0) -> list:
-    """Many prompts in ONE ragged sampler call: prompt i is tokenised, gets its own ``L_i = stroke_length(n_i)`` and is padded
-    with token 0 to the longest prompt.  ``style_vector`` is [1,S,1280] (one writer for every prompt) or [B,S,1280].  Returns a
-    list of [L_i, 3] arrays; entry i equals ``sample(model, text_i, style_i, L=L_i, seed=seed, first_sample=first_sample + i)``."""
+def _encode_batch(who: str, prompts, style_vector):
+    """(text int64 [B,Lt] padded with 0, each prompt's own stroke length, style_vector expanded to [B,S,1280])."""
     prompts = list(prompts)
     if not prompts:
-        raise ValueError("infer_batch: no prompts")
+        raise ValueError(f"{who}: no prompts")
     tok = Tokenizer()
     ids = [tok.encode(p) for p in prompts]
     if any(len(i) == 0 for i in ids):
-        raise ValueError("infer_batch: every prompt needs at least one token")
+        raise ValueError(f"{who}: every prompt needs at least one token")
     B, Lt = len(ids), max(len(i) for i in ids)
     text = torch.zeros((B, Lt), dtype=torch.int64)
     for b, i in enumerate(ids):
@@ -114,6 +183,16 @@ def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diff
         sv = sv.expand(B, -1, -1)
     if sv.is_cuda:
         text = text.to(sv.device)
+    return text, lens, sv
+
+
+def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diffusion_mode: str = "new", T: int = 60,
+                seed: int = 0, first_sample: int = 0) -> list:
+    """Many prompts in ONE ragged sampler call: prompt i is tokenised, gets its own ``L_i = stroke_length(n_i)`` and is padded
+    with token 0 to the longest prompt.  ``style_vector`` is [1,S,1280] (one writer for every prompt) or [B,S,1280].  Returns a
+    list of [L_i, 3] arrays; entry i equals ``sample(model, text_i, style_i, L=L_i, seed=seed, first_sample=first_sample + i)``."""
+    text, lens, sv = _encode_batch("infer_batch", prompts, style_vector)
+    B = len(lens)
     out = sample(model, text, sv, L=max(lens), T=T, diffusion_mode=diffusion_mode, seed=seed, first_sample=first_sample, lengths=lens)
     out = out.detach().cpu().numpy()
     return [out[b, :lens[b]].copy() for b in range(B)]
@@ -264,4 +343,44 @@ def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint
     elif render:
         for i, s in enumerate(strokes):
             show_strokes(s, scale=1, name=f"{output}_{i}", show_output=False)
+    return strokes
+
+
+def pad_strokes(strokes_list) -> np.ndarray:
+    """A list of [L_i,3] stroke arrays as one f32 [B, max L_i, 3] array, 0 past each line's end: what ``infer.py
+    --save-strokes`` writes and ``--restyle`` reads back (line i's length follows from its prompt)."""
+    lens = [int(len(s)) for s in strokes_list]
+    batch = np.zeros((len(lens), max(lens), 3), np.float32)
+    for b, s_ in enumerate(strokes_list):
+        batch[b, :lens[b]] = np.asarray(s_, np.float32)
+    return batch
+
+
+def restyle_file(prompts, strokes_path, source, config_path: str | None = None, checkpoint_path: str | None = None,
+                 experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *, strength: float = 0.5,
+                 precision: str = "bf16", seed: int = 0, render: bool = True, style_weights: str | None = None,
+                 renderer: str = "matplotlib") -> list:
+    """``infer.py --restyle``: the lines of ``prompts`` as an earlier run wrote them (``strokes_path``: the .npy of ``infer.py
+    --save-strokes``, [B, >= max L_i, 3]) rewritten in the hand of ``source`` by one ``restyle`` call; ``./<output>_<i>.png``
+    per line.  Returns the list of [L_i, 3] strokes."""
+    from .checkpoint import load_model
+    from .vis import render_lines_png, show_strokes
+
+    _check_renderer(renderer)
+    prompts = list(prompts)
+    config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
+    style = load_style(source, style_weights)
+    text, lens, sv = _encode_batch("restyle_file", prompts, style)
+    old = np.load(str(strokes_path), allow_pickle=False)
+    if old.ndim != 3 or old.shape[0] != len(lens) or old.shape[1] < max(lens) or old.shape[2] != 3:
+        raise ValueError(f"{strokes_path}: expected strokes [{len(lens)}, >= {max(lens)}, 3] for these prompts, got {tuple(old.shape)}")
+    old = torch.from_numpy(np.ascontiguousarray(old[:, :max(lens)], dtype=np.float32))
+    model = load_model(config_path, checkpoint_path, precision=precision, max_B=len(lens), style_rows=style.shape[1])
+    out = restyle(old, text, sv, model, lengths=lens, strength=strength, diffusion_mode=diffusion_mode, seed=seed).detach().cpu().numpy()
+    strokes = [out[b, :lens[b]].copy() for b in range(len(lens))]
+    if render and renderer == "gpu":
+        render_lines_png(strokes, [f"{output}_{i}" for i in range(len(strokes))])
+    elif render:
+        for i, s_ in enumerate(strokes):
+            show_strokes(s_, scale=1, name=f"{output}_{i}", show_output=False)
     return strokes

@@ -122,6 +122,42 @@ int dhw_sample_ragged(dhw_handle*, const int64_t* text, const float* style, int 
                       const int32_t* lens, int T, int mode, const float* noise, uint64_t seed,
                       int64_t first_sample, float* out, void* hip_stream);
 
+/* Conditioned sampling (replacement conditioning of the reverse process): keep the strokes of chosen rows exactly as given
+ * (in-painting, completion), start from an existing line noised part of the way up the schedule (restyling), or both.  The
+ * arguments are dhw_sample_ragged's, with lens allowed to be NULL (every row has L strokes), plus
+ *    known       device f32 [B,L,3] = (dx, dy, pen), or NULL
+ *    keep        device uint8 [B,L], nonzero = keep this row, or NULL (nothing kept)
+ *    t_start     in [1, T]
+ *    cond_noise  device f32 [T,B,L,2], or NULL.
+ * Symbols: beta[i], abar[i] as dhw_schedule gives them; loop iteration k = 0..T-1 handles schedule index i = T-1-k, as in
+ * dhw_sample; a_next(i) = abar[i-1] for i > 1, else 1 (the reference's quirk, inference.py:87), used for BOTH modes here.
+ * A row (b, p) with p < lens[b] (p < L without lens) is KEPT iff keep && keep[b,p], and SEEDED iff it is kept or t_start < T.
+ *    1. Iterations run.  Only k = T - t_start .. T-1 run.  Iteration numbers, noise indexing (noise[1+k]) and generator
+ *       keys are those of the full call, so t_start = T runs everything.
+ *    2. Start.  z = noise[0], or the device draw with iter = -1, exactly as in dhw_sample.  With i0 = t_start - 1, seeded
+ *       rows get x = fadd(fmul(sqrtf(abar[i0]), known_xy), fmul(sqrtf(1 - abar[i0]), z)); the others x = z.  Coefficients
+ *       are computed on the host in fp32; the device multiplies and adds with round-to-nearest and no contraction.
+ *    3. After the update of iteration k (whichever kernel performs it) every kept row is overwritten with
+ *       x = fadd(fmul(sqrtf(a_next), known_xy), fmul(sqrtf(1 - a_next), zc)), zc = cond_noise[k,b,p] when external noise is
+ *       used, otherwise the generator's draw for (seed, first_sample + b, p, iter = 2^30 + k): an iteration range disjoint
+ *       from everything the sampler draws, so the conditioning stream is independent and as sharding-invariant.  The last
+ *       two iterations have a_next = 1: kept rows equal known_xy from there on.
+ *    4. Output.  Kept rows of out are `known` bit for bit (dx, dy and pen).  Other valid rows are x_0 and the pen of the
+ *       last denoiser call, as in dhw_sample.  Rows past lens[b] are 0.
+ *    5. Rows that are not read.  Rows of `known` that are neither seeded nor kept, and all rows past lens[b], are never
+ *       read: the kernels branch rather than blend, so NaNs there change nothing.  known == NULL is legal only with
+ *       keep == NULL and t_start == T; that call is bit-identical to dhw_sample / dhw_sample_ragged.
+ *    6. Noise arguments.  cond_noise must be given iff noise is given and keep is non-NULL; otherwise DHW_ERR_ARG naming
+ *       the argument.
+ *    7. Persistent step.  A handle created with DHW_PERSIST=1 refuses the call with DHW_ERR_ARG naming the switch.
+ * Every argument check runs before the first HIP call.  known, keep and cond_noise are copied to library-owned buffers on
+ * hip_stream and read by the kernels at run time: one captured graph serves every mask and every `known` of a
+ * (shape, t_start, keep given or not, cond_noise given or not). */
+int dhw_sample_cond(dhw_handle*, const int64_t* text, const float* style, int B, int L, int Lt,
+                    const int32_t* lens, int T, int mode, const float* noise, uint64_t seed,
+                    int64_t first_sample, const float* known, const uint8_t* keep, int t_start,
+                    const float* cond_noise, float* out, void* hip_stream);
+
 /* Stroke rasteriser: sampled strokes -> grey-level line images in the layout dhw_style_forward consumes (ink
  * left-aligned, white to the right).  No handle: errors are read through dhw_last_error(NULL).  The call allocates
  * nothing, synchronises nothing and can be captured into a graph.  All argument checks run before the first HIP call

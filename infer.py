@@ -9,7 +9,13 @@
 
 Many lines of one writer in one batched sampler call (each line at its own stroke length), written to <output>_<i>.png:
 
-    python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --output page"""
+    python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --output page
+
+The same lines in another writer's hand (restyling: the strokes an earlier run saved are noised `--strength` of the way up the
+schedule and denoised under the new style, so the layout stays and the hand changes):
+
+    python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --save-strokes lines.npy
+    python infer.py --prompts-file lines.txt other.npy --experiment-path data/best_exp --restyle lines.npy --strength 0.5"""
 import argparse
 
 import dhg_amd
@@ -30,7 +36,19 @@ def main(argv=None):
     ap.add_argument("--style-weights", help="torchvision mobilenet_v2 state_dict (.pth) for the StyleExtractor")
     ap.add_argument("--renderer", default="matplotlib", choices=list(dhg_amd.inference.RENDERERS),
                     help="how the PNGs are drawn: the reference's matplotlib figure, or the 96-row grey line image rasterised on the GPU")
+    ap.add_argument("--save-strokes", metavar="NPY", help="also write the sampled strokes, [B, max L, 3] padded with 0, to this .npy")
+    ap.add_argument("--restyle", metavar="NPY", help="strokes of these prompts from an earlier run (--save-strokes): rewrite them in the hand of `source`")
+    ap.add_argument("--strength", type=float, default=0.5, help="--restyle: share of the schedule the old strokes are noised up (0..1, default 0.5)")
     a = ap.parse_args(argv)
+    if not 0.0 <= a.strength <= 1.0:
+        ap.error("--strength must lie in [0, 1]")
+
+    def save(strokes_list):
+        if a.save_strokes:
+            import numpy as np
+            np.save(a.save_strokes, dhg_amd.pad_strokes(strokes_list))
+            print(f"strokes {len(strokes_list)} x [L,3] -> {a.save_strokes}")
+
     if a.prompts_file:
         if a.prompt is not None and a.source is not None:
             ap.error("with --prompts-file pass only the source")
@@ -41,15 +59,29 @@ def main(argv=None):
             prompts = [ln.rstrip("\r\n") for ln in f if ln.strip()]
         if not prompts:
             ap.error(f"{a.prompts_file} holds no prompt")
-        out = dhg_amd.infer_file_batch(prompts, source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
-                                       a.diffusion_mode, precision=a.precision, seed=a.seed, style_weights=a.style_weights, renderer=a.renderer)
+        if a.restyle:
+            out = dhg_amd.restyle_file(prompts, a.restyle, source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
+                                       a.diffusion_mode, strength=a.strength, precision=a.precision, seed=a.seed,
+                                       style_weights=a.style_weights, renderer=a.renderer)
+        else:
+            out = dhg_amd.infer_file_batch(prompts, source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
+                                           a.diffusion_mode, precision=a.precision, seed=a.seed, style_weights=a.style_weights, renderer=a.renderer)
+        save(out)
         for i, s in enumerate(out):
             print(f"{s.shape[0]} stroke points -> ./{a.output}_{i}.png")
         return
     if a.prompt is None or a.source is None:
         ap.error("the following arguments are required: prompt, source")
+    if a.restyle:
+        (strokes,) = dhg_amd.restyle_file([a.prompt], a.restyle, a.source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
+                                          a.diffusion_mode, strength=a.strength, precision=a.precision, seed=a.seed,
+                                          style_weights=a.style_weights, renderer=a.renderer)
+        save([strokes])
+        print(f"{strokes.shape[0]} stroke points -> ./{a.output}_0.png")
+        return
     strokes = dhg_amd.infer_file(a.prompt, a.source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
                                  a.diffusion_mode, precision=a.precision, seed=a.seed, style_weights=a.style_weights, renderer=a.renderer)
+    save([strokes])
     print(f"{strokes.shape[0]} stroke points -> ./{a.output}.png")
 
 
