@@ -159,6 +159,9 @@ struct dhw_handle {
   unsigned char* d_keep_stage = nullptr;
   float* d_cond_noise_stage = nullptr;
   size_t cond_noise_stage_cap = 0;
+  // scoring calls (dhw_score): x_t, z, eps_hat [max_B*max_L, 2], pen_hat [max_B*max_L] and sigma [max_B], allocated once, at
+  // the first such call, and never moved.  No graph reads them: a score call launches eagerly and leaves the cached graphs alone.
+  float *d_score_xt = nullptr, *d_score_z = nullptr, *d_score_eps = nullptr, *d_score_pen = nullptr, *d_score_sigma = nullptr;
   uint64_t* d_seed = nullptr;   // [seed, first_sample] read by the noise kernels
   // ragged calls (dhw_forward_ragged / dhw_sample_ragged): the per-sample lengths, copied on the caller's stream from a pinned host
   // buffer the handle owns.  The kernels read them at run time, so one captured graph serves every set of lengths of a shape.
@@ -228,6 +231,11 @@ void destroy_impl(dhw_handle* h);
 
 // ---------------------------------------------------------------- sampler/sample.cpp
 void schedule_host(int T, std::vector<float>& beta, std::vector<float>& alpha);
+int check_shapes(dhw_handle* h, int B, int L, int Lt);
+int check_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling);
+int stage_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling, hipStream_t st);
+int forward_enqueue(dhw_handle* h, const float* strokes, const int64_t* text, const float* sigma, const float* style, int B, int L, int Lt,
+                    float* eps_out, float* pen_out, hipStream_t st, const int* lens);
 int forward_impl(dhw_handle* h, const char* fn, const float* strokes, const int64_t* text, const float* sigma, const float* style,
                  int B, int L, int Lt, float* eps_out, float* pen_out, void* hip_stream, const int32_t* lens_host, bool ragged);
 int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float* style, int B, int L, int Lt, int T, int mode,

@@ -8,7 +8,7 @@
 #include "../cond/cond.h"
 #include "denoiser.h"
 
-static int check_shapes(dhw_handle* h, int B, int L, int Lt) {
+int check_shapes(dhw_handle* h, int B, int L, int Lt) {
   const dhw_dims& d = h->dims;
   if (B < 1 || B > d.max_B || L < 8 || L > d.max_L || L % 8 || Lt < 1 || Lt > d.max_Lt)
     return fail(h, DHW_ERR_ARG, "shape out of range: B=%d (max %d) L=%d (max %d, multiple of 8) Lt=%d (max %d)", B, d.max_B, L, d.max_L, Lt, d.max_Lt);
@@ -48,7 +48,7 @@ void schedule_host(int T, std::vector<float>& beta, std::vector<float>& alpha) {
 // Ragged calls: check the caller's lengths (host pointer, B entries), refuse the diagnostic configurations that have no per-sample
 // ends, and copy the lengths into h->d_lens on the caller's stream.  The copy's source is the handle's pinned buffer, rewritten only
 // once the previous call's copy has read it (an event on that copy, not a device-wide synchronize).
-static int check_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling) {
+int check_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling) {
   if (!lens) return fail(h, DHW_ERR_ARG, "%s: lens is NULL (B = %d entries expected)", fn, B);
   for (int b = 0; b < B; ++b)
     if (lens[b] < 8 || lens[b] > L || lens[b] % 8)
@@ -57,7 +57,7 @@ static int check_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B,
   return 0;
 }
 
-static int stage_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling, hipStream_t st) {
+int stage_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling, hipStream_t st) {
   if (int rc = check_lens(h, fn, lens, B, L, sampling)) return rc;
   HIPCK(h, hipEventSynchronize(h->lens_ev));
   memcpy(h->h_lens_pin, lens, (size_t)B * 4);
@@ -68,35 +68,40 @@ static int stage_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B,
 
 int forward_impl(dhw_handle* h, const char* fn, const float* strokes, const int64_t* text, const float* sigma, const float* style,
                  int B, int L, int Lt, float* eps_out, float* pen_out, void* hip_stream, const int32_t* lens_host, bool ragged) {
-  {
-    if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
-    if (!strokes || !text || !sigma || !style || !eps_out || !pen_out) return fail(h, DHW_ERR_ARG, "%s: null pointer", fn);
-    int rc = check_shapes(h, B, L, Lt);
-    if (rc) return rc;
-    if ((rc = dhw_finalize(h))) return rc;
-    HIPCK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (ragged && (rc = stage_lens(h, fn, lens_host, B, L, false, st))) return rc;
-    Ctx c{h, &h->ws[0], st, B, L, Lt, h->dims.S * 5, h->d_film, 2L * h->film_tot};
-    c.lens = ragged ? h->d_lens : nullptr;
-    taps_clear(h);
-    RUN_SMALL(c, "sigma_ffn", launch_sigma_ffn(sigma, B, h->sg_w1, h->sg_b1, h->sg_w2, h->sg_b2, h->d_sig32, st));
-    RUN_SMALL(c, "film_table", launch_film(h->d_sig32, B, h->d_film_w, h->d_film_b, 2 * h->film_tot, h->d_film, st));
-    tap(c, TAP_SIGMA_FFN, h->d_sig32, 1, SIG, true);
-    text_style_static(c, text, style);
-    text_style_dynamic(c);
-    stroke_path(c, strokes, text);
-    HeadsParams hp{};
-    hp.eps = eps_out;
-    hp.pen = pen_out;
-    launch_heads_for(c, hp);
-    if (c.lens) {   // ragged: eps / pen past each sample's end are 0
-      RUN_SMALL(c, "zero_tail", launch_zero_tail(eps_out, B, L, 2, c.lens, st));
-      RUN_SMALL(c, "zero_tail", launch_zero_tail(pen_out, B, L, 1, c.lens, st));
-    }
-    h->last_B = B; h->last_L = L; h->last_Lt = Lt;
-    return c.err;
+  if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
+  if (!strokes || !text || !sigma || !style || !eps_out || !pen_out) return fail(h, DHW_ERR_ARG, "%s: null pointer", fn);
+  int rc = check_shapes(h, B, L, Lt);
+  if (rc) return rc;
+  if ((rc = dhw_finalize(h))) return rc;
+  HIPCK(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (ragged && (rc = stage_lens(h, fn, lens_host, B, L, false, st))) return rc;
+  return forward_enqueue(h, strokes, text, sigma, style, B, L, Lt, eps_out, pen_out, st, ragged ? h->d_lens : nullptr);
+}
+
+// The launches of one denoiser call on checked arguments (dhw_forward / dhw_forward_ragged, and every level of dhw_score);
+// lens = the staged device lengths of a ragged call, or null.
+int forward_enqueue(dhw_handle* h, const float* strokes, const int64_t* text, const float* sigma, const float* style, int B, int L, int Lt,
+                    float* eps_out, float* pen_out, hipStream_t st, const int* lens) {
+  Ctx c{h, &h->ws[0], st, B, L, Lt, h->dims.S * 5, h->d_film, 2L * h->film_tot};
+  c.lens = lens;
+  taps_clear(h);
+  RUN_SMALL(c, "sigma_ffn", launch_sigma_ffn(sigma, B, h->sg_w1, h->sg_b1, h->sg_w2, h->sg_b2, h->d_sig32, st));
+  RUN_SMALL(c, "film_table", launch_film(h->d_sig32, B, h->d_film_w, h->d_film_b, 2 * h->film_tot, h->d_film, st));
+  tap(c, TAP_SIGMA_FFN, h->d_sig32, 1, SIG, true);
+  text_style_static(c, text, style);
+  text_style_dynamic(c);
+  stroke_path(c, strokes, text);
+  HeadsParams hp{};
+  hp.eps = eps_out;
+  hp.pen = pen_out;
+  launch_heads_for(c, hp);
+  if (c.lens) {   // ragged: eps / pen past each sample's end are 0
+    RUN_SMALL(c, "zero_tail", launch_zero_tail(eps_out, B, L, 2, c.lens, st));
+    RUN_SMALL(c, "zero_tail", launch_zero_tail(pen_out, B, L, 1, c.lens, st));
   }
+  h->last_B = B; h->last_L = L; h->last_Lt = Lt;
+  return c.err;
 }
 
 // sampler steps whose text side is precomputed together (bounds the plane's memory for long schedules)

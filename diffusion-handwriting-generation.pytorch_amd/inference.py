@@ -162,6 +162,87 @@ def infer(prompt: str, style_vector: torch.Tensor, model: DiffusionModel, diffus
     return out[0].detach().cpu().numpy()
 
 
+def default_levels(T: int = 60) -> list:
+    """The noise levels ``score`` evaluates when none are given: four schedule indices spread over the schedule,
+    ``(2j+1) * T // 8`` (7, 22, 37, 52 at T = 60; duplicates of a short schedule dropped)."""
+    return sorted({(2 * j + 1) * T // 8 for j in range(4)})
+
+
+def _check_levels(levels, T: int) -> list:
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 1:
+        raise ValueError(f"T = {T!r} must be a positive integer")
+    if levels is None:
+        return default_levels(T)
+    if isinstance(levels, torch.Tensor):
+        levels = levels.detach().cpu().tolist()
+    try:
+        seq = list(levels)
+    except TypeError:
+        raise ValueError(f"levels must be a sequence of schedule indices, got {type(levels).__name__}") from None
+    if not seq:
+        raise ValueError("levels is empty: at least one schedule index is needed")
+    if len(seq) > T:
+        raise ValueError(f"levels has {len(seq)} entries, more than T = {T}")
+    for k, v in enumerate(seq):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"levels[{k}] = {v!r} is not an integer")
+        if v < 0 or v >= T:
+            raise ValueError(f"levels[{k}] = {v} must lie in [0, T = {T})")
+    return [int(v) for v in seq]
+
+
+def score(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, style_vector: torch.Tensor, lengths=None, levels=None,
+          T: int = 60, noise: torch.Tensor | None = None, seed: int = 0, first_sample: int = 0, pen_round: bool = False) -> torch.Tensor:
+    """How well existing strokes fit a text and a hand under the model: the denoising objective (the reference's training
+    loss, loss.py:29-37) at chosen noise levels (include/dhw.h dhw_score).  Lower is better.
+
+    strokes f32 [B,L,3] = (dx, dy, pen), text int [B,Lt], style_vector [B,S,1280] -> [B,K,2]: per sample and level the mean
+    squared error of the predicted noise and the abar-weighted cross-entropy of the predicted pen lifts, both over the
+    sample's own ``lengths[b]`` rows (rows past them are never read).  ``levels``: K schedule indices in [0, T), default
+    ``default_levels(T)``.  ``noise`` f32 [K,B,L,2]: the perturbing draws; without it the generator draws them keyed by
+    (seed, first_sample + b, position, level), so a level's score depends neither on the other levels nor on sharding.
+    ``pen_round``: score against ``torch.round(pen)`` (half to even, the renderer's reading of a sampled pen value)."""
+    if not isinstance(strokes, torch.Tensor) or not strokes.dtype.is_floating_point:
+        raise ValueError("strokes must be a floating-point tensor [B,L,3]")
+    if strokes.dim() != 3 or strokes.shape[2] != 3:
+        raise ValueError(f"strokes must be [B,L,3], got {tuple(strokes.shape)}")
+    B, L, _ = strokes.shape
+    if text.dim() != 2 or text.shape[0] != B:
+        raise ValueError(f"text must be [B = {B}, Lt], got {tuple(text.shape)}")
+    if L < 8 or L % 8:
+        raise ValueError(f"strokes: L = {L} must be a multiple of 8, at least 8")
+    lens = check_lengths(lengths, B, L) if lengths is not None else None
+    lv = _check_levels(levels, T)
+    K, Lt = len(lv), text.shape[1]
+    if noise is not None:
+        if not isinstance(noise, torch.Tensor) or not noise.dtype.is_floating_point:
+            raise ValueError("noise must be a floating-point tensor [K,B,L,2]")
+        if tuple(noise.shape) != (K, B, L, 2):
+            raise ValueError(f"noise must be [K,B,L,2] = {(K, B, L, 2)}, got {tuple(noise.shape)}")
+    if not hasattr(model, "_validated_text"):
+        model._validated_text = []
+    check_token_ids(text, model._validated_text)
+    dev = model._device(strokes, text, style_vector)
+    h = model._ensure_handle(dev, B, L, Lt, style_vector.shape[1])
+    ret_dev = strokes.device
+    with torch.cuda.device(dev):
+        s = strokes.to(dev, torch.float32)
+        if pen_round:
+            s = torch.cat((s[..., :2], torch.round(s[..., 2:])), dim=2)
+        s = s.contiguous()
+        t = text.to(dev, torch.int64).contiguous()
+        sv = style_vector.to(dev, torch.float32).contiguous()
+        nz = noise.to(dev, torch.float32).contiguous() if noise is not None else None
+        out = torch.empty((K, B, 2), device=dev, dtype=torch.float32)
+        stream = torch.cuda.current_stream(dev)
+        _lib.check(_lib.lib().dhw_score(h, s.data_ptr(), t.data_ptr(), sv.data_ptr(), B, L, Lt, (C.c_int32 * B)(*lens) if lens is not None else None,
+                                        T, (C.c_int32 * K)(*lv), K, nz.data_ptr() if nz is not None else None, seed, first_sample,
+                                        out.data_ptr(), C.c_void_p(stream.cuda_stream)), h)
+        # the launches read the inputs in place: pin them to the model so they outlive the stream's work
+        model._last_score_inputs = (s, t, sv, nz, out)
+    return out.transpose(0, 1).to(ret_dev)
+
+
 def _encode_batch(who: str, prompts, style_vector):
     """(text int64 [B,Lt] padded with 0, each prompt's own stroke length, style_vector expanded to [B,S,1280])."""
     prompts = list(prompts)
@@ -187,15 +268,48 @@ def _encode_batch(who: str, prompts, style_vector):
 
 
 def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diffusion_mode: str = "new", T: int = 60,
-                seed: int = 0, first_sample: int = 0) -> list:
+                seed: int = 0, first_sample: int = 0, candidates: int = 1, levels=None) -> list:
     """Many prompts in ONE ragged sampler call: prompt i is tokenised, gets its own ``L_i = stroke_length(n_i)`` and is padded
     with token 0 to the longest prompt.  ``style_vector`` is [1,S,1280] (one writer for every prompt) or [B,S,1280].  Returns a
-    list of [L_i, 3] arrays; entry i equals ``sample(model, text_i, style_i, L=L_i, seed=seed, first_sample=first_sample + i)``."""
+    list of [L_i, 3] arrays; entry i equals ``sample(model, text_i, style_i, L=L_i, seed=seed, first_sample=first_sample + i)``.
+
+    ``candidates = N > 1`` (best of N): every prompt is sampled N times — candidate j of prompt b is the sample with generator
+    index ``first_sample + j*B + b``, so candidate 0 is the line above — and scored by ``score(..., pen_round=True)`` at
+    ``levels``; the line returned for a prompt is the candidate with the lowest mean over levels of score term + pen term
+    (ties: the lower j)."""
+    candidates = _check_candidates(candidates)
     text, lens, sv = _encode_batch("infer_batch", prompts, style_vector)
     B = len(lens)
-    out = sample(model, text, sv, L=max(lens), T=T, diffusion_mode=diffusion_mode, seed=seed, first_sample=first_sample, lengths=lens)
-    out = out.detach().cpu().numpy()
-    return [out[b, :lens[b]].copy() for b in range(B)]
+    if candidates == 1:
+        out = sample(model, text, sv, L=max(lens), T=T, diffusion_mode=diffusion_mode, seed=seed, first_sample=first_sample, lengths=lens)
+        out = out.detach().cpu().numpy()
+        return [out[b, :lens[b]].copy() for b in range(B)]
+    lv = _check_levels(levels, T)
+    # whole candidate rounds per call, as many as the model's batch capacity holds: row j*B + b of the stacked batch is
+    # candidate j of prompt b.  Every row is its alone run bit for bit, so the split changes nothing.
+    per = max(1, max(B, int(model._cap["max_B"])) // B)
+    best, best_total = [None] * B, [float("inf")] * B
+    for j0 in range(0, candidates, per):
+        r = min(per, candidates - j0)
+        tx, st, ln = text.repeat(r, 1), sv.repeat(r, 1, 1), lens * r
+        first = first_sample + j0 * B
+        out = sample(model, tx, st, L=max(lens), T=T, diffusion_mode=diffusion_mode, seed=seed, first_sample=first, lengths=ln)
+        sc = score(model, out, tx, st, lengths=ln, levels=lv, T=T, seed=seed, first_sample=first, pen_round=True)
+        total = sc.detach().cpu().double().sum(dim=2).mean(dim=1).tolist()   # (on the host in fp64: the ranking is the same everywhere)
+        out = out.detach().cpu().numpy()
+        for j in range(r):
+            for b in range(B):
+                if total[j * B + b] < best_total[b]:
+                    best_total[b], best[b] = total[j * B + b], out[j * B + b, :lens[b]].copy()
+    if any(x is None for x in best):
+        raise RuntimeError("infer_batch: a prompt has no finite candidate score")
+    return best
+
+
+def _check_candidates(candidates) -> int:
+    if isinstance(candidates, bool) or not isinstance(candidates, (int, np.integer)) or candidates < 1:
+        raise ValueError(f"candidates = {candidates!r} must be an integer >= 1")
+    return int(candidates)
 
 
 def remove_whitespace(img: np.ndarray, thresh: float) -> np.ndarray:
@@ -280,15 +394,17 @@ def _check_renderer(renderer: str) -> None:
 
 def infer_file(prompt: str, source, config_path: str | None = None, checkpoint_path: str | None = None,
                experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *, precision: str = "bf16",
-               seed: int = 0, render: bool = True, style_weights: str | None = None, renderer: str = "matplotlib") -> np.ndarray:
+               seed: int = 0, render: bool = True, style_weights: str | None = None, renderer: str = "matplotlib",
+               candidates: int = 1) -> np.ndarray:
     """The reference's command-line entry (inference.py:19-27) around this build's sampler: resolve config / checkpoint
     (directly or inside ``experiment_path``), load the model, sample one prompt, write ``./<output>.png`` (``renderer``:
     "matplotlib" = the reference's figure, "gpu" = the 96-row grey line image of ``render_strokes``).
-    Returns the [L,3] strokes."""
+    ``candidates = N > 1``: the best of N samples by ``score`` (``infer_batch``).  Returns the [L,3] strokes."""
     from .checkpoint import find_checkpoint, load_model
     from .vis import render_lines_png, show_strokes
 
     _check_renderer(renderer)
+    candidates = _check_candidates(candidates)
 
     if experiment_path:
         from pathlib import Path
@@ -300,13 +416,21 @@ def infer_file(prompt: str, source, config_path: str | None = None, checkpoint_p
     if not config_path or not checkpoint_path:
         raise ValueError("Both config_path and checkpoint_path must be provided, either directly or via experiment_path.")
     style = load_style(source, style_weights)
-    model = load_model(config_path, checkpoint_path, precision=precision, max_B=1, style_rows=style.shape[1])
-    strokes = infer(prompt, style, model, diffusion_mode=diffusion_mode, seed=seed)
+    model = load_model(config_path, checkpoint_path, precision=precision, max_B=_rounds_capacity(1, candidates), style_rows=style.shape[1])
+    if candidates > 1:
+        (strokes,) = infer_batch([prompt], style, model, diffusion_mode=diffusion_mode, seed=seed, candidates=candidates)
+    else:
+        strokes = infer(prompt, style, model, diffusion_mode=diffusion_mode, seed=seed)
     if render and renderer == "gpu":
         render_lines_png([strokes], [output])
     elif render:
         show_strokes(strokes, scale=1, name=output, show_output=False)
     return strokes
+
+
+def _rounds_capacity(B: int, candidates: int, limit: int = 64) -> int:
+    """Batch capacity for best-of-N over B prompts: as many whole candidate rounds as fit under ``limit`` rows, at least one."""
+    return B * max(1, min(candidates, limit // B))
 
 
 def _resolve_experiment(config_path, checkpoint_path, experiment_path):
@@ -326,18 +450,21 @@ def _resolve_experiment(config_path, checkpoint_path, experiment_path):
 def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint_path: str | None = None,
                      experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
                      precision: str = "bf16", seed: int = 0, render: bool = True, style_weights: str | None = None,
-                     renderer: str = "matplotlib") -> list:
+                     renderer: str = "matplotlib", candidates: int = 1) -> list:
     """``infer_file`` for many prompts of one writer: one ragged sampler call (``infer_batch``), ``./<output>_<i>.png`` per
-    prompt (``renderer="gpu"``: every line rasterised in one ``render_strokes`` call).  Returns the list of [L_i, 3] strokes."""
+    prompt (``renderer="gpu"``: every line rasterised in one ``render_strokes`` call).  ``candidates = N > 1``: every line is
+    the best of N samples by ``score``.  Returns the list of [L_i, 3] strokes."""
     from .checkpoint import load_model
     from .vis import render_lines_png, show_strokes
 
     _check_renderer(renderer)
+    candidates = _check_candidates(candidates)
     prompts = list(prompts)
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
-    model = load_model(config_path, checkpoint_path, precision=precision, max_B=max(1, len(prompts)), style_rows=style.shape[1])
-    strokes = infer_batch(prompts, style, model, diffusion_mode=diffusion_mode, seed=seed)
+    model = load_model(config_path, checkpoint_path, precision=precision, max_B=_rounds_capacity(max(1, len(prompts)), candidates),
+                       style_rows=style.shape[1])
+    strokes = infer_batch(prompts, style, model, diffusion_mode=diffusion_mode, seed=seed, candidates=candidates)
     if render and renderer == "gpu":
         render_lines_png(strokes, [f"{output}_{i}" for i in range(len(strokes))])
     elif render:
@@ -356,6 +483,31 @@ def pad_strokes(strokes_list) -> np.ndarray:
     return batch
 
 
+def _load_strokes(strokes_path, lens) -> torch.Tensor:
+    """The .npy of ``infer.py --save-strokes`` for prompts of stroke lengths ``lens``, cut to [B, max(lens), 3]."""
+    old = np.load(str(strokes_path), allow_pickle=False)
+    if old.ndim != 3 or old.shape[0] != len(lens) or old.shape[1] < max(lens) or old.shape[2] != 3:
+        raise ValueError(f"{strokes_path}: expected strokes [{len(lens)}, >= {max(lens)}, 3] for these prompts, got {tuple(old.shape)}")
+    return torch.from_numpy(np.ascontiguousarray(old[:, :max(lens)], dtype=np.float32))
+
+
+def score_file(prompts, strokes_path, source, config_path: str | None = None, checkpoint_path: str | None = None,
+               experiment_path: str | None = None, *, precision: str = "bf16", seed: int = 0, style_weights: str | None = None) -> list:
+    """``infer.py --score``: the lines of ``prompts`` as an earlier run wrote them (``strokes_path``: the .npy of ``infer.py
+    --save-strokes``) scored against their text and the hand of ``source`` by one ``score(..., pen_round=True)`` call at the
+    default levels.  Returns one ``(L_i, score term, pen term, total)`` per line, each averaged over the levels."""
+    from .checkpoint import load_model
+
+    prompts = list(prompts)
+    config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
+    style = load_style(source, style_weights)
+    text, lens, sv = _encode_batch("score_file", prompts, style)
+    old = _load_strokes(strokes_path, lens)
+    model = load_model(config_path, checkpoint_path, precision=precision, max_B=len(lens), style_rows=style.shape[1])
+    sc = score(model, old, text, sv, lengths=lens, seed=seed, pen_round=True).mean(dim=1).detach().cpu().tolist()
+    return [(lens[b], sc[b][0], sc[b][1], sc[b][0] + sc[b][1]) for b in range(len(lens))]
+
+
 def restyle_file(prompts, strokes_path, source, config_path: str | None = None, checkpoint_path: str | None = None,
                  experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *, strength: float = 0.5,
                  precision: str = "bf16", seed: int = 0, render: bool = True, style_weights: str | None = None,
@@ -371,10 +523,7 @@ def restyle_file(prompts, strokes_path, source, config_path: str | None = None, 
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
     text, lens, sv = _encode_batch("restyle_file", prompts, style)
-    old = np.load(str(strokes_path), allow_pickle=False)
-    if old.ndim != 3 or old.shape[0] != len(lens) or old.shape[1] < max(lens) or old.shape[2] != 3:
-        raise ValueError(f"{strokes_path}: expected strokes [{len(lens)}, >= {max(lens)}, 3] for these prompts, got {tuple(old.shape)}")
-    old = torch.from_numpy(np.ascontiguousarray(old[:, :max(lens)], dtype=np.float32))
+    old = _load_strokes(strokes_path, lens)
     model = load_model(config_path, checkpoint_path, precision=precision, max_B=len(lens), style_rows=style.shape[1])
     out = restyle(old, text, sv, model, lengths=lens, strength=strength, diffusion_mode=diffusion_mode, seed=seed).detach().cpu().numpy()
     strokes = [out[b, :lens[b]].copy() for b in range(len(lens))]

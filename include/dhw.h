@@ -158,6 +158,40 @@ int dhw_sample_cond(dhw_handle*, const int64_t* text, const float* style, int B,
                     int64_t first_sample, const float* known, const uint8_t* keep, int t_start,
                     const float* cond_noise, float* out, void* hip_stream);
 
+/* Scoring: the denoising objective (the reference's training loss, loss.py:29-37) of strokes that already exist, at chosen
+ * noise levels — how well a line fits a text and a hand under the model.  Nothing is sampled.
+ *    strokes  device f32 [B,L,3] = (dx, dy, pen)
+ *    lens     HOST int32 [B] or NULL (every row has L strokes); the rules for lens are dhw_forward_ragged's
+ *    levels   HOST int32 [K]: schedule indices, 0 <= levels[k] < T; duplicates allowed, any order; 1 <= K <= T
+ *    noise    device f32 [K,B,L,2], or NULL
+ *    out      device f32 [K,B,2]
+ * Symbols: beta[i], abar[i] as dhw_schedule(T) gives them; n = lens[b] (L without lens); i = levels[k].
+ *    1. Noise.  z[k,b,p] = noise[k,b,p,:] when noise is given; otherwise the generator's draw for (seed, first_sample + b,
+ *       p, iter = 2^29 + i): an iteration range disjoint from the sampler's (-1 .. T-1) and from the conditioning
+ *       stream's (2^30 + k).  The draw is keyed by the schedule index i, not by k: the score at a level depends neither on
+ *       which other levels are asked for nor on how the batch is sharded.
+ *    2. Perturbation.  x_t = fadd(fmul(sqrtf(abar[i]), x0), fmul(sqrtf(1 - abar[i]), z)), x0 = strokes[..., :2].  The
+ *       coefficients are computed on the host in fp32; the device rounds each product and the sum, no contraction.
+ *    3. Denoiser.  (eps_hat, pen_hat) = dhw_forward_ragged(x_t, text, sigma = sqrtf(abar[i]) for every row, style, lens):
+ *       the same launches and the same precision as that entry, on every handle (DHW_PERSIST=1 included).
+ *    4. Outputs, both means over the valid rows of sample b only:
+ *          out[k,b,0] = (1/n) sum_{p<n} ((z0 - e0)^2 + (z1 - e1)^2)
+ *          out[k,b,1] = abar[i] * (1/n) sum_{p<n} -( t * max(logf(q), -100) + (1 - t) * max(logf(1 - q), -100) ),
+ *       q = pen_hat[p], t = clamp(pen[p], 1e-7, 1 - 1e-7): torch's binary_cross_entropy after the clamp of loss.py:31.
+ *       Without lens, the mean over b of out[k,:,0] + out[k,:,1] is the reference's loss_fn(...)[0] at alphas = abar[i].
+ *    5. Rows that are not read.  Rows of strokes and noise at or past lens[b] are never read: NaNs there change nothing.
+ *    6. Determinism.  Fixed reduction order, no float atomics: the result is bit-deterministic, and out[:, b] of a batch
+ *       equals sample b scored alone at L = lens[b] with first_sample + b, bit for bit.
+ *    7. Argument checks.  Every check runs before the first HIP call and returns DHW_ERR_ARG naming the argument: the
+ *       forward entry's limits (B, L, Lt, lens), 1 <= T <= 2^29, 1 <= K <= T, 0 <= levels[k] < T, non-NULL strokes / text /
+ *       style / levels / out, out and noise 8-byte aligned.
+ * The K levels run as K denoiser calls over B rows on hip_stream, launched eagerly.  The call reads strokes, text, style and
+ * noise in place (they must stay valid until the stream has run it), stages x_t, z and the denoiser's outputs in buffers the
+ * handle allocates at its first score call, and neither alters nor invalidates anything dhw_sample* has cached. */
+int dhw_score(dhw_handle*, const float* strokes, const int64_t* text, const float* style, int B, int L, int Lt,
+              const int32_t* lens, int T, const int32_t* levels, int K, const float* noise, uint64_t seed,
+              int64_t first_sample, float* out, void* hip_stream);
+
 /* Stroke rasteriser: sampled strokes -> grey-level line images in the layout dhw_style_forward consumes (ink
  * left-aligned, white to the right).  No handle: errors are read through dhw_last_error(NULL).  The call allocates
  * nothing, synchronises nothing and can be captured into a graph.  All argument checks run before the first HIP call

@@ -15,7 +15,13 @@ The same lines in another writer's hand (restyling: the strokes an earlier run s
 schedule and denoised under the new style, so the layout stays and the hand changes):
 
     python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --save-strokes lines.npy
-    python infer.py --prompts-file lines.txt other.npy --experiment-path data/best_exp --restyle lines.npy --strength 0.5"""
+    python infer.py --prompts-file lines.txt other.npy --experiment-path data/best_exp --restyle lines.npy --strength 0.5
+
+Every line as the best of N samples under the model's own denoising objective, and that objective for saved lines (one
+"length, score term, pen term, total" per prompt, lower fits better; no images):
+
+    python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --candidates 8
+    python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --score lines.npy"""
 import argparse
 
 import dhg_amd
@@ -39,9 +45,26 @@ def main(argv=None):
     ap.add_argument("--save-strokes", metavar="NPY", help="also write the sampled strokes, [B, max L, 3] padded with 0, to this .npy")
     ap.add_argument("--restyle", metavar="NPY", help="strokes of these prompts from an earlier run (--save-strokes): rewrite them in the hand of `source`")
     ap.add_argument("--strength", type=float, default=0.5, help="--restyle: share of the schedule the old strokes are noised up (0..1, default 0.5)")
+    ap.add_argument("--candidates", type=int, default=1, metavar="N", help="sample every prompt N times and keep the candidate the model scores best")
+    ap.add_argument("--score", metavar="NPY", help="strokes of these prompts from an earlier run (--save-strokes): print how well each line fits its "
+                                                   "text and the hand of `source` under the model; writes no images")
     a = ap.parse_args(argv)
     if not 0.0 <= a.strength <= 1.0:
         ap.error("--strength must lie in [0, 1]")
+    if a.candidates < 1:
+        ap.error("--candidates must be at least 1")
+    if a.score and (a.restyle or a.candidates > 1 or a.save_strokes):
+        ap.error("--score only reads: it goes with neither --restyle, --candidates nor --save-strokes")
+    if a.restyle and a.candidates > 1:
+        ap.error("--candidates belongs to sampling, not to --restyle")
+
+    def report(prompts, source):
+        rows = dhg_amd.score_file(prompts, a.score, source, a.config_path, a.checkpoint_path, a.experiment_path, precision=a.precision,
+                                  seed=a.seed, style_weights=a.style_weights)
+        for i, (n, s_, p_, t_) in enumerate(rows):
+            print(f"line {i}: length {n} score {s_:.6g} pen {p_:.6g} total {t_:.6g}")
+
+    cand = dict(candidates=a.candidates) if a.candidates > 1 else {}   # (candidates = 1: today's calls, argument for argument)
 
     def save(strokes_list):
         if a.save_strokes:
@@ -59,19 +82,24 @@ def main(argv=None):
             prompts = [ln.rstrip("\r\n") for ln in f if ln.strip()]
         if not prompts:
             ap.error(f"{a.prompts_file} holds no prompt")
+        if a.score:
+            return report(prompts, source)
         if a.restyle:
             out = dhg_amd.restyle_file(prompts, a.restyle, source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
                                        a.diffusion_mode, strength=a.strength, precision=a.precision, seed=a.seed,
                                        style_weights=a.style_weights, renderer=a.renderer)
         else:
             out = dhg_amd.infer_file_batch(prompts, source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
-                                           a.diffusion_mode, precision=a.precision, seed=a.seed, style_weights=a.style_weights, renderer=a.renderer)
+                                           a.diffusion_mode, precision=a.precision, seed=a.seed, style_weights=a.style_weights, renderer=a.renderer,
+                                           **cand)
         save(out)
         for i, s in enumerate(out):
             print(f"{s.shape[0]} stroke points -> ./{a.output}_{i}.png")
         return
     if a.prompt is None or a.source is None:
         ap.error("the following arguments are required: prompt, source")
+    if a.score:
+        return report([a.prompt], a.source)
     if a.restyle:
         (strokes,) = dhg_amd.restyle_file([a.prompt], a.restyle, a.source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
                                           a.diffusion_mode, strength=a.strength, precision=a.precision, seed=a.seed,
@@ -80,7 +108,7 @@ def main(argv=None):
         print(f"{strokes.shape[0]} stroke points -> ./{a.output}_0.png")
         return
     strokes = dhg_amd.infer_file(a.prompt, a.source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
-                                 a.diffusion_mode, precision=a.precision, seed=a.seed, style_weights=a.style_weights, renderer=a.renderer)
+                                 a.diffusion_mode, precision=a.precision, seed=a.seed, style_weights=a.style_weights, renderer=a.renderer, **cand)
     save([strokes])
     print(f"{strokes.shape[0]} stroke points -> ./{a.output}.png")
 
