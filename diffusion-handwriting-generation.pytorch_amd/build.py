@@ -10,8 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdhw_hip.so")
 SOURCES = ["gemm.hip", "convblock.hip", "enclayer.hip", "ragged/gemm_ragged.hip", "ragged/convblock_ragged.hip",
-           "ragged/enclayer_ragged.hip", "ragged/attn_ragged.hip", "persist.hip", "attn.hip", "misc.hip", "style.hip", "textside.hip", "train.hip", "render/render.hip", "cond/cond.hip", "score/score.hip", "dhw_api.cpp", "dhw_style_api.cpp", "dhw_train_api.cpp",
-           "render/dhw_render_api.cpp", "cond/dhw_cond_api.cpp", "score/dhw_score_api.cpp", "sampler/weights.cpp", "sampler/workspace.cpp", "sampler/denoiser.cpp", "sampler/sample.cpp", "sampler/debug.cpp"]
+           "ragged/enclayer_ragged.hip", "ragged/attn_ragged.hip", "persist.hip", "attn.hip", "misc.hip", "style.hip", "textside.hip", "train.hip", "render/render.hip", "cond/cond.hip", "score/score.hip", "attnmap/attnmap.hip", "dhw_api.cpp", "dhw_style_api.cpp", "dhw_train_api.cpp",
+           "render/dhw_render_api.cpp", "cond/dhw_cond_api.cpp", "score/dhw_score_api.cpp", "attnmap/dhw_attnmap_api.cpp", "sampler/weights.cpp", "sampler/workspace.cpp", "sampler/denoiser.cpp", "sampler/sample.cpp", "sampler/debug.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
 
@@ -32,7 +32,7 @@ def _stale(target: str, deps: list[str]) -> bool:
 def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    for sub in ("render", "cond", "score", "host", "sampler"):
+    for sub in ("render", "cond", "score", "attnmap", "host", "sampler"):
         headers += [os.path.join(CSRC, sub, f) for f in os.listdir(os.path.join(CSRC, sub)) if f.endswith(".h")]
     headers += [os.path.join(HERE, "..", "include", f) for f in ("dhw.h", "dhw_debug.h", "dhw_style.h", "dhw_train.h")]
     objdir = os.path.join(HERE, "build")

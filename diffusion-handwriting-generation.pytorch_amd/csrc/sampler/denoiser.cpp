@@ -81,7 +81,7 @@ static double gemm_bytes(const dhw_handle* h, const GemmParams& p) {   // algori
   if (p.pool) b += (double)p.B * p.L * p.N * h->es / 2;
   return b;
 }
-static void run_gemm(Ctx& c, const char* label, const GemmParams& p) {
+void run_gemm(Ctx& c, const char* label, const GemmParams& p) {
   if (c.rec) { c.rec_fail = true; return; }
   if (c.err) return;
   Launch l(c.h, c.st, label, gemm_flops(p), gemm_bytes(c.h, p));

@@ -72,6 +72,7 @@ void* need(Ctx& c, void* p, const char* what);
     }                                                                                              \
   } while (0)
 
+void run_gemm(Ctx& c, const char* label, const GemmParams& p);   // one generic GEMM launch (p.lens: the ragged launcher), profiled under `label`
 void tap(Ctx& c, int id, void* p, int rows, int cols, bool f32 = false);
 void taps_clear(dhw_handle* h);
 EncLayerParams enc_params(Ctx& c, int li, const EncLayerW& w, const void* x, int Lk, int lpad, const int64_t* text, void* pool);

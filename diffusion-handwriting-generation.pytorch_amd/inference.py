@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model import DiffusionModel, check_lengths, check_token_ids
+from .model import DiffusionModel, attention_layer_index, check_lengths, check_token_ids
 from .tokenizer import Tokenizer, stroke_length
 
 
@@ -241,6 +241,140 @@ def score(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, styl
         # the launches read the inputs in place: pin them to the model so they outlive the stream's work
         model._last_score_inputs = (s, t, sv, nz, out)
     return out.transpose(0, 1).to(ret_dev)
+
+
+# ---------------------------------------------------------------- attention maps and alignment (include/dhw.h dhw_attention)
+def _check_attention_args(model: DiffusionModel, strokes, text, sigma, style_vector, lengths, layer):
+    """Every argument of ``attention``, checked on the host before any device is touched; returns (lens or None, layer index)."""
+    if not isinstance(strokes, torch.Tensor) or not strokes.dtype.is_floating_point:
+        raise ValueError("strokes must be a floating-point tensor [B,L,2]")
+    if not isinstance(sigma, torch.Tensor) or not isinstance(style_vector, torch.Tensor):
+        raise ValueError("sigma and style_vector must be tensors")
+    B, L = model._check_forward_inputs(strokes, text, sigma, style_vector)
+    if text.dtype.is_floating_point or text.dtype == torch.bool:
+        raise ValueError(f"text must hold integer token ids, got {text.dtype}")
+    lens = check_lengths(lengths, B, L) if lengths is not None else None
+    if model.training or (torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters())):
+        raise ValueError("attention maps are inference-only (eval() and no gradient recording)")
+    return lens, attention_layer_index(layer, model.num_layers)
+
+
+def attention(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, sigma: torch.Tensor, style_vector: torch.Tensor,
+              lengths=None, layer=-1, heads: bool = False):
+    """Which text token each stroke row attends to, in one denoiser call (include/dhw.h dhw_attention).
+
+    strokes f32 [B,L,2], text int [B,Lt] (0 = pad), sigma [B] / [B,1] / [B,1,1], style_vector [B,S,1280] ->
+    ``(mean [B,Lq,Lt], token [B,Lq] int32)``, and ``probs [B,H,Lq,Lt]`` as a third element with ``heads=True``.  ``layer``:
+    an index (0 = enc3 with Lq = L/2, 1 = enc5 with L/4, 2 + i = att_layers.i with L/8; negative from the end, the default -1
+    is the last attention layer) or the module's name.  ``mean`` is the mean of the heads' probabilities, ``token`` its first
+    argmax.  ``lengths``: a ragged batch, as in ``forward``; rows past a sample's end are 0 / -1."""
+    lens, li = _check_attention_args(model, strokes, text, sigma, style_vector, lengths, layer)
+    if not isinstance(heads, (bool, np.bool_)):
+        raise ValueError(f"heads = {heads!r} must be a bool")
+    ret_dev = strokes.device
+    _, _, probs, mean, token = model._attention_call(strokes, text, sigma, style_vector, lens, li, bool(heads), True, True)
+    out = (mean.to(ret_dev), token.to(ret_dev))
+    return out + (probs.to(ret_dev),) if heads else out
+
+
+def token_spans(token, Lt: int) -> list:
+    """Per prompt, per token k < Lt: ``(first_row, last_row + 1)`` of the rows of ``token`` [B,L] that name k, or None for a
+    token that never wins.  (A token's rows need not be contiguous: the span is their hull.)"""
+    tk = np.asarray(token.detach().cpu() if isinstance(token, torch.Tensor) else token)
+    out = []
+    for row in tk:
+        spans = []
+        for k in range(int(Lt)):
+            idx = np.flatnonzero(row == k)
+            spans.append((int(idx[0]), int(idx[-1]) + 1) if idx.size else None)
+        out.append(spans)
+    return out
+
+
+class Alignment:
+    """What ``align`` returns: ``mean`` [B,Lq,Lt] (the layer's head-mean attention), ``token`` [B,L] int32 (the winning token
+    of every stroke row, -1 past the sample's length), ``spans`` (``token_spans(token, Lt)``), ``lengths`` (list or None),
+    ``layer`` (library index)."""
+
+    def __init__(self, mean, token, spans=None, lengths=None, layer=None):
+        self.mean, self.token, self.lengths, self.layer = mean, token, lengths, layer
+        self.spans = spans if spans is not None else token_spans(token, mean.shape[-1] if mean is not None else int(token.max()) + 1)
+
+
+def align(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, style_vector: torch.Tensor, lengths=None, level: int = 0,
+          T: int = 60, layer=-1) -> Alignment:
+    """Where in a line each character sits: the attention map of ``strokes`` [B,L,3] (a sampled line, or pen data) under
+    their ``text``.  The denoiser runs once on ``strokes[..., :2]`` as given — no noise is added — at
+    ``sigma = sqrt(abar[level])`` of the T-step schedule (level 0: the nearly clean end).  Returns an ``Alignment``."""
+    if not isinstance(strokes, torch.Tensor) or not strokes.dtype.is_floating_point:
+        raise ValueError("strokes must be a floating-point tensor [B,L,3]")
+    if strokes.dim() != 3 or strokes.shape[2] != 3:
+        raise ValueError(f"strokes must be [B,L,3], got {tuple(strokes.shape)}")
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 1:
+        raise ValueError(f"T = {T!r} must be a positive integer")
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level < 0 or level >= T:
+        raise ValueError(f"level = {level!r} must be an integer in [0, T = {T})")
+    B, L, _ = strokes.shape
+    xy = strokes[..., :2]
+    sigma = torch.full((B,), float(np.sqrt(_lib.schedule(int(T))[1][int(level)])), dtype=torch.float32)
+    lens, li = _check_attention_args(model, xy, text, sigma, style_vector, lengths, layer)
+    ret_dev = strokes.device
+    _, _, _, mean, token = model._attention_call(xy, text, sigma, style_vector, lens, li, False, True, True)
+    mean, token = mean.to(ret_dev), token.to(ret_dev)
+    full = token.repeat_interleave(L // token.shape[1], dim=1)   # (rows past a length are -1 already: lengths are multiples of 8)
+    return Alignment(mean, full, token_spans(full, text.shape[1]), lens, li)
+
+
+def rewrite_mask(alignment: Alignment, tok_lo, tok_hi) -> torch.Tensor:
+    """The ``keep`` mask [B,L] (bool) that rewrites tokens [tok_lo, tok_hi) of every line and pins the rest: True inside the
+    sample's length where the row's token lies outside the range, False on the rows to rewrite and past the length — ready
+    for ``sample(..., known=strokes, keep=mask)``.  ``tok_lo`` / ``tok_hi``: ints, or one per prompt."""
+    token = alignment.token
+    if not isinstance(token, torch.Tensor) or token.dim() != 2:
+        raise ValueError("alignment.token must be a tensor [B,L]")
+    B, L = token.shape
+
+    def per_prompt(v, name):
+        seq = [v] * B if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) else v
+        try:
+            seq = list(seq)
+        except TypeError:
+            raise ValueError(f"{name} = {v!r} must be an integer or one integer per prompt") from None
+        if len(seq) != B:
+            raise ValueError(f"{name} has {len(seq)} entries, the batch {B}")
+        for i, x in enumerate(seq):
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+                raise ValueError(f"{name}[{i}] = {x!r} is not an integer")
+        return torch.tensor([int(x) for x in seq], dtype=torch.int64, device=token.device)[:, None]
+
+    lo, hi = per_prompt(tok_lo, "tok_lo"), per_prompt(tok_hi, "tok_hi")
+    if bool((lo > hi).any()) or bool((lo < 0).any()):
+        raise ValueError("tok_lo / tok_hi: every range must satisfy 0 <= tok_lo <= tok_hi")
+    tk = token.to(torch.int64)
+    inside = torch.ones((B, L), dtype=torch.bool, device=token.device)
+    if alignment.lengths is not None:
+        lens = torch.tensor([int(n) for n in alignment.lengths], dtype=torch.int64, device=token.device)[:, None]
+        inside = torch.arange(L, device=token.device)[None, :] < lens
+    return inside & (tk >= 0) & ((tk < lo) | (tk >= hi))
+
+
+def align_file(prompts, strokes_path, source, config_path: str | None = None, checkpoint_path: str | None = None,
+               experiment_path: str | None = None, *, precision: str = "bf16", style_weights: str | None = None, level: int = 0,
+               layer=-1):
+    """``infer.py --align``: the lines of ``prompts`` as an earlier run wrote them (``strokes_path``: the .npy of ``infer.py
+    --save-strokes``) aligned to their text by one ``align`` call.  Returns (the Alignment on the host, the prompts' token
+    id lists, the stroke lengths)."""
+    from .checkpoint import load_model
+
+    prompts = list(prompts)
+    config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
+    style = load_style(source, style_weights)
+    text, lens, sv = _encode_batch("align_file", prompts, style)
+    old = _load_strokes(strokes_path, lens)
+    model = load_model(config_path, checkpoint_path, precision=precision, max_B=len(lens), style_rows=style.shape[1])
+    al = align(model, old, text, sv, lengths=lens, level=level, layer=layer)
+    al.mean, al.token = al.mean.detach().cpu(), al.token.detach().cpu()
+    return al, [[int(v) for v in row if int(v) != 0] for row in text.cpu().tolist()], lens
 
 
 def _encode_batch(who: str, prompts, style_vector):

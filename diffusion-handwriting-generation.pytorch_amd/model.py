@@ -83,6 +83,35 @@ def check_lengths(lengths, B: int, L: int | None) -> list:
     return vals
 
 
+ATTENTION_HEADS = (3, 4, 6)   # enc3, enc5, att_layers.* (reference model.py:88-106)
+
+
+def attention_layer_index(layer, num_layers: int) -> int:
+    """The EncoderLayer an attention map is asked of, as the library numbers them (include/dhw.h dhw_attention): 0 = enc3,
+    1 = enc5, 2 + i = att_layers.i.  ``layer``: that index (negative: from the end, -1 = the last attention layer), ``True``
+    (the last attention layer) or the module's name."""
+    n = 2 + int(num_layers)
+    if layer is True:
+        return n - 1
+    if isinstance(layer, str):
+        names = ["enc3", "enc5"] + [f"att_layers.{i}" for i in range(int(num_layers))]
+        if layer not in names:
+            raise ValueError(f"layer = {layer!r} is not an EncoderLayer of this model ({', '.join(names)})")
+        return names.index(layer)
+    if isinstance(layer, bool) or not isinstance(layer, int):
+        try:
+            import numpy as np
+            ok = isinstance(layer, np.integer)
+        except ImportError:   # pragma: no cover
+            ok = False
+        if not ok:
+            raise ValueError(f"layer = {layer!r} must be an integer, a module name or True")
+    li = int(layer)
+    if li < -n or li >= n:
+        raise ValueError(f"layer = {li} must lie in [{-n}, {n}) (0 = enc3, 1 = enc5, 2 + i = att_layers.i)")
+    return li % n
+
+
 class _DifferentiableForward(torch.autograd.Function):
     """``DiffusionModel.forward`` under autograd (reference train.py:46-60: ``model(x, text, sigma, style)`` ... ``loss.backward()``):
     the forward and backward passes of ``train_model.TrainModel`` (hand-written fp32 HIP ops, include/dhw_train.h) as ONE autograd
@@ -239,9 +268,15 @@ class DiffusionModel(nn.Module):
         return tm
 
     # ------------------------------------------------------------------ forward == reference model.py:121-182
-    def forward(self, strokes: torch.Tensor, text: torch.Tensor, sigma: torch.Tensor, style_vector: torch.Tensor, *, lengths=None):
+    def forward(self, strokes: torch.Tensor, text: torch.Tensor, sigma: torch.Tensor, style_vector: torch.Tensor, *, lengths=None,
+                return_attention=False):
         """strokes [B,T,2], text int [B,Lt] (0 = pad), sigma [B,1] or [B,1,1], style_vector [B,S,1280]
         -> (eps [B,T,2] fp32, pen_lifts [B,T] fp32 in (0,1), None).
+
+        ``return_attention`` (keyword only): ``False`` is the call above.  ``True`` (the last attention layer), a module name
+        ("enc3", "enc5", "att_layers.1") or an index (0 = enc3, 1 = enc5, 2 + i = att_layers.i) makes the third element the
+        cross-attention probabilities of that layer, f32 [B,H,Lq,Lt] (include/dhw.h dhw_attention; the slot the original
+        network filled and the reference leaves None).  Inference only: a train-mode or grad-recording call raises.
 
         ``lengths`` (keyword only, B ints, multiples of 8 in [8, T]): a ragged batch.  Row b is the forward of
         ``strokes[b, :lengths[b]]`` alone; eps / pen past lengths[b] are 0 and the strokes there are ignored.  Inference only:
@@ -252,6 +287,18 @@ class DiffusionModel(nn.Module):
         dropout as ``self.training`` says, and ``loss.backward()`` fills ``p.grad`` as the reference's would (train.py:46-60).
         Gradients with respect to the INPUTS are not produced (the reference's training loop does not use them)."""
         grad_path = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if return_attention is not False:
+            if self.training or grad_path:
+                raise ValueError("return_attention: attention maps are inference-only (eval() and no gradient recording)")
+            li = attention_layer_index(return_attention, self.num_layers)
+            lens = None
+            if lengths is not None:
+                if strokes.dim() != 3:
+                    raise ValueError("strokes must be [B, T, 2]")
+                lens = check_lengths(lengths, strokes.shape[0], strokes.shape[1])
+            ret_dev = strokes.device
+            eps, pen, probs, _, _ = self._attention_call(strokes, text, sigma, style_vector, lens, li, True, False, False)
+            return eps.to(ret_dev), pen.to(ret_dev), probs.to(ret_dev)
         if lengths is not None:
             if self.training or grad_path:
                 raise ValueError("lengths: ragged batches are inference-only (eval() and no gradient recording); training stays uniform")
@@ -299,6 +346,53 @@ class DiffusionModel(nn.Module):
             for x in (s, t, sg, sv):
                 x.record_stream(torch.cuda.current_stream(dev))
         return eps.to(ret_dev), pen.to(ret_dev), None
+
+    # ------------------------------------------------------------------ attention maps (include/dhw.h dhw_attention)
+    def _check_forward_inputs(self, strokes, text, sigma, style_vector):
+        """The shape rules of an inference ``forward``, on the host; returns (B, L)."""
+        if not isinstance(strokes, torch.Tensor) or strokes.dim() != 3 or strokes.shape[-1] != 2:
+            raise ValueError("strokes must be [B, T, 2]")
+        B, L, _ = strokes.shape
+        if L < 8 or L % 8:
+            raise ValueError("T must be a multiple of 8 (three 2x down/up-sampling levels, reference model.py:169-175)")
+        if not isinstance(text, torch.Tensor) or text.dim() != 2 or text.shape[0] != B or text.shape[1] < 1:
+            raise ValueError(f"text must be [B = {B}, Lt]")
+        if style_vector.dim() != 3 or (style_vector.shape[1] * style_vector.shape[2]) % 256 or style_vector.shape[2] != 1280 or style_vector.shape[0] != B:
+            raise ValueError("style_vector must be [B, S, 1280]")
+        if sigma.numel() != B:
+            raise ValueError("sigma must hold one value per sample ([B,1] or [B,1,1])")
+        return B, L
+
+    def _attention_call(self, strokes, text, sigma, style_vector, lens, layer: int, want_probs: bool, want_mean: bool, want_token: bool):
+        """One dhw_attention call on checked ``lens`` (list or None) and ``layer`` (library index); returns the device tensors
+        (eps, pen, probs, mean, token), None for an output that was not asked for."""
+        B, L = self._check_forward_inputs(strokes, text, sigma, style_vector)
+        check_token_ids(text)
+        dev = self._device(strokes, text, sigma, style_vector)
+        Lt = text.shape[1]
+        h = self._ensure_handle(dev, B, L, Lt, style_vector.shape[1])
+        l = _lib.lib()
+        H, Lq = C.c_int(), C.c_int()
+        _lib.check(l.dhw_attention_shape(h, layer, L, C.byref(H), C.byref(Lq)), h)
+        H, Lq = H.value, Lq.value
+        with torch.cuda.device(dev):
+            s = strokes.to(dev, torch.float32).contiguous()
+            t = text.to(dev, torch.int64).contiguous()
+            sg = sigma.to(dev, torch.float32).reshape(B).contiguous()
+            sv = style_vector.to(dev, torch.float32).contiguous()
+            eps = torch.empty((B, L, 2), device=dev, dtype=torch.float32)
+            pen = torch.empty((B, L), device=dev, dtype=torch.float32)
+            probs = torch.empty((B, H, Lq, Lt), device=dev, dtype=torch.float32) if want_probs else None
+            mean = torch.empty((B, Lq, Lt), device=dev, dtype=torch.float32) if want_mean else None
+            token = torch.empty((B, Lq), device=dev, dtype=torch.int32) if want_token else None
+            ptr = lambda x: x.data_ptr() if x is not None else None   # noqa: E731
+            st = torch.cuda.current_stream(dev)
+            _lib.check(l.dhw_attention(h, s.data_ptr(), t.data_ptr(), sg.data_ptr(), sv.data_ptr(), B, L, Lt,
+                                       (C.c_int32 * B)(*lens) if lens is not None else None, layer, ptr(probs), ptr(mean), ptr(token),
+                                       eps.data_ptr(), pen.data_ptr(), C.c_void_p(st.cuda_stream)), h)
+            # the launches read the inputs in place: pin them to the model so they outlive the stream's work
+            self._last_attention_inputs = (s, t, sg, sv, eps, pen, probs, mean, token)
+        return eps, pen, probs, mean, token
 
     # ------------------------------------------------------------------ test / measurement hooks (include/dhw_debug.h)
     def debug_read(self, name: str) -> torch.Tensor:

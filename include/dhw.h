@@ -192,6 +192,47 @@ int dhw_score(dhw_handle*, const float* strokes, const int64_t* text, const floa
               const int32_t* lens, int T, const int32_t* levels, int K, const float* noise, uint64_t seed,
               int64_t first_sample, float* out, void* hip_stream);
 
+/* Attention maps: which text token each stroke row attends to.  Every EncoderLayer cross-attends its stroke rows to the text
+ * tokens (model.py:46); the original network returned that map as its third output.  dhw_attention is one denoiser call that
+ * also writes the map of one layer.  `layer` is numbered as in dhw_debug_attention_time:
+ *    layer 0 = enc3            H = 3 heads, Lq = L/2 rows
+ *    layer 1 = enc5            H = 4,       Lq = L/4
+ *    layer 2 + i = att_layers.i  H = 6,     Lq = L/8
+ * dhw_attention_shape gives (H, Lq) for a layer and a length; it needs no device, and with a NULL handle it answers for any
+ * model (only a handle's own limits, its layer count and max_L, are then not checked).
+ *    strokes, text, sigma, style, eps_out, pen_out   as dhw_forward (device)
+ *    lens        HOST int32 [B] or NULL (every row has L strokes); the rules for lens are dhw_forward_ragged's
+ *    probs_out   device f32 [B,H,Lq,Lt] or NULL
+ *    mean_out    device f32 [B,Lq,Lt] or NULL
+ *    token_out   device int32 [B,Lq] or NULL
+ *    1. Outputs of the forward.  eps_out and pen_out are exactly what dhw_forward (lens == NULL) or dhw_forward_ragged writes
+ *       for the same arguments on the same handle, bit for bit: the call is that forward plus what follows.
+ *    2. Probabilities.  P[b,h,q,k] = softmax_k(Q[b,q,h,:] . K[b,k,h,:] / 8 + (text[b,k] == 0) * (-1e9)), all in fp32, the
+ *       dot product a k-ordered fmaf chain over the 64 channels of the head.  Q = Wq(x + PE) of the layer's `mha`, evaluated
+ *       on the layer input the forward left in the workspace; K is that call's text keys of the layer; both in the handle's
+ *       element type (heads narrower than 64 are zero-padded to 64 and their scale is folded into Wq, so the divisor is
+ *       always 8).  On a bf16 handle this is the map of the stored bf16 operands; it is not promised to be what the fused
+ *       kernels hold internally.  A masked key gets exactly 0.0 whenever the prompt has a non-pad token; an all-pad prompt
+ *       gets 1/Lt everywhere, as the reference does.
+ *    3. Mean and token.  mean[b,q,k] = (((P[b,0] + P[b,1]) + P[b,2]) + ...) * (1/H), in head order, 1/H rounded to fp32;
+ *       token[b,q] = the smallest k at which mean[b,q,:] is largest.  NaN compares larger than nothing: a row of mean that
+ *       is NaN throughout (non-finite weights or inputs) gets token 0, so a valid row's token always lies in [0, Lt).
+ *    4. Ragged rows.  With n = lens[b] >> shift (shift = 1, 2, 3 as Lq = L/2, L/4, L/8): rows q >= n of probs and mean are 0
+ *       and token is -1.  Nothing of strokes past lens[b] is read.  Row b equals its alone run at L = lens[b], bit for bit
+ *       (every sum's order depends on the row alone); with every lens[b] == L the call equals the uniform one.
+ *    5. Argument checks.  Each answers DHW_ERR_ARG, naming the argument and dhw_attention, before dhw_finalize, the first
+ *       thing that can touch HIP: null handle, strokes, text, sigma, style, eps_out or pen_out; the forward entry's limits
+ *       (B, L, Lt, lens); 0 <= layer < 2 + num_layers; at least one of probs_out / mean_out / token_out non-NULL; probs_out
+ *       and mean_out 16-byte aligned; Lt <= 168 (what the kernel's LDS tile holds without a raised limit).
+ *    6. Side effects.  Like dhw_score the call launches eagerly on hip_stream — the forward's launches, one GEMM for Q into
+ *       a workspace buffer, one map kernel — and works on a handle created with DHW_PERSIST=1.  It touches neither the
+ *       sampler's staging buffers and graph cache nor its generator state. */
+int dhw_attention_shape(dhw_handle*, int layer, int L, int* heads_out, int* Lq_out);
+int dhw_attention(dhw_handle*, const float* strokes, const int64_t* text, const float* sigma, const float* style,
+                  int B, int L, int Lt, const int32_t* lens, int layer,
+                  float* probs_out, float* mean_out, int32_t* token_out,
+                  float* eps_out, float* pen_out, void* hip_stream);
+
 /* Stroke rasteriser: sampled strokes -> grey-level line images in the layout dhw_style_forward consumes (ink
  * left-aligned, white to the right).  No handle: errors are read through dhw_last_error(NULL).  The call allocates
  * nothing, synchronises nothing and can be captured into a graph.  All argument checks run before the first HIP call

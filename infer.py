@@ -21,7 +21,12 @@ Every line as the best of N samples under the model's own denoising objective, a
 "length, score term, pen term, total" per prompt, lower fits better; no images):
 
     python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --candidates 8
-    python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --score lines.npy"""
+    python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --score lines.npy
+
+Where each character of saved lines sits, from the model's cross attention ("line i: 'c' rows a..b" per token; writes
+<output>_align.npz with mean, token and lengths, and no images):
+
+    python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --align lines.npy"""
 import argparse
 
 import dhg_amd
@@ -48,6 +53,8 @@ def main(argv=None):
     ap.add_argument("--candidates", type=int, default=1, metavar="N", help="sample every prompt N times and keep the candidate the model scores best")
     ap.add_argument("--score", metavar="NPY", help="strokes of these prompts from an earlier run (--save-strokes): print how well each line fits its "
                                                    "text and the hand of `source` under the model; writes no images")
+    ap.add_argument("--align", metavar="NPY", help="strokes of these prompts from an earlier run (--save-strokes): print the stroke rows the model's "
+                                                   "cross attention assigns to every character and write <output>_align.npz; writes no images")
     a = ap.parse_args(argv)
     if not 0.0 <= a.strength <= 1.0:
         ap.error("--strength must lie in [0, 1]")
@@ -55,6 +62,10 @@ def main(argv=None):
         ap.error("--candidates must be at least 1")
     if a.score and (a.restyle or a.candidates > 1 or a.save_strokes):
         ap.error("--score only reads: it goes with neither --restyle, --candidates nor --save-strokes")
+    if a.align and (a.score or a.restyle or a.candidates > 1 or a.save_strokes):
+        ap.error("--align only reads: it goes with neither --score, --restyle, --candidates nor --save-strokes")
+    if a.align and not a.prompts_file:
+        ap.error("--align needs --prompts-file: the lines the strokes were sampled for")
     if a.restyle and a.candidates > 1:
         ap.error("--candidates belongs to sampling, not to --restyle")
 
@@ -63,6 +74,19 @@ def main(argv=None):
                                   seed=a.seed, style_weights=a.style_weights)
         for i, (n, s_, p_, t_) in enumerate(rows):
             print(f"line {i}: length {n} score {s_:.6g} pen {p_:.6g} total {t_:.6g}")
+
+    def report_align(prompts, source):
+        import numpy as np
+        al, ids, lens = dhg_amd.align_file(prompts, a.align, source, a.config_path, a.checkpoint_path, a.experiment_path, precision=a.precision,
+                                           style_weights=a.style_weights)
+        tok = dhg_amd.Tokenizer()
+        for i, spans in enumerate(al.spans):
+            for k, tid in enumerate(ids[i]):
+                ch = tok.decode([tid])
+                where = f"rows {spans[k][0]}..{spans[k][1]}" if spans[k] is not None else "no rows"
+                print(f"line {i}: {ch!r} {where}")
+        np.savez(f"{a.output}_align.npz", mean=np.asarray(al.mean), token=np.asarray(al.token), lengths=np.asarray(lens, np.int32))
+        print(f"alignment of {len(lens)} lines -> ./{a.output}_align.npz")
 
     cand = dict(candidates=a.candidates) if a.candidates > 1 else {}   # (candidates = 1: today's calls, argument for argument)
 
@@ -84,6 +108,8 @@ def main(argv=None):
             ap.error(f"{a.prompts_file} holds no prompt")
         if a.score:
             return report(prompts, source)
+        if a.align:
+            return report_align(prompts, source)
         if a.restyle:
             out = dhg_amd.restyle_file(prompts, a.restyle, source, a.config_path, a.checkpoint_path, a.experiment_path, a.output,
                                        a.diffusion_mode, strength=a.strength, precision=a.precision, seed=a.seed,
