@@ -9,8 +9,11 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdhw_hip.so")
-SOURCES = ["gemm.hip", "convblock.hip", "enclayer.hip", "ragged/gemm_ragged.hip", "ragged/convblock_ragged.hip",
-           "ragged/enclayer_ragged.hip", "ragged/attn_ragged.hip", "persist.hip", "attn.hip", "misc.hip", "style.hip", "textside.hip", "train.hip", "render/render.hip", "cond/cond.hip", "score/score.hip", "attnmap/attnmap.hip", "dhw_api.cpp", "dhw_style_api.cpp", "dhw_train_api.cpp",
+# (the slowest units first: the pool takes them in this order, and the longest compile bounds a clean build)
+SOURCES = ["train/sgemm_f32.hip", "train/sgemm_bf16.hip", "train/sgemm_group.hip", "convblock.hip", "ragged/convblock_ragged.hip", "enclayer.hip",
+           "ragged/enclayer_ragged.hip", "gemm.hip", "ragged/gemm_ragged.hip", "ragged/attn_ragged.hip", "persist.hip", "attn.hip", "misc.hip", "style.hip", "textside.hip",
+           "train.hip", "train/sgemm_launch.hip", "train/elementwise.hip", "train/film_table.hip", "render/render.hip", "cond/cond.hip", "score/score.hip", "attnmap/attnmap.hip",
+           "dhw_api.cpp", "dhw_style_api.cpp", "dhw_train_api.cpp",
            "render/dhw_render_api.cpp", "cond/dhw_cond_api.cpp", "score/dhw_score_api.cpp", "attnmap/dhw_attnmap_api.cpp", "sampler/weights.cpp", "sampler/workspace.cpp", "sampler/denoiser.cpp", "sampler/sample.cpp", "sampler/debug.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
@@ -29,18 +32,20 @@ def _stale(target: str, deps: list[str]) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _obj(objdir: str, s: str) -> str:
+    return os.path.join(objdir, s.rsplit(".", 1)[0].replace("/", "_") + ".o")   # (named by path: unique across sub-directories)
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    for sub in ("render", "cond", "score", "attnmap", "host", "sampler"):
-        headers += [os.path.join(CSRC, sub, f) for f in os.listdir(os.path.join(CSRC, sub)) if f.endswith(".h")]
+    headers = [os.path.join(d, f) for d, _, files in os.walk(CSRC) for f in files if f.endswith(".h")]
     headers += [os.path.join(HERE, "..", "include", f) for f in ("dhw.h", "dhw_debug.h", "dhw_style.h", "dhw_train.h")]
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     jobs = []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
-        obj = os.path.join(objdir, os.path.basename(s).rsplit(".", 1)[0] + ".o")
+        obj = _obj(objdir, s)
         # ragged/<f>_ragged.hip: <f>.hip compiled with per-sample lengths (csrc/dhw_kernels.h, DHW_LENS)
         base = [os.path.join(CSRC, os.path.basename(s).replace("_ragged", ""))] if s.startswith("ragged/") else []
         if force or _stale(obj, [src] + base + headers):
@@ -55,11 +60,11 @@ def build(force: bool = False, verbose: bool = False) -> str:
             raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + r.stdout + r.stderr)
         return r.stderr
 
-    with ThreadPoolExecutor(max_workers=4) as ex:
+    with ThreadPoolExecutor(max_workers=8) as ex:
         for w in ex.map(run, jobs):
             if verbose and w:
                 print(w)
-    objs = [os.path.join(objdir, os.path.basename(s).rsplit(".", 1)[0] + ".o") for s in SOURCES]
+    objs = [_obj(objdir, s) for s in SOURCES]
     if force or jobs or _stale(LIB, objs):
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
     return LIB

@@ -257,7 +257,7 @@ hipError_t launch_colsum(const float* dy, long rows, int C, float* db, hipStream
 hipError_t launch_wgrad(const float* dy, const float* x, int B, int L, int Cout, int Cin, int taps, float* dw, hipStream_t st);
 hipError_t launch_film_linear_bwd(const float* dfilm, const float* sigma, const float* wcat, int B, int cols, float* dw, float* db, float* dsigma, hipStream_t st);
 
-// generic fp32 ops of the training step (train.hip): see include/dhw_train.h (dhw_op_*)
+// generic fp32 ops of the training step (train.hip, train/): see include/dhw_train.h (dhw_op_*)
 struct OpGemm {
   const float* A; long sam, sak, sazo, sazi; int a_shift, a_tap_shift;
   const float* B; long sbk, sbn, sbzo, sbzi, sbt; int b_shift, b_z_shift;

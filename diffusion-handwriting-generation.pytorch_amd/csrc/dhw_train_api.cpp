@@ -1,6 +1,6 @@
 // dhw_train_api.cpp — C-ABI of the training step's first slice (include/dhw_train.h): loss / perturbation / optimizer
 // kernels and the ConvBlock forward + backward built from the generic MFMA GEMM (forward and data-gradient
-// convolutions, the latter with transposed / tap-flipped packed weights) and the kernels of train.hip.
+// convolutions, the latter with transposed / tap-flipped packed weights) and the kernels of train.hip and train/.
 #include <hip/hip_runtime.h>
 #include <map>
 #include <mutex>
@@ -294,7 +294,7 @@ static int gemm_from_desc(const dhw_gemm_desc* d, OpGemm& g) {
   g.bias = d->bias; g.alpha = d->alpha; g.accumulate = d->accumulate; g.bf16 = d->bf16 ? 1 : 0; g.rowsum = d->rowsum; g.addend = d->addend; g.act_out = d->act_out; g.dsilu_of = d->dsilu_of; g.stamps = nullptr;
   g.film_g = d->film_gamma; g.film_b = d->film_beta; g.film_ps = d->film_pstride; g.film_rows = d->film_rows; g.film_act = d->film_act; g.film_out = d->film_out; g.film_add = d->film_addend;
   if (g.film_out && (!g.film_g || !g.film_b || g.film_rows < 1 || g.accumulate)) return tfail(DHW_ERR_ARG, "dhw_op_gemm: film_out needs gamma, beta, film_rows >= 1 and accumulate = 0");
-  // (the rider's second output and its addend are addressed without a batch offset, train.hip "unbatched GEMMs": every batch of a
+  // (the rider's second output and its addend are addressed without a batch offset, train/sgemm_core.h "unbatched GEMMs": every batch of a
   // batched launch would write the same film_out rows)
   if (g.film_out && (long long)g.nzo * g.nzi != 1) return tfail(DHW_ERR_ARG, "dhw_op_gemm: film_out is for unbatched GEMMs (nzo * nzi = 1), got %d x %d", g.nzo, g.nzi);
   return 0;

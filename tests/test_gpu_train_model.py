@@ -205,6 +205,129 @@ def test_gemm_kernel_paths_against_float64_matmul():
                 assert float((act.cpu().double() - F.silu(ref)).abs().max()) <= 2e-5 * max(float(ref.abs().max()), 1.0), (M, N, K, form, bf16)
 
 
+def test_gemm_entry_points_reach_the_right_kernel_instantiation():
+    """dhw_op_gemm / dhw_op_gemm2 / dhw_op_gemm_group called directly, small shapes, one launch per entry of the kernel tables the
+    launchers index (operand orientation x 16-byte / 4-byte loads of A and of B x fp32 / bf16 staging x plain / Conv1d form x 64- /
+    32-row tiles; the pair and the group kernels): an entry that pointed at another instantiation would contract the wrong index or
+    drop the row shifts.  Reference: float64 matmul (of the bf16-ROUNDED operands in the mixed-precision mode), 2e-5 of its maximum."""
+    import ctypes as C
+    from dhg_amd import _lib
+    lib = _lib.lib()
+    gen = torch.Generator().manual_seed(11)
+
+    def dev(t, off=0):   # a device copy whose first element sits `off` floats into its allocation (off = 1: no 16-byte loads)
+        buf = torch.empty(t.numel() + off, device=DEV)
+        v = buf[off:].view(t.shape)
+        v.copy_(t)
+        return v
+
+    def rnd(t, bf16):
+        return (t.to(torch.bfloat16).to(torch.float32) if bf16 else t).double()
+
+    def desc(A, sam, sak, B, sbk, sbn, Cm, M, N, K, *, acc=0, bf16=0, nzi=1, sczi=0, lr=0, taps=1, a_shift=0, a_tap_shift=0, sbt=0, b_shift=0, b_z_shift=0):
+        d = _lib.GemmDesc(A.data_ptr(), sam, sak, 0, 0, a_shift, a_tap_shift, B.data_ptr(), sbk, sbn, 0, 0, sbt, b_shift, b_z_shift,
+                          Cm.data_ptr(), Cm.stride(-2), 1, 0, sczi, M, N, K, 1, nzi, lr, taps, None, 1.0, acc, bf16)
+        d._keep = (A, B, Cm)
+        return d
+
+    def check(Cm, ref, what):
+        torch.cuda.synchronize()
+        err, tol = float((Cm.cpu().double() - ref).abs().max()), 2e-5 * max(float(ref.abs().max()), 1e-6)
+        assert err <= tol, (what, err, tol)
+
+    def plain(A, B, form, Cm, a_off=0, b_off=0, **kw):   # A [M, K], B [K, N] on the host -> the descriptor of C = A B in the given form
+        (M, K), N = A.shape, B.shape[1]
+        As, (sam, sak) = (dev(A.t().contiguous(), a_off), (1, M)) if form == "ATB" else (dev(A, a_off), (K, 1))
+        Bs, (sbk, sbn) = (dev(B.t().contiguous(), b_off), (1, K)) if form == "ABT" else (dev(B, b_off), (N, 1))
+        return desc(As, sam, sak, Bs, sbk, sbn, Cm, M, N, K, **kw)
+
+    def shifted(x, s, L):   # rows r -> x[r + s] inside each sample of L rows, zero outside
+        y = torch.zeros_like(x).view(-1, L, x.shape[1])
+        xv = x.view(-1, L, x.shape[1])
+        if s >= 0:
+            y[:, :L - s] = xv[:, s:]
+        else:
+            y[:, -s:] = xv[:, :L + s]
+        return y.reshape(x.shape)
+
+    # Conv1d(k = 3, 'same') on C-last rows, weights [tap][Cout][Cin] (conv3 of train_model.py): forward, weight gradient, data gradient
+    def conv_fwd(x, W, L, y, bf16=0, a_off=0):
+        (R, Cin), Cout = x.shape, W.shape[1]
+        d = desc(dev(x, a_off), Cin, 1, dev(W), 1, Cin, y, R, Cout, 3 * Cin, bf16=bf16, taps=3, a_shift=-1, a_tap_shift=1, sbt=Cout * Cin, lr=L)
+        return d, sum(shifted(rnd(x, bf16), t - 1, L) @ rnd(W[t], bf16).t() for t in range(3))
+
+    def conv_wgrad(dy, x, L, dW, bf16=0, a_off=0):   # dW [3][Cout][Cin] += dy^T x[r + tap - 1]: the taps as the inner batch index
+        (R, Cout), Cin = dy.shape, x.shape[1]
+        d = desc(dev(dy, a_off), 1, Cout, dev(x), Cin, 1, dW, Cout, Cin, R, acc=1, bf16=bf16, nzi=3, sczi=Cout * Cin, b_shift=-1, b_z_shift=1, lr=L)
+        return d, dW.cpu().double() + torch.stack([rnd(dy, bf16).t() @ shifted(rnd(x, bf16), t - 1, L) for t in range(3)])
+
+    def conv_dgrad(dy, W, L, dx):
+        (R, Cout), Cin = dy.shape, W.shape[2]
+        d = desc(dev(dy), Cout, 1, dev(W), Cin, 1, dx, R, Cin, 3 * Cout, taps=3, a_shift=1, a_tap_shift=-1, sbt=Cout * Cin, lr=L)
+        return d, sum(shifted(dy.double(), 1 - t, L) @ W[t].double() for t in range(3))
+
+    def randn(*shape):
+        return torch.randn(*shape, generator=gen)
+
+    # one GEMM: a ragged tile with a partial K step, every orientation x staging type x load width of A and of B
+    M, N, K = 72, 40, 36
+    for form in ("AB", "ATB", "ABT"):
+        for bf16 in (0, 1):
+            for a_off, b_off in ((0, 0), (0, 1), (1, 0), (1, 1)):
+                A, B, Cm = randn(M, K), randn(K, N), torch.zeros(M, N, device=DEV)
+                assert lib.dhw_op_gemm(C.byref(plain(A, B, form, Cm, a_off, b_off, bf16=bf16)), None) == 0
+                check(Cm, rnd(A, bf16) @ rnd(B, bf16), (form, bf16, a_off, b_off))
+    # aligned fp32 operands, few workgroups: the 32-row-tile table
+    for form in ("AB", "ATB"):
+        A, B, Cm = randn(96, 64), randn(64, 64), torch.zeros(96, 64, device=DEV)
+        assert lib.dhw_op_gemm(C.byref(plain(A, B, form, Cm)), None) == 0
+        check(Cm, A.double() @ B.double(), ("gm32", form))
+    # the Conv1d form (4-byte loads of A as well: with 16-byte loads these fp32 shapes take the 32-row tiles)
+    Bn, L, Cin, Cout = 2, 24, 32, 64
+    for bf16 in (0, 1):
+        for a_off in (0, 1):
+            x, W, y = randn(Bn * L, Cin), randn(3, Cout, Cin), torch.zeros(Bn * L, Cout, device=DEV)
+            d, ref = conv_fwd(x, W, L, y, bf16, a_off)
+            assert lib.dhw_op_gemm(C.byref(d), None) == 0
+            check(y, ref, ("conv forward", bf16, a_off))
+            dy, dW = randn(Bn * L, Cout), randn(3, Cout, Cin).to(DEV)
+            d, ref = conv_wgrad(dy, x, L, dW, bf16, a_off)
+            assert lib.dhw_op_gemm(C.byref(d), None) == 0
+            check(dW, ref, ("conv weight gradient", bf16, a_off))
+    # two GEMMs in one launch: a weight gradient (A^T B, accumulating, K = 192 rows; 32 output rows, so that it keeps 64-row tiles)
+    # with a data gradient of 32 (64-row tile), 64 and 96 rows (32-row tiles), each of the two plain or in the Conv1d form
+    Rw, Lw, Ld, Cout, Cin = 192, 24, 16, 32, 64
+    for wconv in (0, 1):
+        for dconv in (0, 1):
+            for Rd in (32, 64, 96):
+                dy, x, W, dyd = randn(Rw, Cout), randn(Rw, Cin), randn(3, Cout, Cin), randn(Rd, Cout)
+                dx = torch.zeros(Rd, Cin, device=DEV)
+                if wconv:
+                    dW = randn(3, Cout, Cin).to(DEV)
+                    d0, ref0 = conv_wgrad(dy, x, Lw, dW)
+                else:
+                    dW = randn(Cout, Cin).to(DEV)
+                    d0 = plain(dy.t(), x, "ATB", dW, acc=1)   # (A^T as it lies in memory: dy [rows][Cout])
+                    ref0 = dW.cpu().double() + dy.double().t() @ x.double()
+                if dconv:
+                    d1, ref1 = conv_dgrad(dyd, W, Ld, dx)
+                else:
+                    d1, ref1 = plain(dyd, W[1], "AB", dx), dyd.double() @ W[1].double()
+                assert lib.dhw_op_gemm2(C.byref(d0), C.byref(d1), None) == 1, (wconv, dconv, Rd)   # (one launch: the pair kernel)
+                check(dW, ref0, ("pair: weight gradient", wconv, dconv, Rd))
+                check(dx, ref1, ("pair: data gradient", wconv, dconv, Rd))
+    # three GEMMs of different shapes in one launch: A B^T, A^T B, and A B whose 96 rows take 32-row tiles in fp32
+    for bf16 in (0, 1):
+        items = []
+        for form, (M, N, K) in (("ABT", (32, 64, 64)), ("ATB", (32, 48, 96)), ("AB", (96, 64, 32))):
+            A, B, Cm = randn(M, K), randn(K, N), torch.zeros(M, N, device=DEV)
+            items.append((plain(A, B, form, Cm, bf16=bf16), Cm, rnd(A, bf16) @ rnd(B, bf16), form))
+        arr = (_lib.GemmDesc * 3)(*[it[0] for it in items])
+        assert lib.dhw_op_gemm_group(arr, 3, None) == 1, bf16
+        for _, Cm, ref, form in items:
+            check(Cm, ref, ("group", bf16, form))
+
+
 def test_embedding_gather_and_scatter():
     g = torch.Generator().manual_seed(4)
     table = torch.randn(73, 48, generator=g, requires_grad=True)

@@ -1,6 +1,6 @@
 // bench_sgemm.cpp — the training step's GEMM kernel on its main shapes: time per launch and the phase stamps of one workgroup
 // (the middle row tile): start | prologue done | loads of 4 K steps requested | first tile staged | K loop done | output written.
-// Build: tools/build_tools.sh (links a -DDHW_STAMPS build of csrc/train.hip).
+// Build: tools/build_tools.sh (links a -DDHW_STAMPS build of the GEMM units under csrc/train/).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
