@@ -63,6 +63,11 @@ SIGNATURES = {
                                   C.c_int64, _P, _P, C.c_int, _P, _P, _P]),
     "dhw_score": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, _P,
                             C.c_uint64, C.c_int64, _P, _P]),
+    "dhw_ddim_sample": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, _P,
+                                  C.c_uint64, C.c_int64, _P, _P, _P]),
+    "dhw_ddim_invert": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                  _P, _P]),
+    "dhw_ddim_update": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
     "dhw_attention_shape": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dhw_attention": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _P, _P, _P, _P, _P, _P]),
     "dhw_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

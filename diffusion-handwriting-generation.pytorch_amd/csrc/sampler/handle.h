@@ -162,6 +162,10 @@ struct dhw_handle {
   // scoring calls (dhw_score): x_t, z, eps_hat [max_B*max_L, 2], pen_hat [max_B*max_L] and sigma [max_B], allocated once, at
   // the first such call, and never moved.  No graph reads them: a score call launches eagerly and leaves the cached graphs alone.
   float *d_score_xt = nullptr, *d_score_z = nullptr, *d_score_eps = nullptr, *d_score_pen = nullptr, *d_score_sigma = nullptr;
+  // deterministic sampling / inversion (dhw_ddim_sample, dhw_ddim_invert): the state x and the iterate w [max_B*max_L, 2], the
+  // denoiser's eps [max_B*max_L, 2] and pen [max_B*max_L], and sigma [max_B], allocated once, at the first such call, and never
+  // moved.  No graph reads them: the calls launch eagerly and leave the cached graphs alone.
+  float *d_ddim_x = nullptr, *d_ddim_w = nullptr, *d_ddim_eps = nullptr, *d_ddim_pen = nullptr, *d_ddim_sigma = nullptr;
   uint64_t* d_seed = nullptr;   // [seed, first_sample] read by the noise kernels
   // ragged calls (dhw_forward_ragged / dhw_sample_ragged): the per-sample lengths, copied on the caller's stream from a pinned host
   // buffer the handle owns.  The kernels read them at run time, so one captured graph serves every set of lengths of a shape.

@@ -153,11 +153,15 @@ def restyle(strokes: torch.Tensor, text: torch.Tensor, style_vector: torch.Tenso
 
 
 def infer(prompt: str, style_vector: torch.Tensor, model: DiffusionModel, diffusion_mode: str = "new", T: int = 60,
-          seed: int = 0) -> np.ndarray:
+          seed: int = 0, steps: int | None = None) -> np.ndarray:
     """Single-prompt convenience wrapper with the reference's front end: tokenise, L = 16 per token rounded up
-    to a multiple of 8, sample, return the [L,3] stroke array that the reference hands to ``show_strokes``."""
+    to a multiple of 8, sample, return the [L,3] stroke array that the reference hands to ``show_strokes``.
+    ``steps``: sample deterministically at that many levels instead (``sample_ddim``; ``diffusion_mode`` then plays no part)."""
     ids = Tokenizer().encode(prompt)
     text = torch.tensor([ids], dtype=torch.int64)
+    if steps is not None:
+        out = sample_ddim(model, text, style_vector, L=stroke_length(len(ids)), T=T, levels=ddim_levels(T, steps), seed=seed)
+        return out[0].detach().cpu().numpy()
     out = sample(model, text, style_vector, L=stroke_length(len(ids)), T=T, diffusion_mode=diffusion_mode, seed=seed)
     return out[0].detach().cpu().numpy()
 
@@ -241,6 +245,183 @@ def score(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, styl
         # the launches read the inputs in place: pin them to the model so they outlive the stream's work
         model._last_score_inputs = (s, t, sv, nz, out)
     return out.transpose(0, 1).to(ret_dev)
+
+
+# ---------------------------------------------------------------- deterministic sampling and inversion (include/dhw.h dhw_ddim_*)
+def _check_int(name: str, v, lo: int, hi: int | None = None) -> int:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"{name} = {v!r} is not an integer")
+    if v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{name} = {v} must lie in [{lo}, {hi}]" if hi is not None else f"{name} = {v} must be at least {lo}")
+    return int(v)
+
+
+def ddim_levels(T: int = 60, steps: int | None = None) -> list:
+    """The schedule indices ``sample_ddim`` / ``invert`` visit: ``steps`` of them (default T), from T-1 down to 0, evenly
+    spread: ``levels[j] = ((steps-1-j) * (T-1)) // (steps-1)``; a single step is ``[T-1]``.  60, 4 -> [59, 39, 19, 0]."""
+    T = _check_int("T", T, 1, 2 ** 29)
+    steps = T if steps is None else _check_int("steps", steps, 1)
+    if steps > T:
+        raise ValueError(f"steps = {steps} must lie in [1, T = {T}]")
+    if steps == 1:
+        return [T - 1]
+    return [((steps - 1 - j) * (T - 1)) // (steps - 1) for j in range(steps)]
+
+
+def _check_ddim_levels(levels, steps, T) -> list:
+    """``levels`` as given (checked: integers in [0, T), strictly decreasing, at most T) or ``ddim_levels(T, steps)``."""
+    if levels is None:
+        return ddim_levels(T, steps)
+    if steps is not None:
+        raise ValueError("pass steps or levels, not both")
+    lv = _check_levels(levels, T)
+    for j in range(1, len(lv)):
+        if lv[j] >= lv[j - 1]:
+            raise ValueError(f"levels[{j}] = {lv[j]} is not below levels[{j - 1}] = {lv[j - 1]}: levels must be strictly decreasing")
+    return lv
+
+
+def _check_ddim_common(text, style_vector, B: int, lengths, L):
+    if not isinstance(text, torch.Tensor) or text.dim() != 2 or text.shape[0] != B or text.dtype.is_floating_point:
+        raise ValueError(f"text must be an integer tensor [B = {B}, Lt], got {tuple(text.shape) if isinstance(text, torch.Tensor) else type(text).__name__}")
+    if not isinstance(style_vector, torch.Tensor) or style_vector.dim() != 3 or style_vector.shape[0] != B or style_vector.shape[2] != 1280:
+        raise ValueError(f"style_vector must be a tensor [B = {B}, S, 1280]")
+    return check_lengths(lengths, B, L) if lengths is not None else None
+
+
+def sample_ddim(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor, L: int | None = None, T: int = 60,
+                steps: int | None = None, levels=None, latent: torch.Tensor | None = None, seed: int = 0, first_sample: int = 0,
+                lengths=None, return_latent: bool = False):
+    """Deterministic (DDIM, eta = 0) sampling over a sub-sequence of the schedule (include/dhw.h dhw_ddim_sample): one
+    denoiser call per level and no noise after the start, so the line is a function of its start latent alone.
+
+    ``steps``: how many of the T levels to visit (``ddim_levels(T, steps)``; default all), or ``levels``: the schedule indices
+    themselves, strictly decreasing.  ``latent`` f32 [B,L,2]: the start (from ``invert``, ``slerp``, or an earlier call's
+    ``return_latent=True``); without it the generator draws the x_T ``sample`` would draw for (seed, first_sample + b).
+    ``lengths``: a ragged batch, as in ``sample``.  Returns [B,L,3] = (dx, dy, pen of the last call), or (strokes, latent [B,L,2])
+    with ``return_latent=True``.  The calls launch eagerly; they leave ``sample``'s cached graphs and generator state alone."""
+    if not isinstance(text, torch.Tensor) or text.dim() != 2:
+        raise ValueError("text must be an integer tensor [B, Lt]")
+    B, Lt = text.shape
+    if latent is not None:
+        if not isinstance(latent, torch.Tensor) or not latent.dtype.is_floating_point:
+            raise ValueError("latent must be a floating-point tensor [B,L,2]")
+        if latent.dim() != 3 or latent.shape[0] != B or latent.shape[2] != 2 or (L is not None and latent.shape[1] != L):
+            raise ValueError(f"latent must be [B,L,2] = {(B, L if L is not None else 'L', 2)}, got {tuple(latent.shape)}")
+        L = int(latent.shape[1])
+    lens = _check_ddim_common(text, style_vector, B, lengths, L)
+    if L is None:
+        L = max(lens) if lens is not None else stroke_length(Lt)
+    L = _check_int("L", L, 8)
+    if L % 8:
+        raise ValueError(f"L = {L} must be a multiple of 8")
+    lv = _check_ddim_levels(levels, steps, T)
+    seed, first_sample = _check_int("seed", seed, 0, 2 ** 64 - 1), _check_int("first_sample", first_sample, -2 ** 63, 2 ** 63 - 1)
+    if not hasattr(model, "_validated_text"):
+        model._validated_text = []
+    check_token_ids(text, model._validated_text)
+    dev = model._device(text, style_vector) if latent is None else model._device(text, style_vector, latent)
+    h = model._ensure_handle(dev, B, L, Lt, style_vector.shape[1])
+    ret_dev = text.device
+    with torch.cuda.device(dev):
+        t = text.to(dev, torch.int64).contiguous()
+        sv = style_vector.to(dev, torch.float32).contiguous()
+        lat = latent.to(dev, torch.float32).contiguous() if latent is not None else None
+        lat_out = torch.empty((B, L, 2), device=dev, dtype=torch.float32) if return_latent else None
+        out = torch.empty((B, L, 3), device=dev, dtype=torch.float32)
+        stream = torch.cuda.current_stream(dev)
+        S = len(lv)
+        _lib.check(_lib.lib().dhw_ddim_sample(h, t.data_ptr(), sv.data_ptr(), B, L, Lt, (C.c_int32 * B)(*lens) if lens is not None else None,
+                                              T, (C.c_int32 * S)(*lv), S, lat.data_ptr() if lat is not None else None, seed, first_sample,
+                                              lat_out.data_ptr() if lat_out is not None else None, out.data_ptr(),
+                                              C.c_void_p(stream.cuda_stream)), h)
+        # the launches read the inputs in place: pin them to the model so they outlive the stream's work
+        model._last_ddim_inputs = (t, sv, lat, lat_out, out)
+    return (out.to(ret_dev), lat_out.to(ret_dev)) if return_latent else out.to(ret_dev)
+
+
+def invert(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, style_vector: torch.Tensor, lengths=None, T: int = 60,
+           steps: int | None = None, levels=None, iters: int = 1) -> torch.Tensor:
+    """The latent an existing line came from (include/dhw.h dhw_ddim_invert): the deterministic process of ``sample_ddim`` run
+    backwards over the same levels, from ``strokes`` [B,L,3] (sampled, or pen data; the pen column is not read) up to x_T.
+    ``sample_ddim(latent=invert(x))`` under the same text, style and levels reproduces ``x`` to an error the tests measure;
+    under another style or text it rewrites the line reproducibly (``transfer``).  ``iters`` in [1, 8]: fixed-point
+    iterations per step (1 = the usual DDIM inversion); the call makes ``len(levels) * iters`` denoiser calls.
+    Returns the latent [B,L,2], 0 past ``lengths[b]``."""
+    if not isinstance(strokes, torch.Tensor) or not strokes.dtype.is_floating_point:
+        raise ValueError("strokes must be a floating-point tensor [B,L,3]")
+    if strokes.dim() != 3 or strokes.shape[2] != 3:
+        raise ValueError(f"strokes must be [B,L,3], got {tuple(strokes.shape)}")
+    B, L, _ = strokes.shape
+    if L < 8 or L % 8:
+        raise ValueError(f"strokes: L = {L} must be a multiple of 8, at least 8")
+    lens = _check_ddim_common(text, style_vector, B, lengths, L)
+    lv = _check_ddim_levels(levels, steps, T)
+    iters = _check_int("iters", iters, 1, 8)
+    Lt = text.shape[1]
+    if not hasattr(model, "_validated_text"):
+        model._validated_text = []
+    check_token_ids(text, model._validated_text)
+    dev = model._device(strokes, text, style_vector)
+    h = model._ensure_handle(dev, B, L, Lt, style_vector.shape[1])
+    ret_dev = strokes.device
+    with torch.cuda.device(dev):
+        s = strokes.to(dev, torch.float32).contiguous()
+        t = text.to(dev, torch.int64).contiguous()
+        sv = style_vector.to(dev, torch.float32).contiguous()
+        out = torch.empty((B, L, 2), device=dev, dtype=torch.float32)
+        stream = torch.cuda.current_stream(dev)
+        S = len(lv)
+        _lib.check(_lib.lib().dhw_ddim_invert(h, s.data_ptr(), t.data_ptr(), sv.data_ptr(), B, L, Lt, (C.c_int32 * B)(*lens) if lens is not None else None,
+                                              T, (C.c_int32 * S)(*lv), S, iters, out.data_ptr(), C.c_void_p(stream.cuda_stream)), h)
+        model._last_ddim_inputs = (s, t, sv, out)
+    return out.to(ret_dev)
+
+
+def transfer(strokes: torch.Tensor, text: torch.Tensor, style_from: torch.Tensor, style_to: torch.Tensor, model: DiffusionModel,
+             lengths=None, text_to: torch.Tensor | None = None, **kw) -> torch.Tensor:
+    """Rewrite an existing line reproducibly: invert ``strokes`` under ``(text, style_from)``, then ``sample_ddim`` that latent
+    under ``(text_to or text, style_to)``.  Keywords: T, steps, levels (both halves), iters (the inversion).  Returns [B,L,3],
+    the pen from the last denoiser call.  Unlike ``restyle`` nothing is random and no strength is chosen."""
+    iters = kw.pop("iters", 1)
+    extra = set(kw) - {"T", "steps", "levels"}
+    if extra:
+        raise ValueError(f"transfer: unknown keyword(s) {sorted(extra)} (T, steps, levels, iters)")
+    if text_to is not None and (not isinstance(text_to, torch.Tensor) or text_to.dim() != 2 or text_to.shape[0] != text.shape[0]):
+        raise ValueError("text_to must be an integer tensor [B, Lt']")
+    if not isinstance(style_to, torch.Tensor) or style_to.dim() != 3 or style_to.shape[0] != strokes.shape[0] or style_to.shape[2] != 1280:
+        raise ValueError(f"style_to must be a tensor [B = {strokes.shape[0]}, S, 1280]")
+    latent = invert(model, strokes, text, style_from, lengths=lengths, iters=iters, **kw)
+    return sample_ddim(model, text if text_to is None else text_to, style_to, latent=latent, lengths=lengths, **kw)
+
+
+def slerp(latent_a: torch.Tensor, latent_b: torch.Tensor, w, lengths=None) -> torch.Tensor:
+    """Spherical interpolation of two latents [B,L,2], per sample over its own ``lengths[b]`` rows (rows past them are 0):
+    ``sin((1-w) t)/sin(t) a + sin(w t)/sin(t) b`` with t the angle between the flattened a and b; nearly parallel latents
+    (sin t < 1e-6) are interpolated linearly.  ``w``: a number, or B of them.  Plain torch on the latents' device."""
+    for name, x in (("latent_a", latent_a), ("latent_b", latent_b)):
+        if not isinstance(x, torch.Tensor) or not x.dtype.is_floating_point or x.dim() != 3 or x.shape[2] != 2:
+            raise ValueError(f"{name} must be a floating-point tensor [B,L,2]")
+    if latent_a.shape != latent_b.shape:
+        raise ValueError(f"latent_a {tuple(latent_a.shape)} and latent_b {tuple(latent_b.shape)} differ in shape")
+    B, L, _ = latent_a.shape
+    lens = check_lengths(lengths, B, L) if lengths is not None else [L] * B
+    wt = torch.as_tensor(w, dtype=torch.float32).reshape(-1)
+    if wt.numel() not in (1, B) or not torch.isfinite(wt).all():
+        raise ValueError(f"w must be a finite number or {B} of them")
+    wt = wt.expand(B).tolist()
+    out = torch.zeros_like(latent_a)
+    for b, n in enumerate(lens):
+        a, c = latent_a[b, :n].float(), latent_b[b, :n].float()
+        cos = (a * c).sum() / (a.norm() * c.norm()).clamp_min(1e-30)
+        t = torch.acos(cos.clamp(-1.0, 1.0))
+        st = torch.sin(t)
+        if st.item() < 1e-6:
+            r = (1.0 - wt[b]) * a + wt[b] * c
+        else:
+            r = torch.sin((1.0 - wt[b]) * t) / st * a + torch.sin(wt[b] * t) / st * c
+        out[b, :n] = r.to(out.dtype)
+    return out
 
 
 # ---------------------------------------------------------------- attention maps and alignment (include/dhw.h dhw_attention, DESIGN.md §21)
@@ -402,7 +583,7 @@ def _encode_batch(who: str, prompts, style_vector):
 
 
 def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diffusion_mode: str = "new", T: int = 60,
-                seed: int = 0, first_sample: int = 0, candidates: int = 1, levels=None) -> list:
+                seed: int = 0, first_sample: int = 0, candidates: int = 1, levels=None, steps: int | None = None) -> list:
     """Many prompts in ONE ragged sampler call: prompt i is tokenised, gets its own ``L_i = stroke_length(n_i)`` and is padded
     with token 0 to the longest prompt.  ``style_vector`` is [1,S,1280] (one writer for every prompt) or [B,S,1280].  Returns a
     list of [L_i, 3] arrays; entry i equals ``sample(model, text_i, style_i, L=L_i, seed=seed, first_sample=first_sample + i)``.
@@ -410,12 +591,23 @@ def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diff
     ``candidates = N > 1`` (best of N): every prompt is sampled N times — candidate j of prompt b is the sample with generator
     index ``first_sample + j*B + b``, so candidate 0 is the line above — and scored by ``score(..., pen_round=True)`` at
     ``levels``; the line returned for a prompt is the candidate with the lowest mean over levels of score term + pen term
-    (ties: the lower j)."""
+    (ties: the lower j).
+
+    ``steps``: every line is sampled deterministically at that many levels (``sample_ddim`` with ``ddim_levels(T, steps)``)
+    instead; ``diffusion_mode`` then plays no part."""
     candidates = _check_candidates(candidates)
+    if steps is None:
+        def draw(tx, st, ln, first):
+            return sample(model, tx, st, L=max(lens), T=T, diffusion_mode=diffusion_mode, seed=seed, first_sample=first, lengths=ln)
+    else:
+        ddim = ddim_levels(T, steps)
+
+        def draw(tx, st, ln, first):
+            return sample_ddim(model, tx, st, L=max(lens), T=T, levels=ddim, seed=seed, first_sample=first, lengths=ln)
     text, lens, sv = _encode_batch("infer_batch", prompts, style_vector)
     B = len(lens)
     if candidates == 1:
-        out = sample(model, text, sv, L=max(lens), T=T, diffusion_mode=diffusion_mode, seed=seed, first_sample=first_sample, lengths=lens)
+        out = draw(text, sv, lens, first_sample)
         out = out.detach().cpu().numpy()
         return [out[b, :lens[b]].copy() for b in range(B)]
     lv = _check_levels(levels, T)
@@ -427,7 +619,7 @@ def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diff
         r = min(per, candidates - j0)
         tx, st, ln = text.repeat(r, 1), sv.repeat(r, 1, 1), lens * r
         first = first_sample + j0 * B
-        out = sample(model, tx, st, L=max(lens), T=T, diffusion_mode=diffusion_mode, seed=seed, first_sample=first, lengths=ln)
+        out = draw(tx, st, ln, first)
         sc = score(model, out, tx, st, lengths=ln, levels=lv, T=T, seed=seed, first_sample=first, pen_round=True)
         total = sc.detach().cpu().double().sum(dim=2).mean(dim=1).tolist()   # (on the host in fp64: the ranking is the same everywhere)
         out = out.detach().cpu().numpy()
@@ -529,16 +721,18 @@ def _check_renderer(renderer: str) -> None:
 def infer_file(prompt: str, source, config_path: str | None = None, checkpoint_path: str | None = None,
                experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *, precision: str = "bf16",
                seed: int = 0, render: bool = True, style_weights: str | None = None, renderer: str = "matplotlib",
-               candidates: int = 1) -> np.ndarray:
+               candidates: int = 1, steps: int | None = None) -> np.ndarray:
     """The reference's command-line entry (inference.py:19-27) around this build's sampler: resolve config / checkpoint
     (directly or inside ``experiment_path``), load the model, sample one prompt, write ``./<output>.png`` (``renderer``:
     "matplotlib" = the reference's figure, "gpu" = the 96-row grey line image of ``render_strokes``).
-    ``candidates = N > 1``: the best of N samples by ``score`` (``infer_batch``).  Returns the [L,3] strokes."""
+    ``candidates = N > 1``: the best of N samples by ``score`` (``infer_batch``).  ``steps``: deterministic sampling at that
+    many levels (``sample_ddim``).  Returns the [L,3] strokes."""
     from .checkpoint import find_checkpoint, load_model
     from .vis import render_lines_png, show_strokes
 
     _check_renderer(renderer)
     candidates = _check_candidates(candidates)
+    ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}   # (no steps: today's calls, argument for argument)
 
     if experiment_path:
         from pathlib import Path
@@ -552,9 +746,9 @@ def infer_file(prompt: str, source, config_path: str | None = None, checkpoint_p
     style = load_style(source, style_weights)
     model = load_model(config_path, checkpoint_path, precision=precision, max_B=_rounds_capacity(1, candidates), style_rows=style.shape[1])
     if candidates > 1:
-        (strokes,) = infer_batch([prompt], style, model, diffusion_mode=diffusion_mode, seed=seed, candidates=candidates)
+        (strokes,) = infer_batch([prompt], style, model, diffusion_mode=diffusion_mode, seed=seed, candidates=candidates, **ddim)
     else:
-        strokes = infer(prompt, style, model, diffusion_mode=diffusion_mode, seed=seed)
+        strokes = infer(prompt, style, model, diffusion_mode=diffusion_mode, seed=seed, **ddim)
     if render and renderer == "gpu":
         render_lines_png([strokes], [output])
     elif render:
@@ -584,21 +778,23 @@ def _resolve_experiment(config_path, checkpoint_path, experiment_path):
 def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint_path: str | None = None,
                      experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
                      precision: str = "bf16", seed: int = 0, render: bool = True, style_weights: str | None = None,
-                     renderer: str = "matplotlib", candidates: int = 1) -> list:
+                     renderer: str = "matplotlib", candidates: int = 1, steps: int | None = None) -> list:
     """``infer_file`` for many prompts of one writer: one ragged sampler call (``infer_batch``), ``./<output>_<i>.png`` per
     prompt (``renderer="gpu"``: every line rasterised in one ``render_strokes`` call).  ``candidates = N > 1``: every line is
-    the best of N samples by ``score``.  Returns the list of [L_i, 3] strokes."""
+    the best of N samples by ``score``.  ``steps``: deterministic sampling at that many levels (``sample_ddim``).  Returns the
+    list of [L_i, 3] strokes."""
     from .checkpoint import load_model
     from .vis import render_lines_png, show_strokes
 
     _check_renderer(renderer)
     candidates = _check_candidates(candidates)
+    ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}
     prompts = list(prompts)
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
     model = load_model(config_path, checkpoint_path, precision=precision, max_B=_rounds_capacity(max(1, len(prompts)), candidates),
                        style_rows=style.shape[1])
-    strokes = infer_batch(prompts, style, model, diffusion_mode=diffusion_mode, seed=seed, candidates=candidates)
+    strokes = infer_batch(prompts, style, model, diffusion_mode=diffusion_mode, seed=seed, candidates=candidates, **ddim)
     if render and renderer == "gpu":
         render_lines_png(strokes, [f"{output}_{i}" for i in range(len(strokes))])
     elif render:

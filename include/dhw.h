@@ -233,6 +233,63 @@ int dhw_attention(dhw_handle*, const float* strokes, const int64_t* text, const 
                   float* probs_out, float* mean_out, int32_t* token_out,
                   float* eps_out, float* pen_out, void* hip_stream);
 
+/* Deterministic (DDIM, eta = 0) sampling over a sub-sequence of the schedule, and its inversion: the latent an existing line
+ * came from.  The denoiser is conditioned on the continuous sigma = sqrt(abar), so it can be asked at any subset of the T
+ * levels; a deterministic step draws no noise, so a line is a function of its start latent alone.
+ * Symbols: beta[i], abar[i] as dhw_schedule(T) gives them.  levels is a HOST int32 [S] of schedule indices, STRICTLY
+ * DECREASING, 0 <= levels[j] < T, 1 <= S <= T.  a_j = abar[levels[j]] for j < S and a_S = 1, the clean end.
+ * Coefficients, computed on the host in fp32: A_j = sqrtf(a_j), B_j = sqrtf(1.0f - a_j); A_S = 1, B_S = 0.
+ * The update, per stroke row and per coordinate:
+ *    U(base, e; c0, c1, c2, c3) = fadd(fmul(c2, fdiv(fsub(base, fmul(c1, e)), c0)), fmul(c3, e)),
+ * every operation rounded to nearest (the division correctly rounded), nothing contracted: the x0 estimate from (base, e) at
+ * level (c0, c1), moved to level (c2, c3) along the same e.
+ *
+ * dhw_ddim_sample
+ *    text, style   as dhw_forward (device);  lens  HOST int32 [B] or NULL, the rules of dhw_forward_ragged
+ *    latent        device f32 [B,L,2], or NULL;  latent_out  device f32 [B,L,2], or NULL;  out  device f32 [B,L,3]
+ *    1. Start.  x(0) = latent when it is given; otherwise the generator's draw for (seed, first_sample + b, p, iter = -1),
+ *       the x_T dhw_sample draws.  latent_out receives x(0).
+ *    2. Steps j = 0..S-1.  (e, q) = the forward of x(j) with sigma = A_j for every row: the same launches and the same
+ *       precision as dhw_forward_ragged (dhw_forward when lens == NULL).  x(j+1) = U(x(j), e; A_j, B_j, A_{j+1}, B_{j+1}).
+ *    3. Output.  out[b,p] = (x(S)[b,p], q of the last call) for p < lens[b].  Rows at or past lens[b] of out and latent_out
+ *       are 0; rows of latent there are never read.
+ *
+ * dhw_ddim_invert
+ *    strokes  device f32 [B,L,3] (the pen column is not read);  latent_out  device f32 [B,L,2];  1 <= iters <= 8
+ *    1. Start.  y(S) = strokes[..., :2].
+ *    2. Steps j = S-1 down to 0.  w = y(j+1); iters times: (e, _) = the forward of w at sigma = A_j, then
+ *       w = U(y(j+1), e; A_{j+1}, B_{j+1}, A_j, B_j); then y(j) = w.  iters = 1 is the usual DDIM inversion; more iterations
+ *       are the fixed-point refinement of the same equation, whose fixed point is, in exact arithmetic, the exact inverse of
+ *       step j of the sampler.
+ *    3. Output.  latent_out = y(0), rows at or past lens[b] 0; rows of strokes there are never read.
+ *    4. The call makes S * iters denoiser calls.
+ *
+ * dhw_ddim_update
+ *    The one update kernel on given device arrays, so that it can be pinned bit for bit on its own: out[r] = U(base[r], eps[r];
+ *    c0, c1, c2, c3) for the rows r = b*L + p with p < lens[b], 0 for the others, which are not read.  base, eps, out device
+ *    f32 [B,L,2] (out may be base); lens DEVICE int32 [B] or NULL, any 0 <= n (n >= L: every row).  No handle: errors are
+ *    read through dhw_last_error(NULL).  B, L >= 1, B * L < 2^31.
+ *
+ * Rules for all three entries.
+ *    Arguments.  Every check runs before the first HIP call and returns DHW_ERR_ARG naming the argument: the forward entry's
+ *       limits (B, L, Lt, lens); 1 <= T <= 2^29; 1 <= S <= T; every levels[j] in range and the array strictly decreasing;
+ *       iters in [1, 8]; required pointers non-NULL; latent, latent_out, base, eps and dhw_ddim_update's out 8-byte aligned.
+ *    Determinism.  No atomics, no reductions: the result is bit-deterministic; row b of a batch equals sample b run alone at
+ *       L = lens[b] with first_sample + b, bit for bit; with every lens[b] == L the result equals the call with lens == NULL.
+ *    Side effects, as for dhw_score.  Launches are eager on hip_stream.  The state x, the iterate w, the denoiser's outputs
+ *       and sigma live in buffers the handle allocates, at its capacity, at its first ddim call.  text, style, latent and
+ *       strokes are read in place (they must stay valid until the stream has run the call).  Nothing of the sampler's is
+ *       touched: not its graph cache, its generator state, its staging buffers or its step plans.  The entries work on a
+ *       handle created with DHW_PERSIST=1. */
+int dhw_ddim_sample(dhw_handle*, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens,
+                    int T, const int32_t* levels, int S, const float* latent, uint64_t seed, int64_t first_sample,
+                    float* latent_out, float* out, void* hip_stream);
+int dhw_ddim_invert(dhw_handle*, const float* strokes, const int64_t* text, const float* style, int B, int L, int Lt,
+                    const int32_t* lens, int T, const int32_t* levels, int S, int iters, float* latent_out,
+                    void* hip_stream);
+int dhw_ddim_update(const float* base, const float* eps, const int32_t* lens, int B, int L,
+                    float c0, float c1, float c2, float c3, float* out, void* hip_stream);
+
 /* Stroke rasteriser: sampled strokes -> grey-level line images in the layout dhw_style_forward consumes (ink
  * left-aligned, white to the right).  No handle: errors are read through dhw_last_error(NULL).  The call allocates
  * nothing, synchronises nothing and can be captured into a graph.  All argument checks run before the first HIP call

@@ -26,7 +26,11 @@ Every line as the best of N samples under the model's own denoising objective, a
 Where each character of saved lines sits, from the model's cross attention ("line i: 'c' rows a..b" per token; writes
 <output>_align.npz with mean, token and lengths, and no images):
 
-    python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --align lines.npy"""
+    python infer.py --prompts-file lines.txt style.npy --experiment-path data/best_exp --align lines.npy
+
+Deterministic sampling at N of the schedule's levels (DDIM, eta = 0: N denoiser calls instead of 60, no noise after the start):
+
+    python infer.py "Follow the White Rabbit" style.npy --experiment-path data/best_exp --steps 20"""
 import argparse
 
 import dhg_amd
@@ -55,6 +59,8 @@ def main(argv=None):
                                                    "text and the hand of `source` under the model; writes no images")
     ap.add_argument("--align", metavar="NPY", help="strokes of these prompts from an earlier run (--save-strokes): print the stroke rows the model's "
                                                    "cross attention assigns to every character and write <output>_align.npz; writes no images")
+    ap.add_argument("--steps", type=int, default=None, metavar="N", help="sample deterministically (DDIM, eta = 0) at N evenly spread levels of the "
+                                                                         "schedule instead of the stochastic reverse process over all of them")
     a = ap.parse_args(argv)
     if not 0.0 <= a.strength <= 1.0:
         ap.error("--strength must lie in [0, 1]")
@@ -68,6 +74,10 @@ def main(argv=None):
         ap.error("--align needs --prompts-file: the lines the strokes were sampled for")
     if a.restyle and a.candidates > 1:
         ap.error("--candidates belongs to sampling, not to --restyle")
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.steps is not None and (a.score or a.align or a.restyle):
+        ap.error("--steps belongs to sampling: it goes with neither --score, --align nor --restyle")
 
     def report(prompts, source):
         rows = dhg_amd.score_file(prompts, a.score, source, a.config_path, a.checkpoint_path, a.experiment_path, precision=a.precision,
@@ -89,6 +99,8 @@ def main(argv=None):
         print(f"alignment of {len(lens)} lines -> ./{a.output}_align.npz")
 
     cand = dict(candidates=a.candidates) if a.candidates > 1 else {}   # (candidates = 1: today's calls, argument for argument)
+    if a.steps is not None:
+        cand["steps"] = a.steps
 
     def save(strokes_list):
         if a.save_strokes:
