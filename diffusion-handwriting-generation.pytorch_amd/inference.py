@@ -803,6 +803,113 @@ def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint
     return strokes
 
 
+WRAP_MAX_CHARS = 48   # the model's text cap: the reference's dataset drops lines with len(text) >= max_text_len = 50
+
+
+def wrap_text(text: str, max_chars: int = 40):
+    """Greedy word wrap of a text to lines of at most ``max_chars`` characters -> (lines, slots).
+
+    Every line of ``text`` is wrapped on its own (a newline always ends a line); words are what whitespace separates and are
+    joined by one space; a word longer than ``max_chars`` is split hard into pieces of ``max_chars``.  ``slots[i]`` is the
+    slot ``render_page`` draws ``lines[i]`` in: consecutive, except that a blank line of the input skips one slot (a
+    paragraph gap).  ``max_chars`` in [1, 48]."""
+    if not isinstance(text, str):
+        raise ValueError(f"text must be a str, got {type(text).__name__}")
+    max_chars = _check_int("max_chars", max_chars, 1, WRAP_MAX_CHARS)
+    lines, slots, slot = [], [], 0
+    for raw in text.split("\n"):
+        words = raw.split()
+        if not words:
+            slot += 1
+            continue
+        cur = ""
+        for w in words:
+            if cur and len(cur) + 1 + len(w) <= max_chars:
+                cur += " " + w
+                continue
+            if cur:
+                lines.append(cur)
+            while len(w) > max_chars:
+                lines.append(w[:max_chars])
+                w = w[max_chars:]
+            cur = w
+        lines.append(cur)
+        slots.extend(range(slot, slot + len(lines) - len(slots)))
+        slot = slots[-1] + 1
+    return lines, slots
+
+
+def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, max_chars: int = 40, diffusion_mode: str = "new",
+               T: int = 60, seed: int = 0, first_sample: int = 0, candidates: int = 1, levels=None, steps: int | None = None,
+               pages=None, height: int = 1980, width: int = 1400, lines_per_page: int = 20, margin_left: float = 70.0,
+               margin_top: float = 70.0, pitch: float = 92.0, line_width: float = 2.0, scale=None):
+    """Write a text: ``wrap_text`` to lines, ``infer_batch`` for their strokes, ``render_page`` onto pages at one shared scale.
+
+    ``style_vector`` is [1,S,1280] (one writer).  The lines are sampled in rounds of at most the model's batch capacity
+    (``max_B``): the round that starts at line i0 is ``infer_batch(..., first_sample=first_sample + i0 * candidates)``, so with
+    ``candidates = 1`` line i uses generator index ``first_sample + i`` however the rounds fall, and the rounds of a best-of-N
+    run never share an index.  The sampler arguments are ``infer_batch``'s, the page arguments ``render_page``'s; all are
+    checked, with ValueError, before a device is touched.
+
+    Returns (pages f32 [P,1,height,width] on the GPU, the list of [L_i,3] stroke arrays, one per wrapped line)."""
+    from .vis import check_page_geometry, render_page
+
+    lines, slots = wrap_text(text, max_chars)
+    if not lines:
+        raise ValueError("write_page: the text holds no word")
+    candidates = _check_candidates(candidates)
+    T = _check_int("T", T, 1)
+    first_sample = _check_int("first_sample", first_sample, 0)
+    if steps is not None:
+        ddim_levels(T, steps)
+    if candidates > 1:
+        _check_levels(levels, T)
+    if diffusion_mode not in ("new", "standard"):
+        raise ValueError(f"diffusion_mode must be 'new' or 'standard', got {diffusion_mode!r}")
+    g = check_page_geometry(pages, height, width, lines_per_page, margin_left, margin_top, pitch, line_width, scale)
+    if g["pages"] is None:
+        check_page_geometry(slots[-1] // g["lines_per_page"] + 1, height, width, lines_per_page, margin_left, margin_top, pitch, line_width, scale)
+    sv = torch.as_tensor(style_vector)
+    if sv.dim() != 3 or sv.shape[0] != 1:
+        raise ValueError(f"style_vector must be [1,S,1280], got {tuple(sv.shape)}")
+    _encode_batch("write_page", lines, sv)   # (an empty or untokenisable line is refused here, before the first round)
+
+    cap = max(1, int(model._cap["max_B"]))
+    strokes = []
+    for i0 in range(0, len(lines), cap):
+        strokes += infer_batch(lines[i0:i0 + cap], sv, model, diffusion_mode=diffusion_mode, T=T, seed=seed,
+                               first_sample=first_sample + i0 * candidates, candidates=candidates, levels=levels, steps=steps)
+    out, _, _ = render_page(pad_strokes(strokes), [len(s) for s in strokes], slots, pages=pages, height=height, width=width,
+                            lines_per_page=lines_per_page, margin_left=margin_left, margin_top=margin_top, pitch=pitch,
+                            line_width=line_width, scale=scale)
+    return out, strokes
+
+
+def write_page_file(text: str, source, config_path: str | None = None, checkpoint_path: str | None = None,
+                    experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
+                    precision: str = "bf16", seed: int = 0, style_weights: str | None = None, candidates: int = 1,
+                    steps: int | None = None, **page_kwargs) -> list:
+    """``infer.py --page-file``: resolve config / checkpoint as ``infer_file`` does, ``write_page`` the text in the hand of
+    ``source`` and save ``./<output>_p<k>.png`` per page (``vis.save_page_png``).  Returns the list of [L_i,3] strokes."""
+    from .checkpoint import load_model
+    from .vis import save_page_png
+
+    lines, _ = wrap_text(text, page_kwargs.get("max_chars", 40))
+    if not lines:
+        raise ValueError("write_page_file: the text holds no word")
+    candidates = _check_candidates(candidates)
+    ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}
+    config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
+    style = load_style(source, style_weights)
+    model = load_model(config_path, checkpoint_path, precision=precision, max_B=_rounds_capacity(min(len(lines), 64), candidates),
+                       style_rows=style.shape[1])
+    out, strokes = write_page(text, style, model, diffusion_mode=diffusion_mode, seed=seed, candidates=candidates, **ddim, **page_kwargs)
+    out = out.cpu()
+    for k in range(out.shape[0]):
+        save_page_png(out[k], f"{output}_p{k}")
+    return strokes
+
+
 def pad_strokes(strokes_list) -> np.ndarray:
     """A list of [L_i,3] stroke arrays as one f32 [B, max L_i, 3] array, 0 past each line's end: what ``infer.py
     --save-strokes`` writes and ``--restyle`` reads back (line i's length follows from its prompt)."""

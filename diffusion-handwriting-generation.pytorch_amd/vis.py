@@ -129,6 +129,175 @@ def save_line_png(image, width, name: str) -> None:
     Image.fromarray(np.clip(np.rint(a), 0, 255).astype(np.uint8)).save(f"./{name}.png")
 
 
+PAGE_MAX_N = PAGE_MAX_L = 4096   # csrc/page/page_host.h
+_page_workspaces = {}            # device index -> [uint8 workspace tensors of render_page, the newest (largest) last]
+
+
+def _page_workspace(dev, need: int):
+    """As _render_workspace, for render_page: one per device, grown by doubling, outgrown buffers stay referenced."""
+    import torch
+
+    bufs = _page_workspaces.setdefault(dev.index, [])
+    if not bufs or bufs[-1].numel() < need:
+        size = 1 << 16
+        while size < need:
+            size *= 2
+        bufs.append(torch.empty(size, dtype=torch.uint8, device=dev))
+    return bufs[-1]
+
+
+def _page_int(name: str, v, lo: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"{name} = {v!r} is not an integer")
+    if v < lo:
+        raise ValueError(f"{name} = {v} must be >= {lo}")
+    return int(v)
+
+
+def _page_float(name: str, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{name} = {v!r} is not a number")
+    v = float(np.float32(v))
+    if not np.isfinite(v):
+        raise ValueError(f"{name} = {v} must be finite")
+    return v
+
+
+def check_page_geometry(pages, height, width, lines_per_page, margin_left, margin_top, pitch, line_width, scale) -> dict:
+    """The geometry rules of dhw_page (include/dhw.h) with ValueError, on the host: what render_page and write_page check
+    before they touch a device.  ``pages`` may be None (decided later).  Returns the checked values."""
+    g = dict(pages=None if pages is None else _page_int("pages", pages, 1), height=_page_int("height", height, 8),
+             width=_page_int("width", width, 8), lines_per_page=_page_int("lines_per_page", lines_per_page, 1),
+             margin_left=_page_float("margin_left", margin_left), margin_top=_page_float("margin_top", margin_top),
+             pitch=_page_float("pitch", pitch), line_width=_page_float("line_width", line_width),
+             scale=0.0 if scale is None else _page_float("scale", scale))
+    if g["width"] % 4:
+        raise ValueError(f"width = {g['width']} must be a multiple of 4")
+    if not g["pitch"] > 0:
+        raise ValueError(f"pitch = {g['pitch']} must be > 0")
+    for k in ("margin_left", "margin_top"):
+        if g[k] < 0:
+            raise ValueError(f"{k} = {g[k]} must be >= 0")
+    if not g["width"] - 2 * g["margin_left"] > 0:
+        raise ValueError(f"margin_left = {g['margin_left']} leaves no room: width - 2 margin_left must be > 0 (width {g['width']})")
+    if not 0.5 <= g["line_width"] <= 16:
+        raise ValueError(f"line_width = {g['line_width']} must lie in [0.5, 16]")
+    if scale is not None and not g["scale"] > 0:
+        raise ValueError(f"scale = {g['scale']} must be > 0 (None: automatic)")
+    _check_page_count(g, g["pages"])
+    return g
+
+
+def _check_page_count(g: dict, pages) -> None:
+    if pages is None:
+        return
+    if pages * g["height"] * g["width"] >= 2 ** 31:
+        raise ValueError(f"pages x height x width must stay below 2^31 (pages {pages}, height {g['height']}, width {g['width']})")
+    if pages * -(-g["width"] // 32) >= 2 ** 24 or -(-g["height"] // 96) > 65535:
+        raise ValueError(f"pages x width (or height) is beyond the launch grid (pages {pages}, height {g['height']}, width {g['width']})")
+
+
+def _host_ints(name: str, v, N: int):
+    """A host list / array / CPU tensor of N integers -> list of int (ValueError otherwise)."""
+    host = v.tolist() if hasattr(v, "tolist") else list(v)
+    if len(host) != N:
+        raise ValueError(f"{name} must hold {N} entries, got {len(host)}")
+    for i, x in enumerate(host):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise ValueError(f"{name}[{i}] = {x!r} is not an integer")
+        if not -2 ** 31 <= x < 2 ** 31:
+            raise ValueError(f"{name}[{i}] = {x} does not fit int32")
+    return [int(x) for x in host]
+
+
+def render_page(strokes, lengths=None, slots=None, *, pages=None, height: int = 1980, width: int = 1400, lines_per_page: int = 20,
+                margin_left: float = 70.0, margin_top: float = 70.0, pitch: float = 92.0, line_width: float = 2.0, scale=None):
+    """Compose a batch of lines into page images on the GPU, all at ONE scale (include/dhw.h dhw_page).
+
+    strokes: [N,L,3] = (dx, dy, pen), a tensor on any device or an array.  lengths (optional, N ints in [1, L]): line n uses
+    its first lengths[n] strokes.  slots (optional, N ints; default slot n = n): line n is drawn in slot ``slots[n] %
+    lines_per_page`` of page ``slots[n] // lines_per_page``, ``pitch`` pixels below the slot before; a line whose slot is off
+    the pages is not drawn.  Both may be host data or device tensors (a device tensor stays on the device and is not
+    checked).  ``pages=None``: enough pages for the largest slot when the slots are host data, else ceil(N / lines_per_page).
+    ``scale=None``: the largest scale at which every line fits its slot (height ``pitch``, width ``width - 2 margin_left``);
+    a number: that many pixels per stroke unit, and lines may then overlap their neighbours (composed by min).
+
+    Returns (pages f32 [P,1,height,width] grey levels 0..255, scale f32 [1], boxes f32 [N,4] = left, top, right, bottom of each
+    line's ink in page pixels, zeros for a line that draws nothing), all on the GPU.  Every argument rule raises ValueError
+    before a device is touched.  One workspace is cached per device: calls on one device must be ordered on one stream."""
+    import torch
+
+    x = strokes if isinstance(strokes, torch.Tensor) else torch.as_tensor(np.asarray(strokes))
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise ValueError(f"strokes must be [N, L, 3], got {tuple(x.shape)}")
+    if not x.is_floating_point():
+        raise ValueError(f"strokes must be floating-point, got {x.dtype}")
+    N, L = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= N <= PAGE_MAX_N or not 1 <= L <= PAGE_MAX_L:
+        raise ValueError(f"strokes must be [N, L, 3] with N in [1, {PAGE_MAX_N}] and L in [1, {PAGE_MAX_L}], got {tuple(x.shape)}")
+    g = check_page_geometry(pages, height, width, lines_per_page, margin_left, margin_top, pitch, line_width, scale)
+
+    def on_device(v):
+        return isinstance(v, torch.Tensor) and v.is_cuda
+
+    host_lens = host_slots = None
+    if lengths is not None:
+        if on_device(lengths):
+            if lengths.numel() != N:
+                raise ValueError(f"lengths must hold {N} entries, got {lengths.numel()}")
+        else:
+            host_lens = _host_ints("lengths", lengths, N)
+            if any(v < 1 or v > L for v in host_lens):
+                raise ValueError(f"lengths must be {N} integers in [1, {L}], got {host_lens}")
+    if slots is not None:
+        if on_device(slots):
+            if slots.numel() != N:
+                raise ValueError(f"slots must hold {N} entries, got {slots.numel()}")
+        else:
+            host_slots = _host_ints("slots", slots, N)
+    P = g["pages"]
+    if P is None:
+        lpp = g["lines_per_page"]
+        P = max(0, max(host_slots)) // lpp + 1 if host_slots is not None else -(-N // lpp)
+        _check_page_count(g, P)
+    if not torch.cuda.is_available():
+        raise RuntimeError("render_page needs an MI355X (HIP device): there is no CPU path in this package")
+    from . import _lib
+
+    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    l = _lib.lib()
+    with torch.cuda.device(dev):
+        x = x.detach().to(dev, torch.float32).contiguous()
+
+        def ints(host, given):
+            if given is None:
+                return None
+            return torch.tensor(host, dtype=torch.int32).to(dev) if host is not None else given.to(dev, torch.int32).contiguous()
+
+        lens, slot_t = ints(host_lens, lengths), ints(host_slots, slots)
+        need = int(l.dhw_page_workspace_bytes(N, L))
+        ws = _page_workspace(dev, need)
+        out = torch.empty((P, 1, g["height"], g["width"]), device=dev, dtype=torch.float32)
+        scale_out = torch.empty((1,), device=dev, dtype=torch.float32)
+        boxes = torch.empty((N, 4), device=dev, dtype=torch.float32)
+        st = torch.cuda.current_stream(dev)
+        _lib.check(l.dhw_page(x.data_ptr(), lens.data_ptr() if lens is not None else None, slot_t.data_ptr() if slot_t is not None else None,
+                              N, L, P, g["height"], g["width"], g["lines_per_page"], g["margin_left"], g["margin_top"], g["pitch"],
+                              g["line_width"], g["scale"], out.data_ptr(), scale_out.data_ptr(), boxes.data_ptr(), ws.data_ptr(), need,
+                              C.c_void_p(st.cuda_stream)))
+    return out, scale_out, boxes
+
+
+def save_page_png(page, name: str) -> None:
+    """Write one page of render_page to ./<name>.png: `page` ([H,W] or [1,H,W], tensor or array, grey levels 0..255) rounded
+    to uint8."""
+    from PIL import Image
+
+    a = page.detach().cpu().numpy() if hasattr(page, "detach") else np.asarray(page)
+    a = a.reshape(a.shape[-2], a.shape[-1])
+    Image.fromarray(np.clip(np.rint(a), 0, 255).astype(np.uint8)).save(f"./{name}.png")
+
+
 def render_lines_png(strokes_list, names, height: int = 96, width: int = 1400, line_width: float = 2.0) -> None:
     """Render a list of [L_i,3] stroke arrays in ONE render_strokes call and write ./<names[i]>.png for each."""
     lens = [int(len(s)) for s in strokes_list]

@@ -328,6 +328,51 @@ int dhw_render(const float* strokes,      /* device f32 [B,L,3]                 
                int32_t* widths_out,       /* device [B] or NULL                        */
                void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Page compositor: N lines -> P page images, every line drawn at ONE scale in a slot of its own, ink that reaches into a
+ * neighbouring slot composed by min.  (dhw_render scales each line to fill its own image: stacked, those do not make a
+ * page.)  No handle: errors are read through dhw_last_error(NULL).  The call allocates nothing, synchronises nothing and
+ * can be captured into a graph.  All argument checks run before the first HIP call (DHW_ERR_ARG names the argument):
+ * 1 <= N <= 4096, 1 <= L <= 4096, P >= 1, H >= 8, W >= 8 and W % 4 == 0, P H W < 2^31 (and within the launch grid:
+ * P ceil(W/32) < 2^24, ceil(H/96) <= 65535), lines_per_page >= 1, pitch > 0, margin_left >= 0, margin_top >= 0,
+ * W - 2 margin_left > 0, 0.5 <= line_width <= 16, scale >= 0, every float finite, non-NULL strokes / pages / scale_out /
+ * boxes_out / workspace, pages and workspace 16-byte aligned, workspace_bytes >= dhw_page_workspace_bytes(N, L) (0 for an
+ * N or L outside the ranges above).
+ *
+ * Line n, with lens[n] (L when lens is NULL) strokes and slot[n] = slots[n] (n when slots is NULL):
+ *    1.-5. as dhw_render, unchanged: pos = the prefix sums, lift[i] = (rintf(pen[i]) != 0), last = the largest i with a
+ *       lift, segment i is drawn iff 1 <= i < last and !lift[i] (nothing after the last lift is drawn), and
+ *       (xmin, xmax, ymin, ymax)_n = the box of the endpoints of drawn segments.
+ *    6. A line without a drawn segment, and a line whose slot lies outside [0, P lines_per_page), draws nothing and takes
+ *       no part in the scale.
+ *    7. ex_n = xmax_n - xmin_n, ey_n = ymax_n - ymin_n.  s_n = the smaller of pitch / ey_n (when ey_n > 0) and
+ *       (W - 2 margin_left) / ex_n (when ex_n > 0); both extents 0: s_n = +inf.  Each quotient is one fp32 division,
+ *       W - 2 margin_left is formed in fp32.
+ *    8. s = scale when scale > 0, else (automatic) the minimum of s_n over the lines that take part, or 1 if none is
+ *       finite.  min is exact and commutative: s does not depend on the order of the lines, no float atomics are used.
+ *    9. Line n goes to page slot[n] / lines_per_page;  top_n = margin_top + (slot[n] % lines_per_page) pitch.
+ *   10. px = margin_left + (x - xmin_n) s.
+ *   11. py = top_n + (pitch - ey_n s)/2 + (ymax_n - y) s  (the stroke y axis points up, page rows go down; the ink box is
+ *       centred in its slot).
+ *   12. Pixel (r, c) of a page has its centre at (c + 0.5, r + 0.5); d = the smallest Euclidean distance from that centre
+ *       to a drawn segment of ANY line of that page (a zero-length segment is a point); value = 255 (1 - clamp(
+ *       line_width/2 + 0.5 - d, 0, 1)).  Ink outside the page is clipped.  With an explicit scale lines may overlap their
+ *       neighbours: that is allowed and composes by min.
+ *   13. scale_out[0] = s.  boxes_out[n] = (margin_left, top_n + (pitch - ey_n s)/2, margin_left + ex_n s, that top +
+ *       ey_n s): left, top, right, bottom of the line's ink box in page pixels; all four 0 for a line that draws nothing.
+ * The pages are bit-deterministic, independent of the order of the lines, and equal to the element-wise minimum of the
+ * pages of each line drawn alone at scale s. */
+size_t dhw_page_workspace_bytes(int N, int L);
+int dhw_page(const float* strokes,      /* device f32 [N,L,3]                                             */
+             const int32_t* lens,       /* DEVICE int32 [N] or NULL, any 1 <= n <= L                      */
+             const int32_t* slots,      /* DEVICE int32 [N] or NULL (slot[n] = n)                         */
+             int N, int L, int P, int H, int W, int lines_per_page,
+             float margin_left, float margin_top, float pitch,      /* page pixels                        */
+             float line_width, float scale,                         /* scale 0: automatic                 */
+             float* pages,              /* device f32 [P,1,H,W], 0..255                                   */
+             float* scale_out,          /* device f32 [1]                                                 */
+             float* boxes_out,          /* device f32 [N,4]                                               */
+             void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Host-only: beta_i = 0.02 + exp(linspace(ln 1e-5, ln 0.4, T)), abar = cumprod(1-beta), fp32. */
 int dhw_schedule(int T, float* beta_out, float* alpha_bar_out);
 

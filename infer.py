@@ -30,7 +30,11 @@ Where each character of saved lines sits, from the model's cross attention ("lin
 
 Deterministic sampling at N of the schedule's levels (DDIM, eta = 0: N denoiser calls instead of 60, no noise after the start):
 
-    python infer.py "Follow the White Rabbit" style.npy --experiment-path data/best_exp --steps 20"""
+    python infer.py "Follow the White Rabbit" style.npy --experiment-path data/best_exp --steps 20
+
+A whole text as pages (word-wrapped, every line at the same scale, composed on the GPU into <output>_p<k>.png):
+
+    python infer.py --page-file letter.txt style.npy --experiment-path data/best_exp --output letter"""
 import argparse
 
 import dhg_amd
@@ -61,7 +65,13 @@ def main(argv=None):
                                                    "cross attention assigns to every character and write <output>_align.npz; writes no images")
     ap.add_argument("--steps", type=int, default=None, metavar="N", help="sample deterministically (DDIM, eta = 0) at N evenly spread levels of the "
                                                                          "schedule instead of the stochastic reverse process over all of them")
+    ap.add_argument("--page-file", metavar="TXT", help="a text to write as pages: wrapped to lines, every line sampled, all lines composed on the "
+                                                       "GPU at one shared scale into <output>_p<k>.png (a blank line leaves a gap)")
     a = ap.parse_args(argv)
+    if a.page_file and (a.score or a.align or a.restyle):
+        ap.error("--page-file writes a text: it goes with neither --score, --align nor --restyle")
+    if a.page_file and a.prompts_file:
+        ap.error("--page-file and --prompts-file are two ways to give the text: pass one")
     if not 0.0 <= a.strength <= 1.0:
         ap.error("--strength must lie in [0, 1]")
     if a.candidates < 1:
@@ -108,6 +118,21 @@ def main(argv=None):
             np.save(a.save_strokes, dhg_amd.pad_strokes(strokes_list))
             print(f"strokes {len(strokes_list)} x [L,3] -> {a.save_strokes}")
 
+    if a.page_file:
+        if a.prompt is not None and a.source is not None:
+            ap.error("with --page-file pass only the source")
+        source = a.source if a.source is not None else a.prompt
+        if source is None:
+            ap.error("the source (handwriting image or style features) is required")
+        with open(a.page_file, encoding="utf-8") as f:
+            text = f.read()
+        if not text.split():
+            ap.error(f"{a.page_file} holds no word")
+        out = dhg_amd.write_page_file(text, source, a.config_path, a.checkpoint_path, a.experiment_path, a.output, a.diffusion_mode,
+                                      precision=a.precision, seed=a.seed, style_weights=a.style_weights, **cand)
+        save(out)
+        print(f"{len(out)} lines -> ./{a.output}_p<k>.png")
+        return
     if a.prompts_file:
         if a.prompt is not None and a.source is not None:
             ap.error("with --prompts-file pass only the source")
