@@ -37,29 +37,24 @@ static int attention_impl(dhw_handle* h, const float* strokes, const int64_t* te
   if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
   if (!strokes || !text || !sigma || !style || !eps_out || !pen_out)
     return fail(h, DHW_ERR_ARG, "%s: null pointer (%s)", fn, !strokes ? "strokes" : !text ? "text" : !sigma ? "sigma" : !style ? "style" : !eps_out ? "eps_out" : "pen_out");
-  int rc = check_shapes(h, B, L, Lt);
-  if (rc) {   // (the forward entry's message, under this entry's name)
-    const std::string why = dhw_last_error(h);
-    return fail(h, rc, "%s: %s", fn, why.c_str());
-  }
-  if (lens && (rc = check_lens(h, fn, lens, B, L, false))) return rc;
+  int rc = eager_check(h, fn, B, L, Lt, lens, true);   // (the forward entry's shape message, under this entry's name)
+  if (rc) return rc;
   if ((rc = check_layer(h, fn, layer))) return rc;
   if (!probs_out && !mean_out && !token_out) return fail(h, DHW_ERR_ARG, "%s: probs_out, mean_out and token_out are all NULL: nothing to write", fn);
   if (((uintptr_t)probs_out | (uintptr_t)mean_out) & 15)
     return fail(h, DHW_ERR_ARG, "%s: %s must be 16-byte aligned", fn, ((uintptr_t)probs_out & 15) ? "probs_out" : "mean_out");
   if (Lt > ATTNMAP_MAX_LT) return fail(h, DHW_ERR_ARG, "%s: Lt = %d is more than the map kernel holds (%d)", fn, Lt, ATTNMAP_MAX_LT);
 
-  if ((rc = dhw_finalize(h))) return rc;
-  HIPCK(h, hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (lens && (rc = stage_lens(h, fn, lens, B, L, false, st))) return rc;
-  const int* dlens = lens ? h->d_lens : nullptr;
+  EagerCall ec;
+  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec))) return rc;
+  auto& [st, dlens, c] = ec;
   if ((rc = forward_enqueue(h, strokes, text, sigma, style, B, L, Lt, eps_out, pen_out, st, dlens))) return rc;
 
   const EncLayerW& w = h->el[(size_t)layer];
   const int H = layer_heads(layer), sh = layer_shift(layer), Lq = L >> sh, d = w.d;
   if (w.heads != H || d != H * ATTNMAP_D) return fail(h, DHW_ERR_INTERNAL, "%s: layer %d has %d heads over %d channels, the map kernel expects %d x %d", fn, layer, w.heads, d, H, ATTNMAP_D);
-  Ctx c{h, &h->ws[0], st, B, L, Lt, h->dims.S * 5, h->d_film, 2L * h->film_tot};
+  // the Q projection reads the call's FiLM rows and lengths, as the forward's launches did
+  c.film_bs = 2L * h->film_tot;
   c.lens = dlens;
   // the layer's input, as the forward left it (each a debug tap of that call, in the fused and the one-launch-per-GEMM path)
   const void* x = layer == 0 ? CBB(c, CB_ENC2, out) : layer == 1 ? CBB(c, CB_ENC4, out) : layer == 2 ? WS(c, att_dense) : ELB(c, layer - 1, out);

@@ -1,5 +1,5 @@
 // ddim_host.h — the host arithmetic of dhw_ddim_sample / dhw_ddim_invert (include/dhw.h) that needs neither a handle nor a
-// device: the checks of T, S, levels and iters, and the table of per-step coefficients.  Plain C++
+// device: the checks of T, S, levels (over host/levels.h) and iters, and the table of per-step coefficients.  Plain C++
 // (tests/cpp/ddim_host_check.cpp compiles it alone).
 #pragma once
 #include <cmath>
@@ -7,7 +7,8 @@
 #include <cstdio>
 #include <vector>
 
-constexpr int DDIM_MAX_T = 1 << 29;    // as dhw_score: the largest schedule an entry accepts
+#include "../host/levels.h"
+
 constexpr int DDIM_MAX_ITERS = 8;      // fixed-point iterations per inversion step
 
 // the level of step j: A = sqrtf(a_j), B = sqrtf(1 - a_j); entry S is the clean end (1, 0)
@@ -15,20 +16,8 @@ struct DdimCoef {
   float A, B;
 };
 
-// The checks the ddim entries add to the forward entry's: 0 on success, else -1 with the offending argument named in msg.
-inline int ddim_check_levels(int T, const int32_t* levels, int S, char* msg, size_t msg_len) {
-  if (T < 1 || T > DDIM_MAX_T) { snprintf(msg, msg_len, "T = %d must lie in [1, 2^29]", T); return -1; }
-  if (S < 1 || S > T) { snprintf(msg, msg_len, "S = %d must lie in [1, T = %d]", S, T); return -1; }
-  if (!levels) { snprintf(msg, msg_len, "levels is NULL (S = %d entries expected)", S); return -1; }
-  for (int j = 0; j < S; ++j) {
-    if (levels[j] < 0 || levels[j] >= T) { snprintf(msg, msg_len, "levels[%d] = %d must lie in [0, T = %d)", j, (int)levels[j], T); return -1; }
-    if (j > 0 && levels[j] >= levels[j - 1]) {
-      snprintf(msg, msg_len, "levels[%d] = %d is not below levels[%d] = %d: levels must be strictly decreasing", j, (int)levels[j], j - 1, (int)levels[j - 1]);
-      return -1;
-    }
-  }
-  return 0;
-}
+// The checks the ddim entries add to the forward entry's: check_levels with their own count name, strictly decreasing levels.
+inline int ddim_check_levels(int T, const int32_t* levels, int S, char* msg, size_t msg_len) { return check_levels(T, levels, S, "S", true, msg, msg_len); }
 
 inline int ddim_check_iters(int iters, char* msg, size_t msg_len) {
   if (iters < 1 || iters > DDIM_MAX_ITERS) { snprintf(msg, msg_len, "iters = %d must lie in [1, %d]", iters, DDIM_MAX_ITERS); return -1; }

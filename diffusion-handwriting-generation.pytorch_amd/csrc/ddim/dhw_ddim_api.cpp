@@ -11,30 +11,10 @@ namespace {
 int ddim_check_common(dhw_handle* h, const char* fn, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens, int T,
                       const int32_t* levels, int S) {
   if (!text || !style) return fail(h, DHW_ERR_ARG, "%s: null pointer (%s)", fn, !text ? "text" : "style");
-  int rc = check_shapes(h, B, L, Lt);
-  if (rc) return rc;
-  if (lens && (rc = check_lens(h, fn, lens, B, L, false))) return rc;
+  if (int rc = eager_check(h, fn, B, L, Lt, lens)) return rc;
   char msg[160];
   if (ddim_check_levels(T, levels, S, msg, sizeof msg)) return fail(h, DHW_ERR_ARG, "%s: %s", fn, msg);
   return 0;
-}
-
-// the staging buffers of the ddim entries, at the handle's capacity, at the first such call
-int ddim_ensure_buffers(dhw_handle* h) {
-  if (h->d_ddim_x) return 0;
-  const size_t cap = (size_t)h->dims.max_B * h->dims.max_L;
-  int rc;
-  if ((rc = dev_alloc(h, (void**)&h->d_ddim_w, cap * 2 * 4))) return rc;
-  if ((rc = dev_alloc(h, (void**)&h->d_ddim_eps, cap * 2 * 4))) return rc;
-  if ((rc = dev_alloc(h, (void**)&h->d_ddim_pen, cap * 4))) return rc;
-  if ((rc = dev_alloc(h, (void**)&h->d_ddim_sigma, (size_t)h->dims.max_B * 4))) return rc;
-  return dev_alloc(h, (void**)&h->d_ddim_x, cap * 2 * 4);   // (last: it marks the set as complete)
-}
-
-std::vector<DdimCoef> ddim_table(int T, const int32_t* levels, int S) {
-  std::vector<float> beta, abar;
-  schedule_host(T, beta, abar);
-  return ddim_coef_table(abar.data(), levels, S);
 }
 
 int sample_impl_ddim(dhw_handle* h, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens, int T, const int32_t* levels,
@@ -47,14 +27,11 @@ int sample_impl_ddim(dhw_handle* h, const int64_t* text, const float* style, int
   if (((uintptr_t)latent | (uintptr_t)latent_out) & 7)
     return fail(h, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)latent & 7) ? "latent" : "latent_out");
 
-  if ((rc = dhw_finalize(h))) return rc;
-  HIPCK(h, hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  if ((rc = ddim_ensure_buffers(h))) return rc;
-  if (lens && (rc = stage_lens(h, fn, lens, B, L, false, st))) return rc;
-  const int* dl = lens ? h->d_lens : nullptr;
-  const std::vector<DdimCoef> t = ddim_table(T, levels, S);
-  Ctx c{h, &h->ws[0], st, B, L, Lt, h->dims.S * 5, h->d_film, 0};   // (for the profiling bracket of the small launches)
+  EagerCall ec;
+  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec)) || (rc = ensure_scratch(h))) return rc;
+  auto& [st, dl, c] = ec;   // the stream, the staged lengths or null, the Ctx of the small launches (their profiling bracket)
+  const dhw_handle::DenoiseScratch& s = h->scratch;
+  const std::vector<DdimCoef> t = ddim_coef_table(schedule_abar(T).data(), levels, S);
 
   DdimStartParams sp{};
   sp.src = latent;
@@ -65,31 +42,31 @@ int sample_impl_ddim(dhw_handle* h, const int64_t* text, const float* style, int
   sp.L = L;
   sp.seed = seed;
   sp.first_sample = first_sample;
-  sp.x = h->d_ddim_x;
+  sp.x = s.x;
   sp.copy = latent_out;
-  sp.sigma = h->d_ddim_sigma;
+  sp.sigma = s.sigma;
   sp.sigma0 = t[0].A;
   RUN_SMALL(c, "ddim_start", launch_ddim_start(sp, st));
   if (c.err) return c.err;
 
   DdimParams p{};
-  p.base = h->d_ddim_x;
-  p.eps = h->d_ddim_eps;
+  p.base = s.x;
+  p.eps = s.eps;
   p.lens = dl;
   p.rows = sp.rows;
   p.B = B;
   p.L = L;
-  p.pen = h->d_ddim_pen;
+  p.pen = s.pen;
   for (int j = 0; j < S; ++j) {
-    if ((rc = forward_enqueue(h, h->d_ddim_x, text, h->d_ddim_sigma, style, B, L, Lt, h->d_ddim_eps, h->d_ddim_pen, st, dl))) return rc;
+    if ((rc = forward_enqueue(h, s.x, text, s.sigma, style, B, L, Lt, s.eps, s.pen, st, dl))) return rc;
     const bool last = j == S - 1;
     p.c0 = t[(size_t)j].A;
     p.c1 = t[(size_t)j].B;
     p.c2 = t[(size_t)j + 1].A;
     p.c3 = t[(size_t)j + 1].B;
-    p.out = last ? nullptr : h->d_ddim_x;
+    p.out = last ? nullptr : s.x;
     p.out3 = last ? out : nullptr;
-    p.sigma = last ? nullptr : h->d_ddim_sigma;
+    p.sigma = last ? nullptr : s.sigma;
     p.sigma_next = p.c2;
     RUN_SMALL(c, "ddim_update", launch_ddim_update(p, st));
     if (c.err) return c.err;
@@ -108,14 +85,11 @@ int invert_impl_ddim(dhw_handle* h, const float* strokes, const int64_t* text, c
   if (ddim_check_iters(iters, msg, sizeof msg)) return fail(h, DHW_ERR_ARG, "%s: %s", fn, msg);
   if ((uintptr_t)latent_out & 7) return fail(h, DHW_ERR_ARG, "%s: latent_out must be 8-byte aligned", fn);
 
-  if ((rc = dhw_finalize(h))) return rc;
-  HIPCK(h, hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  if ((rc = ddim_ensure_buffers(h))) return rc;
-  if (lens && (rc = stage_lens(h, fn, lens, B, L, false, st))) return rc;
-  const int* dl = lens ? h->d_lens : nullptr;
-  const std::vector<DdimCoef> t = ddim_table(T, levels, S);
-  Ctx c{h, &h->ws[0], st, B, L, Lt, h->dims.S * 5, h->d_film, 0};
+  EagerCall ec;
+  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec)) || (rc = ensure_scratch(h))) return rc;
+  auto& [st, dl, c] = ec;   // the stream, the staged lengths or null, the Ctx of the small launches (their profiling bracket)
+  const dhw_handle::DenoiseScratch& s = h->scratch;
+  const std::vector<DdimCoef> t = ddim_coef_table(schedule_abar(T).data(), levels, S);
 
   DdimStartParams sp{};
   sp.src = strokes;
@@ -124,17 +98,17 @@ int invert_impl_ddim(dhw_handle* h, const float* strokes, const int64_t* text, c
   sp.rows = (long)B * L;
   sp.B = B;
   sp.L = L;
-  sp.x = h->d_ddim_x;
-  sp.sigma = h->d_ddim_sigma;
+  sp.x = s.x;
+  sp.sigma = s.sigma;
   sp.sigma0 = t[(size_t)S - 1].A;
   RUN_SMALL(c, "ddim_start", launch_ddim_start(sp, st));
   if (c.err) return c.err;
 
-  // y(j+1) stays in d_ddim_x while the iterate w lives in d_ddim_w; the last iteration of a step writes y(j) over it, the last
+  // y(j+1) stays in scratch.x while the iterate w lives in scratch.w; the last iteration of a step writes y(j) over it, the last
   // one of the call writes the caller's latent_out
   DdimParams p{};
-  p.base = h->d_ddim_x;
-  p.eps = h->d_ddim_eps;
+  p.base = s.x;
+  p.eps = s.eps;
   p.lens = dl;
   p.rows = sp.rows;
   p.B = B;
@@ -145,11 +119,11 @@ int invert_impl_ddim(dhw_handle* h, const float* strokes, const int64_t* text, c
     p.c2 = t[(size_t)j].A;
     p.c3 = t[(size_t)j].B;
     for (int k = 0; k < iters; ++k) {
-      const float* w = k == 0 ? h->d_ddim_x : h->d_ddim_w;
-      if ((rc = forward_enqueue(h, w, text, h->d_ddim_sigma, style, B, L, Lt, h->d_ddim_eps, h->d_ddim_pen, st, dl))) return rc;
+      const float* w = k == 0 ? s.x : s.w;
+      if ((rc = forward_enqueue(h, w, text, s.sigma, style, B, L, Lt, s.eps, s.pen, st, dl))) return rc;
       const bool step_done = k == iters - 1;
-      p.out = !step_done ? h->d_ddim_w : j == 0 ? latent_out : h->d_ddim_x;
-      p.sigma = step_done && j > 0 ? h->d_ddim_sigma : nullptr;
+      p.out = !step_done ? s.w : j == 0 ? latent_out : s.x;
+      p.sigma = step_done && j > 0 ? s.sigma : nullptr;
       p.sigma_next = j > 0 ? t[(size_t)j - 1].A : 0.f;
       RUN_SMALL(c, "ddim_update", launch_ddim_update(p, st));
       if (c.err) return c.err;

@@ -81,4 +81,16 @@ void text_style_dynamic(Ctx& c);
 void stroke_path(Ctx& c, const float* strokes, const int64_t* text);
 int launch_heads_for(Ctx& c, HeadsParams hp);
 
+// ---------------------------------------------------------------- the eager entries (sampler/sample.cpp)
+// dhw_forward*, dhw_score, dhw_ddim_sample / _invert and dhw_attention open alike: the entry's own null-pointer line,
+// eager_check (no HIP call: the limits of B, L, Lt, under the entry's name when name_shapes is set, and of lens when given),
+// the entry's own checks, eager_begin (dhw_finalize, the device, the copy of lens to h->d_lens on the stream), the work.
+struct EagerCall {
+  hipStream_t st;
+  const int* lens;   // h->d_lens of a ragged call, or null
+  Ctx small;         // for the entry's own small launches (RUN_SMALL): ws[0], FiLM row stride 0
+};
+int eager_check(dhw_handle* h, const char* fn, int B, int L, int Lt, const int32_t* lens, bool name_shapes = false);
+int eager_begin(dhw_handle* h, int B, int L, int Lt, const int32_t* lens, void* hip_stream, EagerCall* ec);
+
 #pragma GCC visibility pop

@@ -159,13 +159,13 @@ struct dhw_handle {
   unsigned char* d_keep_stage = nullptr;
   float* d_cond_noise_stage = nullptr;
   size_t cond_noise_stage_cap = 0;
-  // scoring calls (dhw_score): x_t, z, eps_hat [max_B*max_L, 2], pen_hat [max_B*max_L] and sigma [max_B], allocated once, at
-  // the first such call, and never moved.  No graph reads them: a score call launches eagerly and leaves the cached graphs alone.
-  float *d_score_xt = nullptr, *d_score_z = nullptr, *d_score_eps = nullptr, *d_score_pen = nullptr, *d_score_sigma = nullptr;
-  // deterministic sampling / inversion (dhw_ddim_sample, dhw_ddim_invert): the state x and the iterate w [max_B*max_L, 2], the
-  // denoiser's eps [max_B*max_L, 2] and pen [max_B*max_L], and sigma [max_B], allocated once, at the first such call, and never
-  // moved.  No graph reads them: the calls launch eagerly and leave the cached graphs alone.
-  float *d_ddim_x = nullptr, *d_ddim_w = nullptr, *d_ddim_eps = nullptr, *d_ddim_pen = nullptr, *d_ddim_sigma = nullptr;
+  // the eager entries around the denoiser (dhw_score, dhw_ddim_sample, dhw_ddim_invert): x, w, eps [max_B*max_L, 2], pen
+  // [max_B*max_L] and sigma [max_B], allocated once, at the first such call (ensure_scratch), and never moved.  dhw_score keeps
+  // x_t in x and its draw z in w; the ddim entries keep the state in x and the inversion's iterate in w; eps, pen and sigma are
+  // the denoiser's outputs and input for both.  The entries share the set as they share ws[0]: all of them launch eagerly on
+  // the caller's stream, and within a call every row p < lens[b] is written before a launch of that call reads it, while rows
+  // at or past lens[b] are never read.  No graph reads the set: these calls leave the cached graphs alone.
+  struct DenoiseScratch { float *x = nullptr, *w = nullptr, *eps = nullptr, *pen = nullptr, *sigma = nullptr; } scratch;
   uint64_t* d_seed = nullptr;   // [seed, first_sample] read by the noise kernels
   // ragged calls (dhw_forward_ragged / dhw_sample_ragged): the per-sample lengths, copied on the caller's stream from a pinned host
   // buffer the handle owns.  The kernels read them at run time, so one captured graph serves every set of lengths of a shape.
@@ -232,12 +232,15 @@ int alloc_shared(dhw_handle* h);
 int verify_workspace(dhw_handle* h, const Workspace& w);
 void build_names(dhw_handle* h);
 void destroy_impl(dhw_handle* h);
+void drop_graphs(dhw_handle* h);     // destroy every cached graph of dhw_sample (the caller has synchronised the device)
+int ensure_scratch(dhw_handle* h);   // h->scratch, at the handle's capacity, at the first call that needs it
 
 // ---------------------------------------------------------------- sampler/sample.cpp
 void schedule_host(int T, std::vector<float>& beta, std::vector<float>& alpha);
-int check_shapes(dhw_handle* h, int B, int L, int Lt);
+std::vector<float> schedule_abar(int T);   // alpha alone: what the level tables of dhw_score and the ddim entries index
+int check_shapes(dhw_handle* h, int B, int L, int Lt, const char* fn = nullptr);   // fn: the message opens with "<fn>: "
 int check_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling);
-int stage_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling, hipStream_t st);
+int stage_lens(dhw_handle* h, const int32_t* lens, int B, hipStream_t st);   // the copy of checked lengths to h->d_lens
 int forward_enqueue(dhw_handle* h, const float* strokes, const int64_t* text, const float* sigma, const float* style, int B, int L, int Lt,
                     float* eps_out, float* pen_out, hipStream_t st, const int* lens);
 int forward_impl(dhw_handle* h, const char* fn, const float* strokes, const int64_t* text, const float* sigma, const float* style,

@@ -8,10 +8,11 @@
 #include "../cond/cond.h"
 #include "denoiser.h"
 
-int check_shapes(dhw_handle* h, int B, int L, int Lt) {
+int check_shapes(dhw_handle* h, int B, int L, int Lt, const char* fn) {
   const dhw_dims& d = h->dims;
   if (B < 1 || B > d.max_B || L < 8 || L > d.max_L || L % 8 || Lt < 1 || Lt > d.max_Lt)
-    return fail(h, DHW_ERR_ARG, "shape out of range: B=%d (max %d) L=%d (max %d, multiple of 8) Lt=%d (max %d)", B, d.max_B, L, d.max_L, Lt, d.max_Lt);
+    return fail(h, DHW_ERR_ARG, "%s%sshape out of range: B=%d (max %d) L=%d (max %d, multiple of 8) Lt=%d (max %d)", fn ? fn : "", fn ? ": " : "",
+                B, d.max_B, L, d.max_L, Lt, d.max_Lt);
   return 0;
 }
 
@@ -45,9 +46,15 @@ void schedule_host(int T, std::vector<float>& beta, std::vector<float>& alpha) {
   }
 }
 
-// Ragged calls: check the caller's lengths (host pointer, B entries), refuse the diagnostic configurations that have no per-sample
-// ends, and copy the lengths into h->d_lens on the caller's stream.  The copy's source is the handle's pinned buffer, rewritten only
-// once the previous call's copy has read it (an event on that copy, not a device-wide synchronize).
+std::vector<float> schedule_abar(int T) {
+  std::vector<float> beta, abar;
+  schedule_host(T, beta, abar);
+  return abar;
+}
+
+// Ragged calls: check_lens checks the caller's lengths (host pointer, B entries) and refuses the diagnostic configurations that have
+// no per-sample ends; stage_lens copies checked lengths into h->d_lens on the caller's stream.  The copy's source is the handle's pinned
+// buffer, rewritten only once the previous call's copy has read it (an event on that copy, not a device-wide synchronize).
 int check_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling) {
   if (!lens) return fail(h, DHW_ERR_ARG, "%s: lens is NULL (B = %d entries expected)", fn, B);
   for (int b = 0; b < B; ++b)
@@ -57,8 +64,7 @@ int check_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L,
   return 0;
 }
 
-int stage_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L, bool sampling, hipStream_t st) {
-  if (int rc = check_lens(h, fn, lens, B, L, sampling)) return rc;
+int stage_lens(dhw_handle* h, const int32_t* lens, int B, hipStream_t st) {
   HIPCK(h, hipEventSynchronize(h->lens_ev));
   memcpy(h->h_lens_pin, lens, (size_t)B * 4);
   HIPCK(h, hipMemcpyAsync(h->d_lens, h->h_lens_pin, (size_t)B * 4, hipMemcpyHostToDevice, st));
@@ -66,17 +72,31 @@ int stage_lens(dhw_handle* h, const char* fn, const int32_t* lens, int B, int L,
   return 0;
 }
 
+int eager_check(dhw_handle* h, const char* fn, int B, int L, int Lt, const int32_t* lens, bool name_shapes) {
+  if (int rc = check_shapes(h, B, L, Lt, name_shapes ? fn : nullptr)) return rc;
+  return lens ? check_lens(h, fn, lens, B, L, false) : 0;
+}
+
+int eager_begin(dhw_handle* h, int B, int L, int Lt, const int32_t* lens, void* hip_stream, EagerCall* ec) {
+  if (int rc = dhw_finalize(h)) return rc;
+  HIPCK(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (lens)
+    if (int rc = stage_lens(h, lens, B, st)) return rc;
+  *ec = EagerCall{st, lens ? h->d_lens : nullptr, Ctx{h, &h->ws[0], st, B, L, Lt, h->dims.S * 5, h->d_film, 0}};
+  return 0;
+}
+
 int forward_impl(dhw_handle* h, const char* fn, const float* strokes, const int64_t* text, const float* sigma, const float* style,
                  int B, int L, int Lt, float* eps_out, float* pen_out, void* hip_stream, const int32_t* lens_host, bool ragged) {
   if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
   if (!strokes || !text || !sigma || !style || !eps_out || !pen_out) return fail(h, DHW_ERR_ARG, "%s: null pointer", fn);
-  int rc = check_shapes(h, B, L, Lt);
+  int rc = eager_check(h, fn, B, L, Lt, lens_host);
   if (rc) return rc;
-  if ((rc = dhw_finalize(h))) return rc;
-  HIPCK(h, hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (ragged && (rc = stage_lens(h, fn, lens_host, B, L, false, st))) return rc;
-  return forward_enqueue(h, strokes, text, sigma, style, B, L, Lt, eps_out, pen_out, st, ragged ? h->d_lens : nullptr);
+  if (ragged && !lens_host) return check_lens(h, fn, lens_host, B, L, false);   // (its message for a missing lens)
+  EagerCall ec;
+  if ((rc = eager_begin(h, B, L, Lt, lens_host, hip_stream, &ec))) return rc;
+  return forward_enqueue(h, strokes, text, sigma, style, B, L, Lt, eps_out, pen_out, ec.st, ec.lens);
 }
 
 // The launches of one denoiser call on checked arguments (dhw_forward / dhw_forward_ragged, and every level of dhw_score);
@@ -336,6 +356,18 @@ static int sample_enqueue_all(dhw_handle* h, const SampleCall& sc, bool fork, hi
   return rc;
 }
 
+// A staging buffer of `need` floats that cached graphs read (d_noise_stage, d_cond_noise_stage): growing it moves it, so the
+// graphs and step plans that captured the old pointer are dropped first.
+static int grow_stage(dhw_handle* h, float** buf, size_t* cap, size_t need) {
+  if (need <= *cap) return 0;
+  HIPCK(h, hipDeviceSynchronize());
+  drop_graphs(h);
+  h->plans.clear();
+  if (int rc = dev_alloc(h, (void**)buf, need * 4, false)) return rc;
+  *cap = need;
+  return 0;
+}
+
 int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float* style, int B, int L, int Lt, int T, int mode,
                 const float* noise, uint64_t seed, int64_t first_sample, float* out, void* hip_stream, const int32_t* lens_host, bool ragged,
                 const CondArgs* cond) {
@@ -345,9 +377,10 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
     if (T < 1 || (mode != 0 && mode != 1)) return fail(h, DHW_ERR_ARG, "%s: bad T/mode", fn);
     int rc = check_shapes(h, B, L, Lt);
     if (rc) return rc;
+    // (a conditioned call refuses the persistent step under its own name, below)
+    if (ragged && (rc = check_lens(h, fn, lens_host, B, L, !cond))) return rc;
     if (cond) {
       // every check of the conditioned entry answers before the first HIP call (include/dhw.h, rules 5-7)
-      if (ragged && (rc = check_lens(h, fn, lens_host, B, L, false))) return rc;
       if (h->persist) return fail(h, DHW_ERR_ARG, "%s: the persistent step kernel (DHW_PERSIST=1) does not support conditioned sampling", fn);
       if (cond->t_start < 1 || cond->t_start > T) return fail(h, DHW_ERR_ARG, "%s: t_start = %d must lie in [1, T = %d]", fn, cond->t_start, T);
       if (!cond->known && cond->keep) return fail(h, DHW_ERR_ARG, "%s: keep needs known (known is NULL)", fn);
@@ -360,7 +393,7 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
     if ((rc = dhw_finalize(h))) return rc;
     HIPCK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (ragged && (rc = stage_lens(h, fn, lens_host, B, L, true, st))) return rc;
+    if (ragged && (rc = stage_lens(h, lens_host, B, st))) return rc;
     const int* lens = ragged ? h->d_lens : nullptr;
     if (h->h_step_err && *(volatile unsigned*)h->h_step_err) {
       // a persistent step kernel gave up waiting (bounded spin, persist.h): its results were wrong; say so and fall back for good
@@ -368,8 +401,7 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
       *(volatile unsigned*)h->h_step_err = 0;
       h->persist = false;
       hipDeviceSynchronize();
-      for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
-      h->graphs.clear();
+      drop_graphs(h);
       if (h->d_step_sync) hipMemset(h->d_step_sync, 0, h->step_sync_words * sizeof(unsigned));
       if (code >= 0x100u)
         return fail(h, DHW_ERR_HIP, "persistent step kernel: XCD %u owns samples but no workgroup of the launch ran there in an EARLIER call (partitioned / "
@@ -411,14 +443,7 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
     const float* nz = nullptr;
     if (noise) {
       const size_t need = (size_t)(T + 1) * rows * 2;
-      if (need > h->noise_stage_cap) {
-        HIPCK(h, hipDeviceSynchronize());
-        for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // they captured the old staging pointer
-        h->graphs.clear();
-        h->plans.clear();   // (so did the step plans)
-        if ((rc = dev_alloc(h, (void**)&h->d_noise_stage, need * 4, false))) return rc;
-        h->noise_stage_cap = need;
-      }
+      if ((rc = grow_stage(h, &h->d_noise_stage, &h->noise_stage_cap, need))) return rc;
       HIPCK(h, hipMemcpyAsync(h->d_noise_stage, noise, need * 4, hipMemcpyDeviceToDevice, st));
       nz = h->d_noise_stage;
     }
@@ -438,14 +463,7 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
       }
       if (cond->cond_noise) {
         const size_t need = (size_t)T * rows * 2;
-        if (need > h->cond_noise_stage_cap) {
-          HIPCK(h, hipDeviceSynchronize());
-          for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // they captured the old staging pointer
-          h->graphs.clear();
-          h->plans.clear();
-          if ((rc = dev_alloc(h, (void**)&h->d_cond_noise_stage, need * 4, false))) return rc;
-          h->cond_noise_stage_cap = need;
-        }
+        if ((rc = grow_stage(h, &h->d_cond_noise_stage, &h->cond_noise_stage_cap, need))) return rc;
         HIPCK(h, hipMemcpyAsync(h->d_cond_noise_stage, cond->cond_noise, need * 4, hipMemcpyDeviceToDevice, st));
         cz = h->d_cond_noise_stage;
       }

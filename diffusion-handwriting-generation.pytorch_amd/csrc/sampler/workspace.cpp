@@ -7,6 +7,23 @@ int dev_alloc(dhw_handle* h, void** p, size_t bytes, bool zero) {
   return 0;
 }
 
+int ensure_scratch(dhw_handle* h) {
+  dhw_handle::DenoiseScratch& s = h->scratch;
+  if (s.x) return 0;
+  const size_t cap = (size_t)h->dims.max_B * h->dims.max_L;
+  int rc;
+  if ((rc = dev_alloc(h, (void**)&s.w, cap * 2 * 4))) return rc;
+  if ((rc = dev_alloc(h, (void**)&s.eps, cap * 2 * 4))) return rc;
+  if ((rc = dev_alloc(h, (void**)&s.pen, cap * 4))) return rc;
+  if ((rc = dev_alloc(h, (void**)&s.sigma, (size_t)h->dims.max_B * 4))) return rc;
+  return dev_alloc(h, (void**)&s.x, cap * 2 * 4);   // (last: it marks the set as complete)
+}
+
+void drop_graphs(dhw_handle* h) {
+  for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
+  h->graphs.clear();
+}
+
 static int act_alloc(dhw_handle* h, void** slot, long rows, int cols, bool f32 = false) {
   const size_t bytes = (size_t)(rows + SLACK_ROWS) * cols * (f32 ? 4 : h->es);
   return dev_alloc(h, slot, bytes, true);
@@ -155,7 +172,7 @@ int verify_workspace(dhw_handle* h, const Workspace& w) {
 void destroy_impl(dhw_handle* h) {
   hipSetDevice(h->device);
   hipDeviceSynchronize();
-  for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
+  drop_graphs(h);
   for (auto& r : h->prof_recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   for (int i = 1; i < MAX_STREAMS; ++i)
     if (h->sub_streams[i]) hipStreamDestroy(h->sub_streams[i]);

@@ -10,50 +10,38 @@ static int score_impl(dhw_handle* h, const float* strokes, const int64_t* text, 
   // every check answers before the first HIP call (include/dhw.h, rule 7)
   if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
   if (!strokes || !text || !style || !out) return fail(h, DHW_ERR_ARG, "%s: null pointer (%s)", fn, !strokes ? "strokes" : !text ? "text" : !style ? "style" : "out");
-  int rc = check_shapes(h, B, L, Lt);
+  int rc = eager_check(h, fn, B, L, Lt, lens);
   if (rc) return rc;
-  if (lens && (rc = check_lens(h, fn, lens, B, L, false))) return rc;
   char msg[128];
   if (score_check_levels(T, levels, K, msg, sizeof msg)) return fail(h, DHW_ERR_ARG, "%s: %s", fn, msg);
   if (((uintptr_t)out | (uintptr_t)noise) & 7) return fail(h, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)out & 7) ? "out" : "noise");
 
-  if ((rc = dhw_finalize(h))) return rc;
-  HIPCK(h, hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (!h->d_score_xt) {
-    const size_t cap = (size_t)h->dims.max_B * h->dims.max_L;
-    if ((rc = dev_alloc(h, (void**)&h->d_score_z, cap * 2 * 4))) return rc;
-    if ((rc = dev_alloc(h, (void**)&h->d_score_eps, cap * 2 * 4))) return rc;
-    if ((rc = dev_alloc(h, (void**)&h->d_score_pen, cap * 4))) return rc;
-    if ((rc = dev_alloc(h, (void**)&h->d_score_sigma, (size_t)h->dims.max_B * 4))) return rc;
-    if ((rc = dev_alloc(h, (void**)&h->d_score_xt, cap * 2 * 4))) return rc;   // (last: it marks the set as complete)
-  }
-  if (lens && (rc = stage_lens(h, fn, lens, B, L, false, st))) return rc;
-  std::vector<float> beta, abar;
-  schedule_host(T, beta, abar);
-  const std::vector<ScoreLevel> table = score_level_table(abar.data(), levels, K);
+  EagerCall ec;
+  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec)) || (rc = ensure_scratch(h))) return rc;
+  auto& [st, dl, c] = ec;   // the stream, the staged lengths or null, the Ctx of the two small launches (their profiling bracket)
+  const dhw_handle::DenoiseScratch& s = h->scratch;   // x = x_t, w = the draw z
+  const std::vector<ScoreLevel> table = score_level_table(schedule_abar(T).data(), levels, K);
 
   ScoreParams p{};
   p.strokes = strokes;
-  p.lens = lens ? h->d_lens : nullptr;
+  p.lens = dl;
   p.rows = (long)B * L;
   p.B = B;
   p.L = L;
   p.seed = seed;
   p.first_sample = first_sample;
-  p.xt = h->d_score_xt;
-  p.sigma = h->d_score_sigma;
-  p.z = h->d_score_z;
-  p.eps = h->d_score_eps;
-  p.pen = h->d_score_pen;
-  Ctx c{h, &h->ws[0], st, B, L, Lt, h->dims.S * 5, h->d_film, 0};   // (for the profiling bracket of the two small launches)
+  p.xt = s.x;
+  p.sigma = s.sigma;
+  p.z = s.w;
+  p.eps = s.eps;
+  p.pen = s.pen;
   for (int k = 0; k < K; ++k) {
     p.lv = table[(size_t)k];
     p.noise = noise ? noise + (size_t)k * p.rows * 2 : nullptr;
     p.out = out + (size_t)k * B * 2;
     RUN_SMALL(c, "score_perturb", launch_score_perturb(p, st));
     if (c.err) return c.err;
-    if ((rc = forward_enqueue(h, p.xt, text, p.sigma, style, B, L, Lt, h->d_score_eps, h->d_score_pen, st, p.lens))) return rc;
+    if ((rc = forward_enqueue(h, p.xt, text, p.sigma, style, B, L, Lt, s.eps, s.pen, st, p.lens))) return rc;
     RUN_SMALL(c, "score_reduce", launch_score_reduce(p, st));
     if (c.err) return c.err;
   }

@@ -1,13 +1,15 @@
 // score_host.h — the host arithmetic of dhw_score (include/dhw.h) that needs neither a handle nor a device: the checks of T,
-// K and levels, and the table of per-level coefficients.  Plain C++ (tests/cpp/score_host_check.cpp compiles it alone).
+// K and levels (over host/levels.h) and the table of per-level coefficients.  Plain C++ (tests/cpp/score_host_check.cpp compiles it alone).
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <vector>
 
+#include "../host/levels.h"
+
 // iteration number the scoring draw of schedule index i is keyed by: disjoint from the sampler's (-1 .. T-1) and from the
-// conditioning stream's (2^30 + k)
+// conditioning stream's (2^30 + k); T <= MAX_T keeps SCORE_ITER0 + i below 2^30
 constexpr int SCORE_ITER0 = 1 << 29;
 
 // one noise level of a dhw_score call
@@ -17,15 +19,8 @@ struct ScoreLevel {
   int iter;       // SCORE_ITER0 + i
 };
 
-// The checks dhw_score adds to the forward entry's: 0 on success, else -1 with the offending argument named in msg.
-inline int score_check_levels(int T, const int32_t* levels, int K, char* msg, size_t msg_len) {
-  if (T < 1 || T > SCORE_ITER0) { snprintf(msg, msg_len, "T = %d must lie in [1, 2^29]", T); return -1; }
-  if (K < 1 || K > T) { snprintf(msg, msg_len, "K = %d must lie in [1, T = %d]", K, T); return -1; }
-  if (!levels) { snprintf(msg, msg_len, "levels is NULL (K = %d entries expected)", K); return -1; }
-  for (int k = 0; k < K; ++k)
-    if (levels[k] < 0 || levels[k] >= T) { snprintf(msg, msg_len, "levels[%d] = %d must lie in [0, T = %d)", k, (int)levels[k], T); return -1; }
-  return 0;
-}
+// The checks dhw_score adds to the forward entry's: check_levels with its own count name, any order, duplicates allowed.
+inline int score_check_levels(int T, const int32_t* levels, int K, char* msg, size_t msg_len) { return check_levels(T, levels, K, "K", false, msg, msg_len); }
 
 // levels (checked) -> coefficients; abar holds the T entries dhw_schedule gives.  fp32 throughout.
 inline std::vector<ScoreLevel> score_level_table(const float* abar, const int32_t* levels, int K) {

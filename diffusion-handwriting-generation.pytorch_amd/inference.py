@@ -3,13 +3,11 @@ loop (reference inference.py:80-96) for a whole prompt batch; ``infer`` wraps it
 the tokenizer and the stroke-length heuristic (inference.py:65-78)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
-from .model import DiffusionModel, attention_layer_index, check_lengths, check_token_ids
+from .model import DiffusionModel, attention_layer_index, check_lengths, check_token_ids  # noqa: F401 (check_token_ids: re-exported)
 from .tokenizer import Tokenizer, stroke_length
 
 
@@ -21,6 +19,29 @@ def get_beta_set(T: int = 60) -> torch.Tensor:
 def get_alpha_set(T: int = 60) -> torch.Tensor:
     """abar = cumprod(1 - beta) (reference inference.py:81)."""
     return torch.from_numpy(_lib.schedule(T)[1])
+
+
+def _check_int(name: str, v, lo: int | None = None, hi: int | None = None, why: str | None = None, hi_text: str | None = None) -> int:
+    """The one "a real integer in [lo, hi]" check.  ``why``: the caller's own wording for any failure (``name = v why``);
+    ``hi_text``: how the caller names the upper bound in the range message."""
+    is_int = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
+    in_range = is_int and (lo is None or v >= lo) and (hi is None or v <= hi)
+    if why is not None and not in_range:
+        raise ValueError(f"{name} = {v!r} {why}")
+    if not is_int:
+        raise ValueError(f"{name} = {v!r} is not an integer")
+    if not in_range:
+        raise ValueError(f"{name} = {v} must lie in [{lo}, {hi_text or hi}]" if hi is not None else f"{name} = {v} must be at least {lo}")
+    return int(v)
+
+
+def _check_strokes(strokes, name: str = "strokes"):
+    """The [B,L,3] floating-point rule of every entry that reads existing strokes; returns (B, L)."""
+    if not isinstance(strokes, torch.Tensor) or not strokes.dtype.is_floating_point:
+        raise ValueError(f"{name} must be a floating-point tensor [B,L,3]")
+    if strokes.dim() != 3 or strokes.shape[2] != 3:
+        raise ValueError(f"{name} must be [B,L,3], got {tuple(strokes.shape)}")
+    return int(strokes.shape[0]), int(strokes.shape[1])
 
 
 def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor, L: int | None = None, T: int = 60,
@@ -60,56 +81,28 @@ def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor
     conditioned = known is not None or keep is not None or t_start is not None or cond_noise is not None
     if conditioned:
         t_start = _check_cond(B, L, T, noise, known, keep, t_start, cond_noise)
-    if not hasattr(model, "_validated_text"):
-        model._validated_text = []
-    check_token_ids(text, model._validated_text)   # (once per prompt tensor: the check is a host read)
-    dev = model._device(text, style_vector)
-    h = model._ensure_handle(dev, B, L, Lt, style_vector.shape[1])
-    model._apply_teacher()
-    ret_dev = text.device
-    with torch.cuda.device(dev):
-        t = text.to(dev, torch.int64).contiguous()
-        sv = style_vector.to(dev, torch.float32).contiguous()
-        nz = None
-        if noise is not None:
-            if tuple(noise.shape) != (T + 1, B, L, 2):
-                raise ValueError(f"noise must be [T+1,B,L,2] = {(T + 1, B, L, 2)}")
-            nz = noise.to(dev, torch.float32).contiguous()
-        out = torch.empty((B, L, 3), device=dev, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dev)
-        mode = 0 if diffusion_mode == "new" else 1
+    with model._device_call("sample", text, (text, style_vector), B, L, style_vector.shape[1]) as c:
+        model._apply_teacher()
+        t, sv = c.to(text, torch.int64), c.to(style_vector)
+        if noise is not None and tuple(noise.shape) != (T + 1, B, L, 2):
+            raise ValueError(f"noise must be [T+1,B,L,2] = {(T + 1, B, L, 2)}")
+        nz = c.to(noise)
+        out = c.empty((B, L, 3))
+        head, mode = (t.data_ptr(), sv.data_ptr(), B, L, Lt), 0 if diffusion_mode == "new" else 1
         if conditioned:
-            kn = known.to(dev, torch.float32).contiguous() if known is not None else None
-            kp = keep.to(dev, torch.uint8).contiguous() if keep is not None else None
-            cz = cond_noise.to(dev, torch.float32).contiguous() if cond_noise is not None else None
-            ptr = lambda x: x.data_ptr() if x is not None else None   # noqa: E731
-            _lib.check(_lib.lib().dhw_sample_cond(h, t.data_ptr(), sv.data_ptr(), B, L, Lt, (C.c_int32 * B)(*lens) if lens is not None else None,
-                                                  T, mode, ptr(nz), seed, first_sample, ptr(kn), ptr(kp), t_start, ptr(cz),
-                                                  out.data_ptr(), C.c_void_p(stream.cuda_stream)), h)
-            model._last_sample_inputs = (t, sv, nz, out, kn, kp, cz)
-            return out.to(ret_dev)
-        if lens is None:
-            _lib.check(_lib.lib().dhw_sample(h, t.data_ptr(), sv.data_ptr(), B, L, Lt, T, mode,
-                                             nz.data_ptr() if nz is not None else None, seed, first_sample,
-                                             out.data_ptr(), C.c_void_p(stream.cuda_stream)), h)
+            kn, kp, cz = c.to(known), c.to(keep, torch.uint8), c.to(cond_noise)
+            c.run("dhw_sample_cond", *head, c.lens(lens), T, mode, c.ptr(nz), seed, first_sample, c.ptr(kn), c.ptr(kp), t_start, c.ptr(cz),
+                  out.data_ptr())
+        elif lens is None:
+            c.run("dhw_sample", *head, T, mode, c.ptr(nz), seed, first_sample, out.data_ptr())
         else:
-            _lib.check(_lib.lib().dhw_sample_ragged(h, t.data_ptr(), sv.data_ptr(), B, L, Lt, (C.c_int32 * B)(*lens), T, mode,
-                                                    nz.data_ptr() if nz is not None else None, seed, first_sample,
-                                                    out.data_ptr(), C.c_void_p(stream.cuda_stream)), h)
-        # the library's graph holds raw pointers: pin the inputs to the model so they outlive the launch
-        model._last_sample_inputs = (t, sv, nz, out)
-    return out.to(ret_dev)
+            c.run("dhw_sample_ragged", *head, c.lens(lens), T, mode, c.ptr(nz), seed, first_sample, out.data_ptr())
+    return out.to(text.device)
 
 
 def _check_cond(B: int, L: int, T: int, noise, known, keep, t_start, cond_noise) -> int:
     """The conditioning arguments of ``sample``, checked on the host before any device is touched; returns t_start."""
-    if t_start is None:
-        t_start = T
-    if isinstance(t_start, bool) or not isinstance(t_start, (int, np.integer)):
-        raise ValueError(f"t_start = {t_start!r} is not an integer")
-    t_start = int(t_start)
-    if t_start < 1 or t_start > T:
-        raise ValueError(f"t_start = {t_start} must lie in [1, T = {T}]")
+    t_start = _check_int("t_start", T if t_start is None else t_start, 1, T, hi_text=f"T = {T}")
     if known is not None:
         if not isinstance(known, torch.Tensor) or not known.dtype.is_floating_point:
             raise ValueError("known must be a floating-point tensor [B,L,3]")
@@ -144,8 +137,7 @@ def restyle(strokes: torch.Tensor, text: torch.Tensor, style_vector: torch.Tenso
     [B,L] pins rows exactly; the other keywords are ``sample``'s (T, diffusion_mode, seed, ...).  Returns [B,L,3]."""
     if not 0.0 <= float(strength) <= 1.0:
         raise ValueError(f"strength = {strength!r} must lie in [0, 1]")
-    if strokes.dim() != 3 or strokes.shape[2] != 3:
-        raise ValueError(f"strokes must be [B,L,3], got {tuple(strokes.shape)}")
+    _check_strokes(strokes)
     T = int(sample_kwargs.pop("T", 60))
     t_start = min(T, max(1, int(round(float(strength) * T))))
     return sample(model, text, style_vector, L=int(strokes.shape[1]), T=T, lengths=lengths, known=strokes, keep=keep, t_start=t_start,
@@ -173,8 +165,7 @@ def default_levels(T: int = 60) -> list:
 
 
 def _check_levels(levels, T: int) -> list:
-    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 1:
-        raise ValueError(f"T = {T!r} must be a positive integer")
+    _check_int("T", T, 1, why="must be a positive integer")
     if levels is None:
         return default_levels(T)
     if isinstance(levels, torch.Tensor):
@@ -188,9 +179,7 @@ def _check_levels(levels, T: int) -> list:
     if len(seq) > T:
         raise ValueError(f"levels has {len(seq)} entries, more than T = {T}")
     for k, v in enumerate(seq):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"levels[{k}] = {v!r} is not an integer")
-        if v < 0 or v >= T:
+        if _check_int(f"levels[{k}]", v) < 0 or v >= T:
             raise ValueError(f"levels[{k}] = {v} must lie in [0, T = {T})")
     return [int(v) for v in seq]
 
@@ -206,11 +195,7 @@ def score(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, styl
     ``default_levels(T)``.  ``noise`` f32 [K,B,L,2]: the perturbing draws; without it the generator draws them keyed by
     (seed, first_sample + b, position, level), so a level's score depends neither on the other levels nor on sharding.
     ``pen_round``: score against ``torch.round(pen)`` (half to even, the renderer's reading of a sampled pen value)."""
-    if not isinstance(strokes, torch.Tensor) or not strokes.dtype.is_floating_point:
-        raise ValueError("strokes must be a floating-point tensor [B,L,3]")
-    if strokes.dim() != 3 or strokes.shape[2] != 3:
-        raise ValueError(f"strokes must be [B,L,3], got {tuple(strokes.shape)}")
-    B, L, _ = strokes.shape
+    B, L = _check_strokes(strokes)
     if text.dim() != 2 or text.shape[0] != B:
         raise ValueError(f"text must be [B = {B}, Lt], got {tuple(text.shape)}")
     if L < 8 or L % 8:
@@ -223,39 +208,17 @@ def score(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, styl
             raise ValueError("noise must be a floating-point tensor [K,B,L,2]")
         if tuple(noise.shape) != (K, B, L, 2):
             raise ValueError(f"noise must be [K,B,L,2] = {(K, B, L, 2)}, got {tuple(noise.shape)}")
-    if not hasattr(model, "_validated_text"):
-        model._validated_text = []
-    check_token_ids(text, model._validated_text)
-    dev = model._device(strokes, text, style_vector)
-    h = model._ensure_handle(dev, B, L, Lt, style_vector.shape[1])
-    ret_dev = strokes.device
-    with torch.cuda.device(dev):
-        s = strokes.to(dev, torch.float32)
-        if pen_round:
-            s = torch.cat((s[..., :2], torch.round(s[..., 2:])), dim=2)
-        s = s.contiguous()
-        t = text.to(dev, torch.int64).contiguous()
-        sv = style_vector.to(dev, torch.float32).contiguous()
-        nz = noise.to(dev, torch.float32).contiguous() if noise is not None else None
-        out = torch.empty((K, B, 2), device=dev, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dev)
-        _lib.check(_lib.lib().dhw_score(h, s.data_ptr(), t.data_ptr(), sv.data_ptr(), B, L, Lt, (C.c_int32 * B)(*lens) if lens is not None else None,
-                                        T, (C.c_int32 * K)(*lv), K, nz.data_ptr() if nz is not None else None, seed, first_sample,
-                                        out.data_ptr(), C.c_void_p(stream.cuda_stream)), h)
-        # the launches read the inputs in place: pin them to the model so they outlive the stream's work
-        model._last_score_inputs = (s, t, sv, nz, out)
-    return out.transpose(0, 1).to(ret_dev)
+    with model._device_call("score", text, (strokes, text, style_vector), B, L, style_vector.shape[1]) as c:
+        s = strokes.to(c.dev, torch.float32)
+        s = c.to(torch.cat((s[..., :2], torch.round(s[..., 2:])), dim=2) if pen_round else s)
+        t, sv, nz = c.to(text, torch.int64), c.to(style_vector), c.to(noise)
+        out = c.empty((K, B, 2))
+        c.run("dhw_score", s.data_ptr(), t.data_ptr(), sv.data_ptr(), B, L, Lt, c.lens(lens), T, c.lens(lv), K, c.ptr(nz), seed, first_sample,
+              out.data_ptr())
+    return out.transpose(0, 1).to(strokes.device)
 
 
 # ---------------------------------------------------------------- deterministic sampling and inversion (include/dhw.h dhw_ddim_*)
-def _check_int(name: str, v, lo: int, hi: int | None = None) -> int:
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name} = {v!r} is not an integer")
-    if v < lo or (hi is not None and v > hi):
-        raise ValueError(f"{name} = {v} must lie in [{lo}, {hi}]" if hi is not None else f"{name} = {v} must be at least {lo}")
-    return int(v)
-
-
 def ddim_levels(T: int = 60, steps: int | None = None) -> list:
     """The schedule indices ``sample_ddim`` / ``invert`` visit: ``steps`` of them (default T), from T-1 down to 0, evenly
     spread: ``levels[j] = ((steps-1-j) * (T-1)) // (steps-1)``; a single step is ``[T-1]``.  60, 4 -> [59, 39, 19, 0]."""
@@ -317,27 +280,13 @@ def sample_ddim(model: DiffusionModel, text: torch.Tensor, style_vector: torch.T
         raise ValueError(f"L = {L} must be a multiple of 8")
     lv = _check_ddim_levels(levels, steps, T)
     seed, first_sample = _check_int("seed", seed, 0, 2 ** 64 - 1), _check_int("first_sample", first_sample, -2 ** 63, 2 ** 63 - 1)
-    if not hasattr(model, "_validated_text"):
-        model._validated_text = []
-    check_token_ids(text, model._validated_text)
-    dev = model._device(text, style_vector) if latent is None else model._device(text, style_vector, latent)
-    h = model._ensure_handle(dev, B, L, Lt, style_vector.shape[1])
-    ret_dev = text.device
-    with torch.cuda.device(dev):
-        t = text.to(dev, torch.int64).contiguous()
-        sv = style_vector.to(dev, torch.float32).contiguous()
-        lat = latent.to(dev, torch.float32).contiguous() if latent is not None else None
-        lat_out = torch.empty((B, L, 2), device=dev, dtype=torch.float32) if return_latent else None
-        out = torch.empty((B, L, 3), device=dev, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dev)
-        S = len(lv)
-        _lib.check(_lib.lib().dhw_ddim_sample(h, t.data_ptr(), sv.data_ptr(), B, L, Lt, (C.c_int32 * B)(*lens) if lens is not None else None,
-                                              T, (C.c_int32 * S)(*lv), S, lat.data_ptr() if lat is not None else None, seed, first_sample,
-                                              lat_out.data_ptr() if lat_out is not None else None, out.data_ptr(),
-                                              C.c_void_p(stream.cuda_stream)), h)
-        # the launches read the inputs in place: pin them to the model so they outlive the stream's work
-        model._last_ddim_inputs = (t, sv, lat, lat_out, out)
-    return (out.to(ret_dev), lat_out.to(ret_dev)) if return_latent else out.to(ret_dev)
+    tensors = (text, style_vector) if latent is None else (text, style_vector, latent)
+    with model._device_call("ddim", text, tensors, B, L, style_vector.shape[1]) as c:
+        t, sv, lat = c.to(text, torch.int64), c.to(style_vector), c.to(latent)
+        lat_out, out = c.empty((B, L, 2), wanted=return_latent), c.empty((B, L, 3))
+        c.run("dhw_ddim_sample", t.data_ptr(), sv.data_ptr(), B, L, Lt, c.lens(lens), T, c.lens(lv), len(lv), c.ptr(lat), seed, first_sample,
+              c.ptr(lat_out), out.data_ptr())
+    return (out.to(text.device), lat_out.to(text.device)) if return_latent else out.to(text.device)
 
 
 def invert(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, style_vector: torch.Tensor, lengths=None, T: int = 60,
@@ -348,34 +297,18 @@ def invert(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, sty
     under another style or text it rewrites the line reproducibly (``transfer``).  ``iters`` in [1, 8]: fixed-point
     iterations per step (1 = the usual DDIM inversion); the call makes ``len(levels) * iters`` denoiser calls.
     Returns the latent [B,L,2], 0 past ``lengths[b]``."""
-    if not isinstance(strokes, torch.Tensor) or not strokes.dtype.is_floating_point:
-        raise ValueError("strokes must be a floating-point tensor [B,L,3]")
-    if strokes.dim() != 3 or strokes.shape[2] != 3:
-        raise ValueError(f"strokes must be [B,L,3], got {tuple(strokes.shape)}")
-    B, L, _ = strokes.shape
+    B, L = _check_strokes(strokes)
     if L < 8 or L % 8:
         raise ValueError(f"strokes: L = {L} must be a multiple of 8, at least 8")
     lens = _check_ddim_common(text, style_vector, B, lengths, L)
     lv = _check_ddim_levels(levels, steps, T)
     iters = _check_int("iters", iters, 1, 8)
     Lt = text.shape[1]
-    if not hasattr(model, "_validated_text"):
-        model._validated_text = []
-    check_token_ids(text, model._validated_text)
-    dev = model._device(strokes, text, style_vector)
-    h = model._ensure_handle(dev, B, L, Lt, style_vector.shape[1])
-    ret_dev = strokes.device
-    with torch.cuda.device(dev):
-        s = strokes.to(dev, torch.float32).contiguous()
-        t = text.to(dev, torch.int64).contiguous()
-        sv = style_vector.to(dev, torch.float32).contiguous()
-        out = torch.empty((B, L, 2), device=dev, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dev)
-        S = len(lv)
-        _lib.check(_lib.lib().dhw_ddim_invert(h, s.data_ptr(), t.data_ptr(), sv.data_ptr(), B, L, Lt, (C.c_int32 * B)(*lens) if lens is not None else None,
-                                              T, (C.c_int32 * S)(*lv), S, iters, out.data_ptr(), C.c_void_p(stream.cuda_stream)), h)
-        model._last_ddim_inputs = (s, t, sv, out)
-    return out.to(ret_dev)
+    with model._device_call("ddim", text, (strokes, text, style_vector), B, L, style_vector.shape[1]) as c:
+        s, t, sv = c.to(strokes), c.to(text, torch.int64), c.to(style_vector)
+        out = c.empty((B, L, 2))
+        c.run("dhw_ddim_invert", s.data_ptr(), t.data_ptr(), sv.data_ptr(), B, L, Lt, c.lens(lens), T, c.lens(lv), len(lv), iters, out.data_ptr())
+    return out.to(strokes.device)
 
 
 def transfer(strokes: torch.Tensor, text: torch.Tensor, style_from: torch.Tensor, style_to: torch.Tensor, model: DiffusionModel,
@@ -487,17 +420,11 @@ def align(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, styl
     """Where in a line each character sits: the attention map of ``strokes`` [B,L,3] (a sampled line, or pen data) under
     their ``text``.  The denoiser runs once on ``strokes[..., :2]`` as given — no noise is added — at
     ``sigma = sqrt(abar[level])`` of the T-step schedule (level 0: the nearly clean end).  Returns an ``Alignment``."""
-    if not isinstance(strokes, torch.Tensor) or not strokes.dtype.is_floating_point:
-        raise ValueError("strokes must be a floating-point tensor [B,L,3]")
-    if strokes.dim() != 3 or strokes.shape[2] != 3:
-        raise ValueError(f"strokes must be [B,L,3], got {tuple(strokes.shape)}")
-    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 1:
-        raise ValueError(f"T = {T!r} must be a positive integer")
-    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level < 0 or level >= T:
-        raise ValueError(f"level = {level!r} must be an integer in [0, T = {T})")
-    B, L, _ = strokes.shape
+    B, L = _check_strokes(strokes)
+    T = _check_int("T", T, 1, why="must be a positive integer")
+    level = _check_int("level", level, 0, T - 1, why=f"must be an integer in [0, T = {T})")
     xy = strokes[..., :2]
-    sigma = torch.full((B,), float(np.sqrt(_lib.schedule(int(T))[1][int(level)])), dtype=torch.float32)
+    sigma = torch.full((B,), float(np.sqrt(_lib.schedule(T)[1][level])), dtype=torch.float32)
     lens, li = _check_attention_args(model, xy, text, sigma, style_vector, lengths, layer)
     ret_dev = strokes.device
     _, _, _, mean, token = model._attention_call(xy, text, sigma, style_vector, lens, li, False, True, True)
@@ -524,8 +451,7 @@ def rewrite_mask(alignment: Alignment, tok_lo, tok_hi) -> torch.Tensor:
         if len(seq) != B:
             raise ValueError(f"{name} has {len(seq)} entries, the batch {B}")
         for i, x in enumerate(seq):
-            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
-                raise ValueError(f"{name}[{i}] = {x!r} is not an integer")
+            _check_int(f"{name}[{i}]", x)
         return torch.tensor([int(x) for x in seq], dtype=torch.int64, device=token.device)[:, None]
 
     lo, hi = per_prompt(tok_lo, "tok_lo"), per_prompt(tok_hi, "tok_hi")
@@ -545,14 +471,8 @@ def align_file(prompts, strokes_path, source, config_path: str | None = None, ch
     """``infer.py --align``: the lines of ``prompts`` as an earlier run wrote them (``strokes_path``: the .npy of ``infer.py
     --save-strokes``) aligned to their text by one ``align`` call.  Returns (the Alignment on the host, the prompts' token
     id lists, the stroke lengths)."""
-    from .checkpoint import load_model
-
-    prompts = list(prompts)
-    config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
-    style = load_style(source, style_weights)
-    text, lens, sv = _encode_batch("align_file", prompts, style)
-    old = _load_strokes(strokes_path, lens)
-    model = load_model(config_path, checkpoint_path, precision=precision, max_B=len(lens), style_rows=style.shape[1])
+    model, old, text, sv, lens = _open_lines("align_file", prompts, strokes_path, source, config_path, checkpoint_path, experiment_path, precision,
+                                             style_weights)
     al = align(model, old, text, sv, lengths=lens, level=level, layer=layer)
     al.mean, al.token = al.mean.detach().cpu(), al.token.detach().cpu()
     return al, [[int(v) for v in row if int(v) != 0] for row in text.cpu().tolist()], lens
@@ -633,9 +553,7 @@ def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diff
 
 
 def _check_candidates(candidates) -> int:
-    if isinstance(candidates, bool) or not isinstance(candidates, (int, np.integer)) or candidates < 1:
-        raise ValueError(f"candidates = {candidates!r} must be an integer >= 1")
-    return int(candidates)
+    return _check_int("candidates", candidates, 1, why="must be an integer >= 1")
 
 
 def remove_whitespace(img: np.ndarray, thresh: float) -> np.ndarray:
@@ -727,32 +645,20 @@ def infer_file(prompt: str, source, config_path: str | None = None, checkpoint_p
     "matplotlib" = the reference's figure, "gpu" = the 96-row grey line image of ``render_strokes``).
     ``candidates = N > 1``: the best of N samples by ``score`` (``infer_batch``).  ``steps``: deterministic sampling at that
     many levels (``sample_ddim``).  Returns the [L,3] strokes."""
-    from .checkpoint import find_checkpoint, load_model
-    from .vis import render_lines_png, show_strokes
+    from .checkpoint import load_model
 
     _check_renderer(renderer)
     candidates = _check_candidates(candidates)
     ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}   # (no steps: today's calls, argument for argument)
-
-    if experiment_path:
-        from pathlib import Path
-        if not config_path:
-            config_path = str(Path(experiment_path) / "config.yml")
-        if not checkpoint_path:
-            ckpt = find_checkpoint(experiment_path)
-            checkpoint_path = str(ckpt) if ckpt else None
-    if not config_path or not checkpoint_path:
-        raise ValueError("Both config_path and checkpoint_path must be provided, either directly or via experiment_path.")
+    config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
     model = load_model(config_path, checkpoint_path, precision=precision, max_B=_rounds_capacity(1, candidates), style_rows=style.shape[1])
     if candidates > 1:
         (strokes,) = infer_batch([prompt], style, model, diffusion_mode=diffusion_mode, seed=seed, candidates=candidates, **ddim)
     else:
         strokes = infer(prompt, style, model, diffusion_mode=diffusion_mode, seed=seed, **ddim)
-    if render and renderer == "gpu":
-        render_lines_png([strokes], [output])
-    elif render:
-        show_strokes(strokes, scale=1, name=output, show_output=False)
+    if render:
+        _save_lines([strokes], [output], renderer)
     return strokes
 
 
@@ -775,6 +681,28 @@ def _resolve_experiment(config_path, checkpoint_path, experiment_path):
     return config_path, checkpoint_path
 
 
+def _save_lines(strokes, names, renderer: str) -> None:
+    """``./<name>.png`` per line: "gpu" rasterises every line in one ``render_strokes`` call, "matplotlib" draws the reference's figure."""
+    from .vis import render_lines_png, show_strokes
+    if renderer == "gpu":
+        render_lines_png(strokes, names)
+    else:
+        for s, name in zip(strokes, names):
+            show_strokes(s, scale=1, name=name, show_output=False)
+
+
+def _open_lines(who: str, prompts, strokes_path, source, config_path, checkpoint_path, experiment_path, precision, style_weights):
+    """What the front ends that read back saved lines open with -> (model sized for the batch, strokes [B, max L_i, 3], text, style
+    [B,S,1280], stroke lengths)."""
+    from .checkpoint import load_model
+    config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
+    style = load_style(source, style_weights)
+    text, lens, sv = _encode_batch(who, list(prompts), style)
+    old = _load_strokes(strokes_path, lens)
+    model = load_model(config_path, checkpoint_path, precision=precision, max_B=len(lens), style_rows=style.shape[1])
+    return model, old, text, sv, lens
+
+
 def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint_path: str | None = None,
                      experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
                      precision: str = "bf16", seed: int = 0, render: bool = True, style_weights: str | None = None,
@@ -784,7 +712,6 @@ def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint
     the best of N samples by ``score``.  ``steps``: deterministic sampling at that many levels (``sample_ddim``).  Returns the
     list of [L_i, 3] strokes."""
     from .checkpoint import load_model
-    from .vis import render_lines_png, show_strokes
 
     _check_renderer(renderer)
     candidates = _check_candidates(candidates)
@@ -795,11 +722,8 @@ def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint
     model = load_model(config_path, checkpoint_path, precision=precision, max_B=_rounds_capacity(max(1, len(prompts)), candidates),
                        style_rows=style.shape[1])
     strokes = infer_batch(prompts, style, model, diffusion_mode=diffusion_mode, seed=seed, candidates=candidates, **ddim)
-    if render and renderer == "gpu":
-        render_lines_png(strokes, [f"{output}_{i}" for i in range(len(strokes))])
-    elif render:
-        for i, s in enumerate(strokes):
-            show_strokes(s, scale=1, name=f"{output}_{i}", show_output=False)
+    if render:
+        _save_lines(strokes, [f"{output}_{i}" for i in range(len(strokes))], renderer)
     return strokes
 
 
@@ -933,14 +857,8 @@ def score_file(prompts, strokes_path, source, config_path: str | None = None, ch
     """``infer.py --score``: the lines of ``prompts`` as an earlier run wrote them (``strokes_path``: the .npy of ``infer.py
     --save-strokes``) scored against their text and the hand of ``source`` by one ``score(..., pen_round=True)`` call at the
     default levels.  Returns one ``(L_i, score term, pen term, total)`` per line, each averaged over the levels."""
-    from .checkpoint import load_model
-
-    prompts = list(prompts)
-    config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
-    style = load_style(source, style_weights)
-    text, lens, sv = _encode_batch("score_file", prompts, style)
-    old = _load_strokes(strokes_path, lens)
-    model = load_model(config_path, checkpoint_path, precision=precision, max_B=len(lens), style_rows=style.shape[1])
+    model, old, text, sv, lens = _open_lines("score_file", prompts, strokes_path, source, config_path, checkpoint_path, experiment_path, precision,
+                                             style_weights)
     sc = score(model, old, text, sv, lengths=lens, seed=seed, pen_round=True).mean(dim=1).detach().cpu().tolist()
     return [(lens[b], sc[b][0], sc[b][1], sc[b][0] + sc[b][1]) for b in range(len(lens))]
 
@@ -952,21 +870,11 @@ def restyle_file(prompts, strokes_path, source, config_path: str | None = None, 
     """``infer.py --restyle``: the lines of ``prompts`` as an earlier run wrote them (``strokes_path``: the .npy of ``infer.py
     --save-strokes``, [B, >= max L_i, 3]) rewritten in the hand of ``source`` by one ``restyle`` call; ``./<output>_<i>.png``
     per line.  Returns the list of [L_i, 3] strokes."""
-    from .checkpoint import load_model
-    from .vis import render_lines_png, show_strokes
-
     _check_renderer(renderer)
-    prompts = list(prompts)
-    config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
-    style = load_style(source, style_weights)
-    text, lens, sv = _encode_batch("restyle_file", prompts, style)
-    old = _load_strokes(strokes_path, lens)
-    model = load_model(config_path, checkpoint_path, precision=precision, max_B=len(lens), style_rows=style.shape[1])
+    model, old, text, sv, lens = _open_lines("restyle_file", prompts, strokes_path, source, config_path, checkpoint_path, experiment_path, precision,
+                                             style_weights)
     out = restyle(old, text, sv, model, lengths=lens, strength=strength, diffusion_mode=diffusion_mode, seed=seed).detach().cpu().numpy()
     strokes = [out[b, :lens[b]].copy() for b in range(len(lens))]
-    if render and renderer == "gpu":
-        render_lines_png(strokes, [f"{output}_{i}" for i in range(len(strokes))])
-    elif render:
-        for i, s_ in enumerate(strokes):
-            show_strokes(s_, scale=1, name=f"{output}_{i}", show_output=False)
+    if render:
+        _save_lines(strokes, [f"{output}_{i}" for i in range(len(strokes))], renderer)
     return strokes

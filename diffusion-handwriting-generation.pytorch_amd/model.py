@@ -10,6 +10,7 @@ buffers and the stream.  There is no CPU fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 
@@ -145,6 +146,41 @@ class _DifferentiableForward(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(tm.p[k].g.clone() for k in tm.names)
 
 
+class _DeviceCall:
+    """The device side of one library call (``DiffusionModel._device_call``): the conversions every entry needs, and the
+    tensors the call hands to the library, kept so that they outlive the stream's work."""
+
+    def __init__(self, dev: torch.device, handle):
+        self.dev, self.h = dev, handle
+        self.stream = torch.cuda.current_stream(dev)
+        self.inputs, self.outputs = [], []
+
+    def to(self, x, dtype=torch.float32):
+        """``x`` (or None) as a contiguous tensor of ``dtype`` on the call's device."""
+        if x is not None:
+            x = x.to(self.dev, dtype).contiguous()
+            self.inputs.append(x)
+        return x
+
+    def empty(self, shape, dtype=torch.float32, wanted: bool = True):
+        if not wanted:
+            return None
+        self.outputs.append(torch.empty(shape, device=self.dev, dtype=dtype))
+        return self.outputs[-1]
+
+    @staticmethod
+    def ptr(x):
+        return x.data_ptr() if x is not None else None
+
+    @staticmethod
+    def lens(lens):
+        return (C.c_int32 * len(lens))(*lens) if lens is not None else None
+
+    def run(self, entry: str, *args):
+        """``entry(handle, *args, stream)``: every denoiser entry of include/dhw.h opens with the handle and ends with the stream."""
+        _lib.check(getattr(_lib.lib(), entry)(self.h, *args, C.c_void_p(self.stream.cuda_stream)), self.h)
+
+
 def _torch_dtype_code(t: torch.Tensor) -> int:
     return {torch.float32: _lib.DHW_F32, torch.bfloat16: _lib.DHW_BF16, torch.float16: _lib.DHW_F16,
             torch.float64: _lib.DHW_F64}[t.dtype]
@@ -167,6 +203,7 @@ class DiffusionModel(nn.Module):
         self._wtoken = None
         self._trainer = None          # train_model.TrainModel behind the differentiable forward (created on first use)
         self._train_generation = 0
+        self._pinned = {}             # per entry: the tensors its last library call reads or writes (_device_call)
         for name, shape, kind in param_spec(num_layers, c1, c2, c3):
             node = self
             parts = name.split(".")
@@ -229,6 +266,29 @@ class DiffusionModel(nn.Module):
             self._push_weights()
             self._wtoken = token
         return self._handle
+
+    @contextlib.contextmanager
+    def _device_call(self, slot: str | None, text: torch.Tensor, tensors, B: int, L: int, S: int, seen: bool = True):
+        """The one path from checked arguments to the library: validate the token ids (``seen``: through the model's cache of
+        validated prompt tensors; ``forward`` and the attention call read them every time, as ``check_token_ids`` promises), pick
+        the device (the first CUDA tensor of ``tensors`` decides), make sure the handle fits, enter the device and yield a
+        ``_DeviceCall``.  The library reads its inputs in place and ``sample``'s graph holds raw pointers, so after the call its
+        tensors stay referenced in ``self._pinned[slot]`` until the next call of the same slot (one slot per entry: a score call
+        must not release what a sampler graph on another stream may still read); ``slot=None`` marks the inputs as in use by
+        the stream instead (``record_stream``)."""
+        if seen and not hasattr(self, "_validated_text"):
+            self._validated_text = []
+        check_token_ids(text, self._validated_text if seen else None)   # (cached: once per prompt tensor, the check is a host read)
+        dev = self._device(*tensors)
+        h = self._ensure_handle(dev, B, L, text.shape[1], S)
+        with torch.cuda.device(dev):
+            call = _DeviceCall(dev, h)
+            yield call
+            if slot is None:
+                for x in call.inputs:
+                    x.record_stream(call.stream)
+            else:
+                self._pinned[slot] = tuple(call.inputs + call.outputs)
 
     def _push_weights(self):
         l = _lib.lib()
@@ -324,27 +384,15 @@ class DiffusionModel(nn.Module):
             raise ValueError("style_vector must be [B, S, 1280]")
         if sigma.numel() != B:
             raise ValueError("sigma must hold one value per sample ([B,1] or [B,1,1])")
-        check_token_ids(text)
         ret_dev = strokes.device
-        dev = self._device(strokes, text, sigma, style_vector)
-        h = self._ensure_handle(dev, B, L, text.shape[1], style_vector.shape[1])
-        with torch.cuda.device(dev):
-            s = strokes.to(dev, torch.float32).contiguous()
-            t = text.to(dev, torch.int64).contiguous()
-            sg = sigma.to(dev, torch.float32).reshape(B).contiguous()
-            sv = style_vector.to(dev, torch.float32).contiguous()
-            eps = torch.empty((B, L, 2), device=dev, dtype=torch.float32)
-            pen = torch.empty((B, L), device=dev, dtype=torch.float32)
-            st = torch.cuda.current_stream(dev).cuda_stream
+        with self._device_call(None, text, (strokes, text, sigma, style_vector), B, L, style_vector.shape[1], seen=False) as c:
+            s, t, sg, sv = c.to(strokes), c.to(text, torch.int64), c.to(sigma.reshape(B)), c.to(style_vector)
+            eps, pen = c.empty((B, L, 2)), c.empty((B, L))
+            head = (s.data_ptr(), t.data_ptr(), sg.data_ptr(), sv.data_ptr(), B, L, t.shape[1])
             if lengths is None:
-                _lib.check(_lib.lib().dhw_forward(h, s.data_ptr(), t.data_ptr(), sg.data_ptr(), sv.data_ptr(), B, L,
-                                                  t.shape[1], eps.data_ptr(), pen.data_ptr(), C.c_void_p(st)), h)
+                c.run("dhw_forward", *head, eps.data_ptr(), pen.data_ptr())
             else:
-                _lib.check(_lib.lib().dhw_forward_ragged(h, s.data_ptr(), t.data_ptr(), sg.data_ptr(), sv.data_ptr(), B, L, t.shape[1],
-                                                         (C.c_int32 * B)(*lens), eps.data_ptr(), pen.data_ptr(), C.c_void_p(st)), h)
-            # keep the inputs alive until the stream has consumed them
-            for x in (s, t, sg, sv):
-                x.record_stream(torch.cuda.current_stream(dev))
+                c.run("dhw_forward_ragged", *head, c.lens(lens), eps.data_ptr(), pen.data_ptr())
         return eps.to(ret_dev), pen.to(ret_dev), None
 
     # ------------------------------------------------------------------ attention maps (include/dhw.h dhw_attention)
@@ -367,31 +415,17 @@ class DiffusionModel(nn.Module):
         """One dhw_attention call on checked ``lens`` (list or None) and ``layer`` (library index); returns the device tensors
         (eps, pen, probs, mean, token), None for an output that was not asked for."""
         B, L = self._check_forward_inputs(strokes, text, sigma, style_vector)
-        check_token_ids(text)
-        dev = self._device(strokes, text, sigma, style_vector)
         Lt = text.shape[1]
-        h = self._ensure_handle(dev, B, L, Lt, style_vector.shape[1])
-        l = _lib.lib()
-        H, Lq = C.c_int(), C.c_int()
-        _lib.check(l.dhw_attention_shape(h, layer, L, C.byref(H), C.byref(Lq)), h)
-        H, Lq = H.value, Lq.value
-        with torch.cuda.device(dev):
-            s = strokes.to(dev, torch.float32).contiguous()
-            t = text.to(dev, torch.int64).contiguous()
-            sg = sigma.to(dev, torch.float32).reshape(B).contiguous()
-            sv = style_vector.to(dev, torch.float32).contiguous()
-            eps = torch.empty((B, L, 2), device=dev, dtype=torch.float32)
-            pen = torch.empty((B, L), device=dev, dtype=torch.float32)
-            probs = torch.empty((B, H, Lq, Lt), device=dev, dtype=torch.float32) if want_probs else None
-            mean = torch.empty((B, Lq, Lt), device=dev, dtype=torch.float32) if want_mean else None
-            token = torch.empty((B, Lq), device=dev, dtype=torch.int32) if want_token else None
-            ptr = lambda x: x.data_ptr() if x is not None else None   # noqa: E731
-            st = torch.cuda.current_stream(dev)
-            _lib.check(l.dhw_attention(h, s.data_ptr(), t.data_ptr(), sg.data_ptr(), sv.data_ptr(), B, L, Lt,
-                                       (C.c_int32 * B)(*lens) if lens is not None else None, layer, ptr(probs), ptr(mean), ptr(token),
-                                       eps.data_ptr(), pen.data_ptr(), C.c_void_p(st.cuda_stream)), h)
-            # the launches read the inputs in place: pin them to the model so they outlive the stream's work
-            self._last_attention_inputs = (s, t, sg, sv, eps, pen, probs, mean, token)
+        with self._device_call("attention", text, (strokes, text, sigma, style_vector), B, L, style_vector.shape[1], seen=False) as c:
+            H, Lq = C.c_int(), C.c_int()
+            _lib.check(_lib.lib().dhw_attention_shape(c.h, layer, L, C.byref(H), C.byref(Lq)), c.h)
+            H, Lq = H.value, Lq.value
+            s, t, sg, sv = c.to(strokes), c.to(text, torch.int64), c.to(sigma.reshape(B)), c.to(style_vector)
+            eps, pen = c.empty((B, L, 2)), c.empty((B, L))
+            probs, mean = c.empty((B, H, Lq, Lt), wanted=want_probs), c.empty((B, Lq, Lt), wanted=want_mean)
+            token = c.empty((B, Lq), torch.int32, wanted=want_token)
+            c.run("dhw_attention", s.data_ptr(), t.data_ptr(), sg.data_ptr(), sv.data_ptr(), B, L, Lt, c.lens(lens), layer, c.ptr(probs),
+                  c.ptr(mean), c.ptr(token), eps.data_ptr(), pen.data_ptr())
         return eps, pen, probs, mean, token
 
     # ------------------------------------------------------------------ test / measurement hooks (include/dhw_debug.h)
