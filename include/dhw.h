@@ -373,6 +373,49 @@ int dhw_page(const float* strokes,      /* device f32 [N,L,3]                   
              float* boxes_out,          /* device f32 [N,4]                                               */
              void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Stroke encoder: raw pen trajectories (tablet points grouped into pen-down strokes, the IAM-OnDB lineStrokes data) -> the
+ * model's (dx, dy, pen) rows, normalised and thinned as the reference's parse_strokes_xml + combine_strokes + pad_stroke_seq
+ * prepare the training corpus.  No handle: errors are read through dhw_last_error(NULL).  The call allocates nothing,
+ * synchronises nothing, makes no host read of counts and can be captured into a graph.  All argument checks run before the
+ * first HIP call (DHW_ERR_ARG names the argument): 1 <= B <= 65535, 2 <= N <= 4096, 8 <= L <= 4096, 0 <= rounds <= 8,
+ * max_abs > 0 and finite, non-NULL points / strokes_out / lens_out / status_out, points / strokes_out / workspace 16-byte
+ * aligned, workspace_bytes >= dhw_encode_workspace_bytes(B, N).  A line of 4096 points stays in LDS, so the workspace size
+ * is 0 at every shape today (and for a B or N outside the ranges) and workspace may then be NULL; the argument is there so
+ * that a later layout can spill without a change of the ABI.
+ *
+ * Line b, with n = counts[b] (N when counts is NULL) points (x, y, end)[i], i < n; y grows DOWNWARD (tablet / IAM), end != 0
+ * marks the last point of a pen-down stroke.  Points at or past n are never read.  All arithmetic is fp64 on values
+ * converted from the f32 input, without fused multiply-add:
+ *    1. Row i, 0 <= i < M with M = n - 1: d[i] = (x[i+1] - x[i], -(y[i+1] - y[i])), e[i] = (end[i+1] != 0).
+ *    2. The pen column is e rolled by one: pen[0] = e[M-1], pen[i] = e[i-1] (the reference's convention: a 1 means the move
+ *       TO this row is a jump).  The caller makes sure the last point of a line is marked as an end.
+ *    3. Normalise: divide every dx and dy by s, the population standard deviation (ddof 0) of the 2M values dx and dy taken as
+ *       ONE set, in two passes (the mean, then the mean squared deviation), each summed in a fixed tree; no float atomics.
+ *    4. `rounds` times, with M the current row count: k = M / 5 (integer division; equal to the reference's int(M * 0.2) for
+ *       every M <= 4096).  The pairs are (2j, 2j+1) for j < M / 2; an odd last row has no partner.
+ *       v_j = |d[2j]| + |d[2j+1]| - |d[2j] + d[2j+1]| (Euclidean norms, sqrt(x x + y y)).  The k pairs that are smallest under
+ *       the order (v_j, j) merge: on equal v the lower j goes first (the reference's argsort leaves ties at the cut
+ *       unspecified).  A merged pair: d[2j] += d[2j+1], pen[2j] = (pen[2j] + pen[2j+1] > 0), row 2j+1 is deleted.  Unmerged
+ *       rows keep their pen value.  After the deletions, rule 3 again on the new set.
+ *    5. lens_out[b] = the final M (a function of n and rounds alone).
+ *    6. status_out[b] is a bit set: 1: n < 2 or n > N.  2: a non-finite input among the n points, or a std that is 0 or
+ *       non-finite at any normalisation (the values mean nothing from there on: the remaining rounds only shrink M, and
+ *       bit 8 is not looked at).  4: final M > L.  8: max(|dx|, |dy|) over the final rows > max_abs (the reference's
+ *       pad_stroke_seq uses 15).
+ *    7. Status 0: rows i < M of strokes_out[b] are the f32 roundings of (dx, dy, pen); rows M <= i < L are (0, 0, 1), the
+ *       reference's padding.
+ *    8. Status non-zero: all L rows are (0, 0, 1) (the reference drops such a line); with bit 1 set lens_out[b] = 0 and no
+ *       other bit is set.
+ *    9. Row b of a batch equals the same line encoded alone, bit for bit, for any B, N and L that admit it. */
+size_t dhw_encode_workspace_bytes(int B, int N);
+int dhw_encode(const float* points,      /* device f32 [B,N,3] = (x, y, end)                     */
+               const int32_t* counts,    /* DEVICE int32 [B] or NULL (every line has N points)   */
+               int B, int N, int L, int rounds, float max_abs,
+               float* strokes_out,       /* device f32 [B,L,3]                                   */
+               int32_t* lens_out,        /* device [B]                                           */
+               int32_t* status_out,      /* device [B]                                           */
+               void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Host-only: beta_i = 0.02 + exp(linspace(ln 1e-5, ln 0.4, T)), abar = cumprod(1-beta), fp32. */
 int dhw_schedule(int T, float* beta_out, float* alpha_bar_out);
 
