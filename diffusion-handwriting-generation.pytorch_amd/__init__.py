@@ -5,6 +5,7 @@ from .checkpoint import find_checkpoint, load_model, read_config, read_state_dic
 from .inference import Alignment, align, align_file, attention, ddim_levels, default_levels, get_alpha_set, get_beta_set, infer, infer_batch, infer_file, infer_file_batch, invert, load_style, pad_strokes, read_img, remove_whitespace, restyle, restyle_file, rewrite_mask, sample, sample_ddim, score, score_file, slerp, token_spans, transfer, wrap_text, write_page, write_page_file  # noqa: F401
 from .vis import render_page, render_strokes, save_line_png, save_page_png, show_strokes, strokes_to_polylines  # noqa: F401
 from .encode import encode_strokes, make_batches, padded_lengths, read_strokes_xml  # noqa: F401
+from .imgprep import load_styles, prepare_images  # noqa: F401
 from .model import DiffusionModel, DiffusionWriter  # noqa: F401
 from .style_extractor import StyleExtractor  # noqa: F401
 from .tokenizer import Tokenizer, stroke_length  # noqa: F401

@@ -416,6 +416,54 @@ int dhw_encode(const float* points,      /* device f32 [B,N,3] = (x, y, end)    
                int32_t* status_out,      /* device [B]                                           */
                void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Writer-image preparation: B grey images of different sizes -> one f32 [B,1,H,W] batch that dhw_style_forward accepts, as
+ * the reference's read_img (remove_whitespace, cv2.resize INTER_CUBIC to H rows) and its dataset's pad_img prepare a style
+ * image.  No handle: errors are read through dhw_last_error(NULL).  The call allocates nothing, synchronises nothing, makes no
+ * host read of sizes or of the crop boxes and can be captured into a graph.  All argument checks run before the first HIP call
+ * (DHW_ERR_ARG names the argument): 1 <= B <= 65535, 1 <= Hin <= 4096, 16 <= Win <= 16384 and Win % 16 == 0, 8 <= H <= 512,
+ * 8 <= W <= 4096 and W % 4 == 0, B H W < 2^31, 1 <= thresh <= 255, non-NULL images / img_out / status_out / workspace, images /
+ * img_out / workspace 16-byte aligned (sizes / widths_out / boxes_out / status_out 4-byte), workspace_bytes >=
+ * dhw_prep_workspace_bytes(B) (16 B bytes: the crop boxes; 0 for a B out of range).
+ *
+ * Image b, with (h, w) = sizes[b] (Hin, Win when sizes is NULL), lies in the top-left h x w corner of slot b of `images`:
+ *    1. Pixels read.  Only pixels (r, c) with r < h and c < w are ever read.
+ *    2. Crop box: the reference's remove_whitespace(img, thresh), remove_middle=False.  A pixel is dark iff its u8 value is
+ *       < thresh.  r0, r1 = the first and last row holding a dark pixel, c0, c1 likewise for columns.  The crop is rows [r0, r1)
+ *       and columns [c0, c1), upper bounds EXCLUSIVE as the reference slices: the last inked row and column are dropped.
+ *       ch = r1 - r0, cw = c1 - c0.
+ *    3. Output width: ow = (H cw) / ch, integer division (the reference's height * w // h).
+ *    4. status_out[b] is a bit set: 1: h outside [1, Hin] or w outside [1, Win] (no other bit is then set and nothing of the
+ *       image is read).  2: no dark pixel, or ch == 0, or cw == 0.  4: ow > W.  8: ow == 0.
+ *    5. Resize: OpenCV's INTER_CUBIC conventions in fixed point.  For an axis with n_in source and n_out destination samples,
+ *       destination index d has num = (2d + 1) n_in - n_out, den = 2 n_out, x0 = floor(num / den), t = (double)(num - x0 den) /
+ *       (double)den (one fp64 division).  The Keys weights with a = -0.75 are evaluated in fp64 WITHOUT fused multiply-add:
+ *       w0 = ((a (t+1) - 5a)(t+1) + 8a)(t+1) - 4a, w1 = (((a+2) t - (a+3)) t) t + 1, w2 = w1 at 1 - t, each product taken left
+ *       to right.  c_k = rint(2048 w_k) for k = 0, 1, 2 (ties to even), c_3 = 2048 - c_0 - c_1 - c_2: a constant image stays
+ *       constant.  The taps are the source indices clip(x0 - 1 + k, 0, n_in - 1) RELATIVE TO THE CROP: the border replicates
+ *       the crop's own edge, pixels of the image outside the crop are not visible.  Horizontally n_in = cw, n_out = ow;
+ *       vertically n_in = ch, n_out = H.
+ *       value(e, d) = clamp((sum_j sum_k cy[e][j] cx[d][k] src[tap_y(e,j)][tap_x(d,k)] + 2^21) >> 22, 0, 255), exact integer
+ *       arithmetic with an arithmetic shift, so the result does not depend on the order of evaluation (the separable form,
+ *       horizontal pass first, gives the same integers).  sum |c| <= 2816 on each axis, so |sum| + 2^21 <= 255 * 2816^2 + 2^21
+ *       < 2^31.
+ *    6. Status 0: img_out[b,0,e,d] = (float)value(e, d) for d < ow and 255.0f for ow <= d < W (the reference's pad_img);
+ *       widths_out[b] = ow, boxes_out[b] = (r0, r1, c0, c1).
+ *    7. Status non-zero: all H W values are 255 and widths_out[b] = 0; boxes_out[b] holds the box when bit 1 is clear and there
+ *       is ink, otherwise four zeros.
+ *    8. Row b of a batch equals the same image prepared alone, bit for bit, for any B, Hin, Win and W that admit it.
+ * PARITY WITH cv2 ITSELF IS UNPINNED: cv2 is not importable where this was written and its SIMD vertical pass is not
+ * integer-exact; the scheme above is the deterministic statement this project pins (within one grey level of the float
+ * resize of read_img: the coefficients are off by at most 3 / 4096). */
+size_t dhw_prep_workspace_bytes(int B);
+int dhw_prep(const uint8_t* images,   /* device u8 [B,Hin,Win], image b in the top-left h_b x w_b corner */
+             const int32_t* sizes,    /* DEVICE int32 [B,2] = (h_b, w_b), or NULL: every image is Hin x Win */
+             int B, int Hin, int Win, int H, int W, int thresh,
+             float* img_out,          /* device f32 [B,1,H,W], grey levels 0..255 */
+             int32_t* widths_out,     /* device [B] or NULL */
+             int32_t* boxes_out,      /* device [B,4] = (r0, r1, c0, c1) or NULL */
+             int32_t* status_out,     /* device [B] */
+             void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Host-only: beta_i = 0.02 + exp(linspace(ln 1e-5, ln 0.4, T)), abar = cumprod(1-beta), fp32. */
 int dhw_schedule(int T, float* beta_out, float* alpha_bar_out);
 
