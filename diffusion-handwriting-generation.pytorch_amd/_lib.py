@@ -98,6 +98,8 @@ SIGNATURES = {
     "dhw_debug_raise": (C.c_int, [_P, C.c_int]),
     "dhw_debug_attention_time": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "dhw_set_streams": (C.c_int, [_P, C.c_int]),
+    "dhw_debug_plane_reuse": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "dhw_debug_plane_tag": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
     # include/dhw_style.h
     "dhw_style_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "dhw_style_load": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),

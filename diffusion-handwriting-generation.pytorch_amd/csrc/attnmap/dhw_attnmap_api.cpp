@@ -46,7 +46,7 @@ static int attention_impl(dhw_handle* h, const float* strokes, const int64_t* te
   if (Lt > ATTNMAP_MAX_LT) return fail(h, DHW_ERR_ARG, "%s: Lt = %d is more than the map kernel holds (%d)", fn, Lt, ATTNMAP_MAX_LT);
 
   EagerCall ec;
-  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec))) return rc;
+  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec))) return rc;   // (leaves dhw_sample's text plane alone: forward_enqueue)
   auto& [st, dlens, c] = ec;
   if ((rc = forward_enqueue(h, strokes, text, sigma, style, B, L, Lt, eps_out, pen_out, st, dlens))) return rc;
 

@@ -28,7 +28,7 @@ int sample_impl_ddim(dhw_handle* h, const int64_t* text, const float* style, int
     return fail(h, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)latent & 7) ? "latent" : "latent_out");
 
   EagerCall ec;
-  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec)) || (rc = ensure_scratch(h))) return rc;
+  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec)) || (rc = ensure_scratch(h))) return rc;   // (leaves dhw_sample's text plane alone: forward_enqueue)
   auto& [st, dl, c] = ec;   // the stream, the staged lengths or null, the Ctx of the small launches (their profiling bracket)
   const dhw_handle::DenoiseScratch& s = h->scratch;
   const std::vector<DdimCoef> t = ddim_coef_table(schedule_abar(T).data(), levels, S);
@@ -86,7 +86,7 @@ int invert_impl_ddim(dhw_handle* h, const float* strokes, const int64_t* text, c
   if ((uintptr_t)latent_out & 7) return fail(h, DHW_ERR_ARG, "%s: latent_out must be 8-byte aligned", fn);
 
   EagerCall ec;
-  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec)) || (rc = ensure_scratch(h))) return rc;
+  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec)) || (rc = ensure_scratch(h))) return rc;   // (leaves dhw_sample's text plane alone: forward_enqueue)
   auto& [st, dl, c] = ec;   // the stream, the staged lengths or null, the Ctx of the small launches (their profiling bracket)
   const dhw_handle::DenoiseScratch& s = h->scratch;
   const std::vector<DdimCoef> t = ddim_coef_table(schedule_abar(T).data(), levels, S);

@@ -98,6 +98,7 @@ int dhw_create(dhw_handle** out, const dhw_dims* dims, int device) {
     if (const char* e = getenv("DHW_FUSE_UP")) h->fuse_up = atoi(e) != 0;
     if (const char* e = getenv("DHW_CHAIN")) h->chain = atoi(e) != 0;
     if (const char* e = getenv("DHW_PERSIST")) h->persist = atoi(e) != 0;
+    if (const char* e = getenv("DHW_PLANE_REUSE")) h->plane_reuse = atoi(e) != 0;
     if (const char* e = getenv("DHW_TEXT_PAIRS")) h->text_pairs = atoi(e) == 1 ? 1 : atoi(e) == 2 ? 2 : 0;
     if (h->padded) h->fuse = false;   // (pad_weights: the fused block kernels have compile-time LayerNorm widths)
     if (!rc && h->prec == PREC_BF16 && h->persist) {
@@ -154,6 +155,7 @@ int dhw_load(dhw_handle* h, const char* key, const void* host_ptr, int dtype, co
       case WeightStore::LOADED: break;
     }
     h->packed = false;
+    plane_invalidate(h);   // (the next call's dhw_finalize repacks and counts a new weights generation)
     return 0;
   });
 }
@@ -231,6 +233,21 @@ int dhw_debug_persist_trace(dhw_handle* h, unsigned long long* host_dst, int64_t
 }
 int dhw_set_graph(dhw_handle* h, int on) {
   DHW_GUARD(h, "dhw_set_graph", int, { return set_graph(h, on); });
+}
+int dhw_debug_plane_reuse(dhw_handle* h, int* last, long* calls, long* reused) {
+  DHW_GUARD(h, "dhw_debug_plane_reuse", int, { return debug_plane_reuse(h, last, calls, reused); });
+}
+int dhw_debug_plane_tag(const int64_t resident[10], const int64_t call[10], int gates) {
+  DHW_GUARD(nullptr, "dhw_debug_plane_tag", int, {
+    if (!resident || !call) return fail(nullptr, DHW_ERR_ARG, "dhw_debug_plane_tag: null argument");
+    auto tag = [](const int64_t* v) {
+      PlaneTag t;
+      t.valid = v[0] != 0; t.B = (int)v[1]; t.nstreams = (int)v[2]; t.Lt = (int)v[3]; t.S = (int)v[4]; t.T = (int)v[5]; t.t_start = (int)v[6];
+      t.weights_gen = (uint64_t)v[7]; t.film = (const void*)(uintptr_t)v[8]; t.plane_gen = (uint64_t)v[9];
+      return t;
+    };
+    return (int)plane_host_ok(tag(resident), tag(call), PlaneGate{(gates & 1) != 0, (gates & 2) != 0, (gates & 4) != 0});
+  });
 }
 
 int dhw_debug_set_teacher(dhw_handle* h, const float* reset_dev, float* capture_dev, int every) {

@@ -197,7 +197,16 @@ hipError_t launch_heads(const HeadsParams& p, hipStream_t st);
 // x_T ~ N(0,1) from Philox, same keying as the per-step draws (iter = -1)
 hipError_t launch_randn_init(float* xt, long rows, int L, const uint64_t* seed_ptr, int sample_off, hipStream_t st, int iter = -1);
 // seed_ptr[0] = seed, seed_ptr[1] = first_sample (by-value kernel arguments: no host buffer lifetime)
-hipError_t launch_set_seed(uint64_t* seed_ptr, uint64_t seed, int64_t first_sample, hipStream_t st);
+// plane_skip (dhw_sample; or null): plane_skip[1] += plane_skip[0] (the finished call's flag joins the count of reused calls), then
+// plane_skip[0] = host_ok — the opening value of this call's plane-reuse flag, which launch_stage_compare can only clear
+hipError_t launch_set_seed(uint64_t* seed_ptr, uint64_t seed, int64_t first_sample, hipStream_t st, unsigned* plane_skip = nullptr,
+                           unsigned host_ok = 0);
+// dhw_sample's staging of the caller's prompts and styles, and the content compare behind the plane reuse, in one launch: every
+// piece of text [text_bytes] and style [style_bytes] is read from the caller and from the stage, compared AS BITS (-0.0 != 0.0, NaN
+// payloads count) and written to the stage; any differing piece stores 0 to *plane_skip.  Byte counts are multiples of 8 (text,
+// int64) and 4 (style, fp32); pieces are 16 bytes wide where the caller's pointer and the count allow it.
+hipError_t launch_stage_compare(const void* text, void* text_stage, size_t text_bytes, const void* style, void* style_stage, size_t style_bytes,
+                                unsigned* plane_skip, hipStream_t st);
 // x[b, r, :] = 0 for r >= lens[b] (rows of C fp32 values, L rows per sample): the padding rows of ragged sampler state / outputs
 hipError_t launch_zero_tail(float* x, int B, int L, int C, const int* lens, hipStream_t st);
 // one-time per-process kernel attribute setup (dynamic LDS > 64 KiB)
@@ -223,6 +232,7 @@ struct TextStyleParams {
   const void *w_q8, *w_kv8, *w_d8, *w_tf1, *w_tf3;   // packed as for the GEMM kernel ([384x384], [768x384] K|V, [384x384], [768x384], [384x768])
   const float *b_q8, *b_kv8, *b_d8, *b_tf1, *b_tf3;
   void* text_out;         // [n][Lt][384]
+  const unsigned* skip;   // all-steps plane only, else null: *skip != 0 = text_out already holds this launch's result -> return at once
 };
 struct TextLayerParams {
   int n, Lt, d;           // pairs, tokens (<= 32), layer width (192 / 256 / 384)
@@ -234,6 +244,7 @@ struct TextLayerParams {
   void* k1;               // [n][Lt][d]
   void* vt1; int lpadT;   // v1 [n][Lt][d], rows like k1 (lpadT unused)
   int pairs;              // pairs per workgroup: 0 = the launcher's choice, 1, 2 (2 needs an even film_div: textside.hip)
+  const unsigned* skip;   // as TextStyleParams.skip, for k1 / vt1
 };
 bool textside_supported(int prec, int Lt, int S5, int dt);
 hipError_t launch_text_style(int prec, const TextStyleParams& p, hipStream_t st);

@@ -128,9 +128,38 @@ __global__ __launch_bounds__(256) void heads_kernel(const HeadsParams p) {
   heads_finish(p, row, a0, a1, a2);
 }
 
-__global__ void set_seed_kernel(uint64_t* p, uint64_t seed, int64_t first) {
+__global__ void set_seed_kernel(uint64_t* p, uint64_t seed, int64_t first, unsigned* plane_skip, unsigned host_ok) {
   p[0] = seed;
   p[1] = (uint64_t)first;
+  if (plane_skip) {
+    plane_skip[1] += plane_skip[0];   // the call before this one ran with that flag
+    plane_skip[0] = host_ok;
+  }
+}
+
+// One piece of V (4 / 8 / 16 bytes) of a staged tensor: stage[i] := src[i]; a piece whose bits differ from what the stage held clears *flag.
+template <typename V>
+__device__ __forceinline__ void stage_piece(const void* src, void* stage, size_t i, unsigned* flag) {
+  const V a = reinterpret_cast<const V*>(src)[i];
+  V* d = reinterpret_cast<V*>(stage) + i;
+  const V b = *d;
+  bool same;
+  if constexpr (sizeof(V) == 16) same = a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w;
+  else if constexpr (sizeof(V) == 8) same = a.x == b.x && a.y == b.y;
+  else same = a == b;
+  *d = a;
+  if (!same) *flag = 0u;   // (every such thread stores the same 0)
+}
+struct StageSeg { const void* src; void* stage; size_t pieces; int lg; };   // lg: log2 of the piece size in bytes (2, 3, 4)
+__global__ __launch_bounds__(256) void stage_compare_kernel(StageSeg s0, StageSeg s1, unsigned* flag) {
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const bool second = i >= s0.pieces;
+  const StageSeg& s = second ? s1 : s0;
+  if (second) i -= s0.pieces;
+  if (i >= s.pieces) return;
+  if (s.lg == 4) stage_piece<uint4>(s.src, s.stage, i, flag);
+  else if (s.lg == 3) stage_piece<uint2>(s.src, s.stage, i, flag);
+  else stage_piece<unsigned>(s.src, s.stage, i, flag);
 }
 
 // iter = -1: x_T; iter = k >= 0: the draw the k-th sampler step adds (the same call heads_finish makes)
@@ -211,7 +240,21 @@ hipError_t launch_randn_init(float* xt, long rows, int L, const uint64_t* seed_p
   hipLaunchKernelGGL(randn_init_kernel, dim3(nblk(rows, 256)), dim3(256), 0, st, xt, rows, L, seed_ptr, sample_off, iter);
   return hipGetLastError();
 }
-hipError_t launch_set_seed(uint64_t* seed_ptr, uint64_t seed, int64_t first_sample, hipStream_t st) {
-  hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, seed_ptr, seed, first_sample);
+hipError_t launch_set_seed(uint64_t* seed_ptr, uint64_t seed, int64_t first_sample, hipStream_t st, unsigned* plane_skip, unsigned host_ok) {
+  hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, seed_ptr, seed, first_sample, plane_skip, host_ok);
+  return hipGetLastError();
+}
+hipError_t launch_stage_compare(const void* text, void* text_stage, size_t text_bytes, const void* style, void* style_stage, size_t style_bytes,
+                                unsigned* plane_skip, hipStream_t st) {
+  if (!text || !text_stage || !style || !style_stage || !plane_skip || text_bytes % 8 || style_bytes % 4) return hipErrorInvalidValue;
+  // the widest piece that both pointers' alignment and the byte count allow (a caller's tensor may be a view at any element offset)
+  auto seg = [](const void* src, void* stage, size_t bytes, int lg_min) {
+    int lg = 4;
+    while (lg > lg_min && (((uintptr_t)src | (uintptr_t)stage | bytes) & ((1u << lg) - 1))) --lg;
+    return StageSeg{src, stage, bytes >> lg, lg};
+  };
+  const StageSeg s0 = seg(text, text_stage, text_bytes, 3), s1 = seg(style, style_stage, style_bytes, 2);
+  if (s0.pieces + s1.pieces == 0) return hipSuccess;
+  hipLaunchKernelGGL(stage_compare_kernel, dim3(nblk((long)(s0.pieces + s1.pieces), 256)), dim3(256), 0, st, s0, s1, plane_skip);
   return hipGetLastError();
 }

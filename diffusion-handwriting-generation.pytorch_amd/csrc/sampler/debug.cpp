@@ -68,7 +68,7 @@ int debug_attention_time(dhw_handle* h, int layer, int iters, double* us_with, d
   const int Lk = (int)el_rows(L, layer);
   Ctx c{h, &h->ws[0], st, B, L, h->last_Lt, h->dims.S * 5, h->d_film, 2L * h->film_tot};
   const void* x = layer == 0 ? CBB(c, CB_ENC2, out) : layer == 1 ? CBB(c, CB_ENC4, out) : layer == 2 ? WS(c, att_dense) : ELB(c, layer - 1, out);
-  EncLayerParams q = enc_params(c, layer, w, x, Lk, h->lpadX[layer < 2 ? layer : 2], h->d_text_stage, nullptr);
+  EncLayerParams q = enc_params(c, layer, w, x, Lk, h->lpadX[layer < 2 ? layer : 2], h->d_text_stage, nullptr);   // (reads the stage; the plane tag stays)
   // (the measured launches write the layer's `out` again: same inputs, same values; with the stage skipped, different ones —
   // the workspace is scratch between calls)
   if (c.err) return c.err;
@@ -98,8 +98,11 @@ int debug_attention_time(dhw_handle* h, int layer, int iters, double* us_with, d
   return 0;
 }
 
+// (profiled calls launch eagerly into the same ".T" buffers and evaluate the same kernels: the resident plane stays valid)
 int profile_enable(dhw_handle* h, int on) {
   if (!h) return DHW_ERR_ARG;
+  if (on && !h->h_prof_skip && (hipSetDevice(h->device) != hipSuccess || hipHostMalloc((void**)&h->h_prof_skip, dhw_handle::PROF_SKIP_CAP * sizeof(unsigned)) != hipSuccess))
+    return fail(h, DHW_ERR_HIP, "pinned plane-flag buffer: %s", hipGetErrorString(hipGetLastError()));
   h->prof = on != 0;
   return 0;
 }
@@ -110,6 +113,7 @@ int profile_reset(dhw_handle* h) {
   for (auto& r : h->prof_recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   h->prof_recs.clear();
   h->prof_agg.clear();
+  h->prof_calls = 0;
   return 0;
 }
 int profile_count(dhw_handle* h) {
@@ -122,7 +126,9 @@ int profile_count(dhw_handle* h) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) continue;
     ProfAgg& a = h->prof_agg[r.label];
-    a.ms += ms; a.flops += r.flops; a.bytes += r.bytes; a.n += 1;
+    // a text-plane launch of a call that reused the resident plane returned at once: its time counts, its algorithmic work does not
+    const bool skipped = r.plane_call >= 0 && h->h_prof_skip && h->h_prof_skip[r.plane_call] != 0;
+    a.ms += ms; a.flops += skipped ? 0.0 : r.flops; a.bytes += skipped ? 0.0 : r.bytes; a.n += 1;
   }
   return (int)h->prof_agg.size();
 }
@@ -140,6 +146,7 @@ int profile_get(dhw_handle* h, int i, const char** label, double* total_ms, int6
 int set_streams(dhw_handle* h, int n) {
   if (!h || n < 1) return DHW_ERR_ARG;
   h->nstreams = std::min(n, h->nstreams_alloc);
+  plane_invalidate(h);   // (the sub-batch split decides which workspace's plane holds which prompts)
   return h->nstreams;
 }
 // shapes of dhw_sample that run as one persistent launch per denoiser call (persist.h): cached plans that are in use
@@ -162,12 +169,28 @@ int debug_persist_trace(dhw_handle* h, unsigned long long* host_dst, int64_t max
 int set_graph(dhw_handle* h, int on) {
   if (!h) return DHW_ERR_ARG;
   h->use_graph = on != 0;
+  plane_invalidate(h);   // every dhw_set_* clears the tag: the first call after a switch evaluates the text side
+  return 0;
+}
+
+// The plane-reuse flag of the most recent dhw_sample* call, read back from the device, and the counts: calls enqueued, and how
+// many of them ran with the flag set (the device folds each finished call's flag into a counter when the next one opens).
+int debug_plane_reuse(dhw_handle* h, int* last, long* calls, long* reused) {
+  if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
+  HIPCK(h, hipSetDevice(h->device));
+  HIPCK(h, hipDeviceSynchronize());
+  unsigned w[2] = {0, 0};
+  HIPCK(h, hipMemcpy(w, h->d_plane_skip, sizeof(w), hipMemcpyDeviceToHost));
+  if (last) *last = h->plane_calls ? (int)w[0] : 0;
+  if (calls) *calls = h->plane_calls;
+  if (reused) *reused = h->plane_calls ? (long)w[1] + (long)w[0] : 0;
   return 0;
 }
 
 int debug_set_teacher(dhw_handle* h, const float* reset_dev, float* capture_dev, int every) {
   if (!h) return DHW_ERR_ARG;
   if (every < 0 || (every > 0 && (!reset_dev || !capture_dev))) return fail(h, DHW_ERR_ARG, "dhw_debug_set_teacher: bad arguments");
+  if (every != h->teach_every) plane_invalidate(h);   // (the python binding re-applies an unchanged setting before every sample call)
   h->teach_every = every;
   h->teach_reset = every ? reset_dev : nullptr;
   h->teach_capture = every ? capture_dev : nullptr;

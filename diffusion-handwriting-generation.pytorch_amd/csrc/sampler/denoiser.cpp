@@ -451,10 +451,15 @@ void text_style_dynamic(Ctx& c) {
     q.w_q8 = h->w_q8; q.w_kv8 = h->w_kv8; q.w_d8 = h->w_d8; q.w_tf1 = h->w_tf1; q.w_tf3 = h->w_tf3;
     q.b_q8 = h->b_q8; q.b_kv8 = h->b_kv8; q.b_d8 = h->b_d8; q.b_tf1 = h->b_tf1; q.b_tf3 = h->b_tf3;
     q.text_out = TS(c, text_out);
+    // plane reuse: only the all-steps launches of the sampling loop carry the flag; per-step launches, dhw_forward and the
+    // generic path below always evaluate
+    const unsigned* skip = c.planeT ? c.plane_skip : nullptr;
+    const int pcall = skip ? c.plane_call : -1;
+    q.skip = skip;
     if (!c.err) {
       const double n = c.B, ddt = dt;
       Launch l(h, c.st, "ts.fused", n * (2.0 * c.S5 * ddt * 2 * ddt + 2.0 * c.Lt * ddt * ddt * 2 + 4.0 * c.Lt * c.S5 * ddt + 2.0 * c.Lt * ddt * 2 * ddt * 2),
-               n * c.Lt * ddt * h->es + (double)in_B * (c.S5 + c.Lt) * ddt * h->es + 8.0 * ddt * ddt * h->es);
+               n * c.Lt * ddt * h->es + (double)in_B * (c.S5 + c.Lt) * ddt * h->es + 8.0 * ddt * ddt * h->es, pcall);
       hipError_t e = launch_text_style(h->prec, q, c.st);
       if (e != hipSuccess) c.err = fail(h, DHW_ERR_HIP, "text_style fused: %s", hipGetErrorString(e));
     }
@@ -470,8 +475,9 @@ void text_style_dynamic(Ctx& c) {
       t.k1 = ELT(c, (int)i, k1); t.vt1 = ELT(c, (int)i, vt1); t.lpadT = h->lpadT;
       if (c.err) break;
       t.pairs = h->text_pairs;
+      t.skip = skip;
       const double n = c.B, dd = w.d;
-      Launch l(h, c.st, "enc.text_fused", n * c.Lt * (2.0 * dt * dd + 4.0 * dd * dd), n * c.Lt * (dt + 2.0 * dd) * h->es + (dt * dd + 2.0 * dd * dd) * h->es);
+      Launch l(h, c.st, "enc.text_fused", n * c.Lt * (2.0 * dt * dd + 4.0 * dd * dd), n * c.Lt * (dt + 2.0 * dd) * h->es + (dt * dd + 2.0 * dd * dd) * h->es, pcall);
       hipError_t e = launch_text_layer(h->prec, t, c.st);
       if (e != hipSuccess) c.err = fail(h, DHW_ERR_HIP, "text layer %s: %s", h->el_name[i].c_str(), hipGetErrorString(e));
     }

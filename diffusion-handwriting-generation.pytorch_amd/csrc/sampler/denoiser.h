@@ -10,13 +10,14 @@ struct Launch {
   dhw_handle* h;
   hipStream_t st;
   int rec = -1;
-  Launch(dhw_handle* h_, hipStream_t st_, const char* label, double flops = 0, double bytes = 0) : h(h_), st(st_) {
+  // plane_call: >= 0 for a launch that the plane-reuse flag of that profiled call may have skipped (handle.h h_prof_skip)
+  Launch(dhw_handle* h_, hipStream_t st_, const char* label, double flops = 0, double bytes = 0, int plane_call = -1) : h(h_), st(st_) {
     if (!h->prof) return;
     int id = -1;
     for (size_t i = 0; i < h->prof_labels.size(); ++i)
       if (h->prof_labels[i] == label) id = (int)i;
     if (id < 0) { id = (int)h->prof_labels.size(); h->prof_labels.push_back(label); }
-    ProfRec r{id, nullptr, nullptr, flops, bytes};
+    ProfRec r{id, nullptr, nullptr, flops, bytes, plane_call};
     hipEventCreate(&r.a);
     hipEventCreate(&r.b);
     hipEventRecord(r.a, st);
@@ -40,6 +41,8 @@ struct Ctx {
   int film_div = 1;    // samples per FiLM row
   int in_B = 0;        // batch of the sigma-independent inputs (0 = B); the text plane replicates them over steps
   bool planeT = false; // the text side writes the all-steps plane (".T" buffers) instead of the per-call ones
+  const unsigned* plane_skip = nullptr;   // planeT only: the fused text-side launches return at once when *plane_skip != 0
+  int plane_call = -1;      // profile mode: this call's slot of h_prof_skip
   const HeadsParams* fhp = nullptr;   // sampling loop: dec1 evaluates the heads + scheduler step itself
   bool fuse_input = false;  // enc1 evaluates input_dense while staging (sampling loop); forward() keeps the tap
   bool use_plane = false;   // stroke path reads the text K/V of step `plane_step` from the plane

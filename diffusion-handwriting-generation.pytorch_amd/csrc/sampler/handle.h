@@ -13,6 +13,7 @@
 #include "../abi_guard.h"
 #include "../dhw_kernels.h"
 #include "../persist.h"
+#include "plane_tag.h"
 #include "../host/device_arena.h"
 #include "../host/weight_store.h"
 
@@ -21,7 +22,7 @@
 constexpr int SIG = 32, SIG_HID = 2048, VOCAB = 73, STYLE_CH = 256;
 constexpr int SLACK_ROWS = 64;   // every activation buffer is over-allocated so tile over-reads stay in bounds
 
-struct ProfRec { int label; hipEvent_t a, b; double flops, bytes; };
+struct ProfRec { int label; hipEvent_t a, b; double flops, bytes; int plane_call = -1; };   // plane_call: slot of h_prof_skip that says whether this launch was skipped
 struct ProfAgg { std::string label; double ms = 0, flops = 0, bytes = 0; int64_t n = 0; };
 
 struct Tap { void* p; int rows; int cols; bool f32; };
@@ -148,6 +149,7 @@ struct dhw_handle {
   bool fuse_text = true;        // fused text-side kernels (textside.hip; env DHW_FUSE_TEXT=0 -> generic GEMM / attention launches)
   int text_pairs = 0;           // (step, prompt) pairs per workgroup of text_layer_kernel: 0 = by size, env DHW_TEXT_PAIRS = 1 / 2 forces one form
   std::map<std::vector<uint64_t>, hipGraphExec_t> graphs;
+  std::map<std::vector<uint64_t>, uint64_t> graph_plane_gen;   // per cached graph: plane_gen when it was captured (it keeps those ".T" buffers)
   int64_t* d_text_stage = nullptr;
   float* d_style_stage = nullptr;
   float* d_out_stage = nullptr;
@@ -167,6 +169,20 @@ struct dhw_handle {
   // at or past lens[b] are never read.  No graph reads the set: these calls leave the cached graphs alone.
   struct DenoiseScratch { float *x = nullptr, *w = nullptr, *eps = nullptr, *pen = nullptr, *sigma = nullptr; } scratch;
   uint64_t* d_seed = nullptr;   // [seed, first_sample] read by the noise kernels
+  // Reuse of the all-steps text plane across dhw_sample* calls.  plane_tag: what the plane in the ".T" buffers was
+  // computed for; cleared by everything that may change it (plane_invalidate) and while a call is being enqueued.
+  // d_plane_skip[0]: 1 = the plane is valid for the call in flight (set_seed_kernel writes the host's verdict, stage_compare_kernel
+  // clears it when prompts or styles differ, text_style_kernel / text_layer_kernel read it inside the graph); [1]: earlier calls that reused.
+  bool plane_reuse = true;      // env DHW_PLANE_REUSE=0 -> the host's verdict is always 0
+  PlaneTag plane_tag;
+  uint64_t weights_gen = 0, plane_gen = 0;
+  unsigned* d_plane_skip = nullptr;
+  long plane_calls = 0;         // dhw_sample* calls enqueued on this handle
+  // profile mode: the flag of every call, copied behind its compare into a pinned slot, so that the rows of skipped launches
+  // can report no work once the events are resolved
+  unsigned* h_prof_skip = nullptr;
+  int prof_calls = 0;
+  static constexpr int PROF_SKIP_CAP = 4096;
   // ragged calls (dhw_forward_ragged / dhw_sample_ragged): the per-sample lengths, copied on the caller's stream from a pinned host
   // buffer the handle owns.  The kernels read them at run time, so one captured graph serves every set of lengths of a shape.
   int* d_lens = nullptr;          // [max_B]
@@ -263,6 +279,8 @@ int set_streams(dhw_handle* h, int n);
 int debug_persist_plans(dhw_handle* h);
 int debug_persist_trace(dhw_handle* h, unsigned long long* host_dst, int64_t max_words);
 int set_graph(dhw_handle* h, int on);
+int debug_plane_reuse(dhw_handle* h, int* last, long* calls, long* reused);
+inline void plane_invalidate(dhw_handle* h) { h->plane_tag.valid = false; }   // the resident plane is no longer known to match anything
 int debug_set_teacher(dhw_handle* h, const float* reset_dev, float* capture_dev, int every);
 
 #pragma GCC visibility pop

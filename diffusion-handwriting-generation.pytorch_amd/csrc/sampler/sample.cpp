@@ -77,6 +77,7 @@ int eager_check(dhw_handle* h, const char* fn, int B, int L, int Lt, const int32
   return lens ? check_lens(h, fn, lens, B, L, false) : 0;
 }
 
+// (plane reuse, DESIGN 27: the prologue writes h->d_lens alone — neither the all-steps plane nor the text / style staging buffers)
 int eager_begin(dhw_handle* h, int B, int L, int Lt, const int32_t* lens, void* hip_stream, EagerCall* ec) {
   if (int rc = dhw_finalize(h)) return rc;
   HIPCK(h, hipSetDevice(h->device));
@@ -101,6 +102,8 @@ int forward_impl(dhw_handle* h, const char* fn, const float* strokes, const int6
 
 // The launches of one denoiser call on checked arguments (dhw_forward / dhw_forward_ragged, and every level of dhw_score);
 // lens = the staged device lengths of a ragged call, or null.
+// (plane reuse, DESIGN 27: the text side runs from the caller's own pointers into the per-call buffers ts / el[i].t of ws[0], planeT
+// false and no skip word — the all-steps plane, the staging buffers and the plane tag are left alone by every entry built on this)
 int forward_enqueue(dhw_handle* h, const float* strokes, const int64_t* text, const float* sigma, const float* style, int B, int L, int Lt,
                     float* eps_out, float* pen_out, hipStream_t st, const int* lens) {
   Ctx c{h, &h->ws[0], st, B, L, Lt, h->dims.S * 5, h->d_film, 2L * h->film_tot};
@@ -110,7 +113,7 @@ int forward_enqueue(dhw_handle* h, const float* strokes, const int64_t* text, co
   RUN_SMALL(c, "film_table", launch_film(h->d_sig32, B, h->d_film_w, h->d_film_b, 2 * h->film_tot, h->d_film, st));
   tap(c, TAP_SIGMA_FFN, h->d_sig32, 1, SIG, true);
   text_style_static(c, text, style);
-  text_style_dynamic(c);
+  text_style_dynamic(c);   // (c.planeT false: always evaluated)
   stroke_path(c, strokes, text);
   HeadsParams hp{};
   hp.eps = eps_out;
@@ -123,9 +126,6 @@ int forward_enqueue(dhw_handle* h, const float* strokes, const int64_t* text, co
   h->last_B = B; h->last_L = L; h->last_Lt = Lt;
   return c.err;
 }
-
-// sampler steps whose text side is precomputed together (bounds the plane's memory for long schedules)
-static int plane_chunk(int T) { return std::min(T, 64); }
 
 // What is constant over one dhw_sample call: the shape, the library-owned staging buffers the call reads and writes, the
 // schedule (T entries each), and the device lengths of a ragged call (or null).  A conditioned call (dhw_sample_cond) adds the
@@ -142,6 +142,7 @@ struct SampleCall {
   const unsigned char* keep;
   const float* cond_noise;
   int t_start;
+  int plane_call;   // profile mode: the slot of h_prof_skip that receives this call's plane-reuse flag, or -1
 };
 
 // One prompt sub-batch [b0, b0+Bs) of a B-prompt batch, enqueued on `st` with workspace `w`.
@@ -214,6 +215,8 @@ static int sample_enqueue(dhw_handle* h, const SampleCall& sc, Workspace* w, int
       cp.film_bs = -2L * h->film_tot;
       cp.film_div = Bs;
       cp.planeT = true;
+      cp.plane_skip = h->d_plane_skip;   // resident and valid for this call: the launches return at once
+      cp.plane_call = sc.plane_call;
       text_style_dynamic(cp);
       if (cp.err) return cp.err;
     }
@@ -222,7 +225,7 @@ static int sample_enqueue(dhw_handle* h, const SampleCall& sc, Workspace* w, int
     c.plane_step = (step - first) % TC;
     if (!h->plane) {
       if (rec_out) return 0;   // (the persistent form reads the text K/V from the all-steps plane)
-      text_style_dynamic(c);
+      text_style_dynamic(c);   // (per step into the per-call buffers: no skip word)
     }
     HeadsParams hp{};
     hp.eps = nullptr;
@@ -401,7 +404,7 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
       *(volatile unsigned*)h->h_step_err = 0;
       h->persist = false;
       hipDeviceSynchronize();
-      drop_graphs(h);
+      drop_graphs(h);   // (and with them the plane tag)
       if (h->d_step_sync) hipMemset(h->d_step_sync, 0, h->step_sync_words * sizeof(unsigned));
       if (code >= 0x100u)
         return fail(h, DHW_ERR_HIP, "persistent step kernel: XCD %u owns samples but no workgroup of the launch ran there in an EARLIER call (partitioned / "
@@ -431,15 +434,47 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
       if (c.err) return c.err;
       ft->ready = true;
     }
+    // the staging buffers that cached graphs read grow (dropping those graphs) before the reuse verdict below looks a graph up
+    const size_t rows = (size_t)B * L;
+    if (noise && (rc = grow_stage(h, &h->d_noise_stage, &h->noise_stage_cap, (size_t)(T + 1) * rows * 2))) return rc;
+    if (cond && cond->cond_noise && (rc = grow_stage(h, &h->d_cond_noise_stage, &h->cond_noise_stage_cap, (size_t)T * rows * 2))) return rc;
+    // Plane reuse: the host's half of the verdict.  The tag stays cleared until this call has been enqueued, so any
+    // error return below leaves it cleared.  A graph keeps the ".T" buffers it was captured with: its generation is the one then.
+    const bool graph = h->use_graph && !h->prof && !h->teach_every;
+    const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)Lt, (uint64_t)T, (uint64_t)mode, (uint64_t)(noise != nullptr), (uint64_t)h->nstreams, (uint64_t)h->plane, (uint64_t)h->fuse_heads, (uint64_t)h->fuse_up, (uint64_t)h->chain, (uint64_t)h->persist,
+                                         (uint64_t)ragged,   // (ragged: the kernels read the lengths from h->d_lens at replay)
+                                         // conditioned calls: known / keep / cond_noise are read from the staging buffers at replay,
+                                         // so one graph serves every mask; the iterations it holds depend on t_start
+                                         (uint64_t)(cond != nullptr), (uint64_t)(cond ? cond->t_start : T), (uint64_t)(cond && cond->keep), (uint64_t)(cond && cond->cond_noise)};
+    PlaneTag call_tag;
     {
-      hipError_t e = launch_set_seed(h->d_seed, seed, first_sample, st);
+      auto gen = h->graph_plane_gen.find(key);
+      call_tag.valid = true;
+      call_tag.B = B; call_tag.nstreams = h->nstreams; call_tag.Lt = Lt; call_tag.S = h->dims.S; call_tag.T = T;
+      call_tag.t_start = cond ? cond->t_start : T;
+      call_tag.weights_gen = h->weights_gen;
+      call_tag.film = ft->d_film;
+      call_tag.plane_gen = graph && gen != h->graph_plane_gen.end() ? gen->second : h->plane_gen;
+    }
+    const PlaneGate gate{h->plane_reuse, h->plane, h->fuse && h->fuse_text && textside_supported(h->prec, Lt, h->dims.S * 5, 2 * h->dims.c2)};
+    const unsigned host_ok = plane_host_ok(h->plane_tag, call_tag, gate);
+    plane_invalidate(h);
+    {
+      hipError_t e = launch_set_seed(h->d_seed, seed, first_sample, st, h->d_plane_skip, host_ok);
       if (e != hipSuccess) return fail(h, DHW_ERR_HIP, "set_seed: %s", hipGetErrorString(e));
     }
 
-    // stage the caller's tensors into library-owned buffers (tiny D2D copies, outside the graph)
-    const size_t rows = (size_t)B * L;
-    HIPCK(h, hipMemcpyAsync(h->d_text_stage, text, (size_t)B * Lt * 8, hipMemcpyDeviceToDevice, st));
-    HIPCK(h, hipMemcpyAsync(h->d_style_stage, style, (size_t)B * h->dims.S * 1280 * 4, hipMemcpyDeviceToDevice, st));
+    // stage the caller's prompts and styles into library-owned buffers (outside the graph); the same launch compares them with
+    // what the stage held and clears the reuse flag on any difference
+    {
+      hipError_t e = launch_stage_compare(text, h->d_text_stage, (size_t)B * Lt * 8, style, h->d_style_stage, (size_t)B * h->dims.S * 1280 * 4, h->d_plane_skip, st);
+      if (e != hipSuccess) return fail(h, DHW_ERR_HIP, "stage_compare: %s", hipGetErrorString(e));
+    }
+    int plane_call = -1;
+    if (h->prof && h->h_prof_skip && h->prof_calls < dhw_handle::PROF_SKIP_CAP) {
+      plane_call = h->prof_calls++;
+      HIPCK(h, hipMemcpyAsync(h->h_prof_skip + plane_call, h->d_plane_skip, 4, hipMemcpyDeviceToHost, st));
+    }
     const float* nz = nullptr;
     if (noise) {
       const size_t need = (size_t)(T + 1) * rows * 2;
@@ -470,18 +505,12 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
     }
 
     const SampleCall sc{B, L, Lt, T, mode, h->d_text_stage, h->d_style_stage, nz, h->d_out_stage, beta.data(), alpha.data(), lens,
-                        kn, kp, cz, cond ? cond->t_start : T};
-    const bool graph = h->use_graph && !h->prof && !h->teach_every;
+                        kn, kp, cz, cond ? cond->t_start : T, plane_call};
     if (!graph) {
       // eager launches: sub-batches still fork onto the side streams (concurrent kernels of different sub-batches);
       // profiling keeps one stream so the per-launch events bracket one kernel each
       rc = sample_enqueue_all(h, sc, !h->prof, st);
     } else {
-      const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)Lt, (uint64_t)T, (uint64_t)mode, (uint64_t)(nz != nullptr), (uint64_t)h->nstreams, (uint64_t)h->plane, (uint64_t)h->fuse_heads, (uint64_t)h->fuse_up, (uint64_t)h->chain, (uint64_t)h->persist,
-                                           (uint64_t)ragged,   // (ragged: the kernels read the lengths from h->d_lens at replay)
-                                           // conditioned calls: known / keep / cond_noise are read from the staging buffers at replay,
-                                           // so one graph serves every mask; the iterations it holds depend on t_start
-                                           (uint64_t)(kn != nullptr), (uint64_t)sc.t_start, (uint64_t)(kp != nullptr), (uint64_t)(cz != nullptr)};
       auto it = h->graphs.find(key);
       if (it == h->graphs.end()) {
         const StepPlan* d_plans = ragged || kn ? nullptr : ensure_step_plans(h, key, sc);   // (before the capture: it uploads)
@@ -502,11 +531,16 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
         hipStreamDestroy(cs);
         if (rc) return rc;
         it = h->graphs.emplace(key, ex).first;
+        h->graph_plane_gen[key] = h->plane_gen;   // (== call_tag.plane_gen: no entry was found above)
       }
       HIPCK(h, hipGraphLaunch(it->second, st));
     }
     if (rc == 0) HIPCK(h, hipMemcpyAsync(out, h->d_out_stage, rows * 3 * 4, hipMemcpyDeviceToDevice, st));
     h->last_B = B; h->last_L = L; h->last_Lt = Lt;
+    if (rc == 0) {   // enqueued: after this call the ".T" buffers hold the plane of call_tag (computed by it, or found valid)
+      ++h->plane_calls;
+      if (gate.plane && gate.text_fused) h->plane_tag = call_tag;
+    }
     return rc;
   }
 }

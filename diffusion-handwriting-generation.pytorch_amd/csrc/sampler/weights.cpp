@@ -293,7 +293,8 @@ int finalize_impl(dhw_handle* h) {
   if (const int m = h->store.first_missing(); m >= 0) return fail(h, DHW_ERR_KEY, "missing key in state_dict: %s", h->store.spec[m].key.c_str());
   HIPCK(h, hipSetDevice(h->device));
   HIPCK(h, hipDeviceSynchronize());
-  drop_graphs(h);   // device is idle here (synchronised above)
+  drop_graphs(h);   // device is idle here (synchronised above); the resident text plane goes with the graphs
+  ++h->weights_gen;
   const dhw_dims& d = h->dims;
   const int c1 = d.c1, c2 = d.c2, c3 = d.c3, dt = 2 * c2;
   int rc;

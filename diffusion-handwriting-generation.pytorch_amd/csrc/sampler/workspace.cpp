@@ -22,6 +22,8 @@ int ensure_scratch(dhw_handle* h) {
 void drop_graphs(dhw_handle* h) {
   for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
   h->graphs.clear();
+  h->graph_plane_gen.clear();
+  plane_invalidate(h);   // (every caller is an event after which the resident plane may be stale: new weights, a persistent-step fallback)
 }
 
 static int act_alloc(dhw_handle* h, void** slot, long rows, int cols, bool f32 = false) {
@@ -105,6 +107,8 @@ int ensure_plane(dhw_handle* h, Workspace& w, long steps, long B) {
   }
 #undef AA
   w.plane_cap = n;   // (a grown plane leaks the smaller one until destroy)
+  ++h->plane_gen;    // new, zeroed ".T" buffers: nothing resident (graphs captured earlier keep writing and reading the old ones)
+  plane_invalidate(h);
   return 0;
 }
 
@@ -116,6 +120,7 @@ int alloc_shared(dhw_handle* h) {
   if ((rc = dev_alloc(h, (void**)&h->d_sig32, B * SIG * 4))) return rc;
   if ((rc = dev_alloc(h, (void**)&h->d_film, (size_t)B * 2 * h->film_tot * 4))) return rc;
   if ((rc = dev_alloc(h, (void**)&h->d_seed, 16))) return rc;
+  if ((rc = dev_alloc(h, (void**)&h->d_plane_skip, 8))) return rc;
   if ((rc = dev_alloc(h, (void**)&h->d_text_stage, (size_t)(B * Lt + 64) * 8))) return rc;
   if ((rc = dev_alloc(h, (void**)&h->d_style_stage, (size_t)(B * S5 + SLACK_ROWS) * STYLE_CH * 4))) return rc;
   if ((rc = dev_alloc(h, (void**)&h->d_out_stage, (size_t)(B * L + SLACK_ROWS) * 3 * 4))) return rc;
@@ -179,6 +184,7 @@ void destroy_impl(dhw_handle* h) {
   h->arena.free_all();
   if (h->h_step_err) hipHostFree(h->h_step_err);
   if (h->h_lens_pin) hipHostFree(h->h_lens_pin);
+  if (h->h_prof_skip) hipHostFree(h->h_prof_skip);
   if (h->lens_ev) hipEventDestroy(h->lens_ev);
   delete h;
 }

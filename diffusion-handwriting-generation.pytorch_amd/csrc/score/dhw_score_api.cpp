@@ -17,7 +17,7 @@ static int score_impl(dhw_handle* h, const float* strokes, const int64_t* text, 
   if (((uintptr_t)out | (uintptr_t)noise) & 7) return fail(h, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)out & 7) ? "out" : "noise");
 
   EagerCall ec;
-  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec)) || (rc = ensure_scratch(h))) return rc;
+  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec)) || (rc = ensure_scratch(h))) return rc;   // (leaves dhw_sample's text plane alone: forward_enqueue)
   auto& [st, dl, c] = ec;   // the stream, the staged lengths or null, the Ctx of the two small launches (their profiling bracket)
   const dhw_handle::DenoiseScratch& s = h->scratch;   // x = x_t, w = the draw z
   const std::vector<ScoreLevel> table = score_level_table(schedule_abar(T).data(), levels, K);

@@ -132,6 +132,7 @@ DHW_DEV void stage_film_384(char* dst, int S, const T* src, int rows_valid, int 
 
 template <typename T>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void text_style_kernel(const TextStyleParams p) {
+  if (p.skip && *p.skip) return;   // plane reuse: one uniform scalar load, before any LDS use or barrier
   constexpr int ES = sizeof(T), DM = 384, BM = 32, SM = 80, D = 48, KC = DM / 32;
   constexpr int NT = DM / 8 / 16, MT = BM / 16, MTS = SM / 16;
   constexpr int S = tile_stride<T>(DM), SVT = SM * ES + 16;
@@ -331,6 +332,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // DHW_TEXT_PAIRS=2 only.
 template <typename T, int DMO, int PAIRS>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4 / PAIRS, 4 / PAIRS))) void text_layer_kernel(const TextLayerParams p) {
+  if (p.skip && *p.skip) return;   // (as text_style_kernel)
   constexpr int OCC = 2 / PAIRS;
   constexpr int ES = sizeof(T), DI = 384, BM = 32 * PAIRS, KCI = DI / 32, KCO = DMO / 32;
   constexpr int WN = (DMO % 128 == 0) ? 8 : 6, NT = DMO / WN / 16, MT = BM / 16;

@@ -470,6 +470,15 @@ class DiffusionModel(nn.Module):
         """Number of `sample` shapes that ran every denoiser call as ONE persistent launch (csrc/persist.h; 0 = kernel by kernel)."""
         return int(_lib.lib().dhw_debug_persist_plans(self._handle)) if self._handle else 0
 
+    def plane_reuse(self):
+        """(last, calls, reused) of include/dhw.h dhw_debug_plane_reuse: whether the most recent ``sample`` call found the text side
+        of its prompts and styles still in the handle, the ``sample`` calls so far, and how many of them did.  Synchronises."""
+        if self._handle is None:
+            return 0, 0, 0
+        last, calls, reused = C.c_int(), C.c_long(), C.c_long()
+        _lib.check(_lib.lib().dhw_debug_plane_reuse(self._handle, C.byref(last), C.byref(calls), C.byref(reused)), self._handle)
+        return last.value, calls.value, reused.value
+
     def profile(self, on: bool):
         _lib.check(_lib.lib().dhw_profile_enable(self._handle, int(on)), self._handle)
         if on:

@@ -464,6 +464,16 @@ int dhw_prep(const uint8_t* images,   /* device u8 [B,Hin,Win], image b in the t
              int32_t* status_out,     /* device [B] */
              void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Reuse of the text side across calls.  The text side of the sampler (TextStyleEncoder and every layer's text K / V, for all T
+ * steps) depends on text, style, T and the weights only.  A dhw_sample / dhw_sample_ragged / dhw_sample_cond call whose text and
+ * style hold the same BITS as the previous such call's on this handle, at the same B, Lt, T and t_start, with unchanged weights
+ * and switches, finds that result still in the handle and does not evaluate it again; its samples are bit-identical to a call
+ * that does.  Contents are compared on the device at every call, so tensors edited in place are seen.  The first call, and a call
+ * with other prompts or styles, costs what it always did.  bf16 handles, T <= 64; env DHW_PLANE_REUSE=0 at dhw_create turns the
+ * reuse off.  This entry synchronises the device and reports: last = 1 when the most recent such call reused the text side, calls
+ * = how many were enqueued, reused = how many of them reused it.  Any pointer may be NULL. */
+int dhw_debug_plane_reuse(dhw_handle*, int* last, long* calls, long* reused);
+
 /* Host-only: beta_i = 0.02 + exp(linspace(ln 1e-5, ln 0.4, T)), abar = cumprod(1-beta), fp32. */
 int dhw_schedule(int T, float* beta_out, float* alpha_bar_out);
 

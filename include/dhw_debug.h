@@ -69,6 +69,12 @@ int dhw_debug_attention_time(dhw_handle*, int layer, int iters, double* us_with,
  * "nothing throws across the ABI" (include/dhw.h).  Needs no device; the handle may be NULL (message in the global slot). */
 int dhw_debug_raise(dhw_handle*, int kind);
 
+/* The host half of the text-plane reuse decision (csrc/sampler/plane_tag.h), without a handle or a device: 1 when a call
+ * described by `call` may reuse the plane described by `resident`, else 0.  Both are {valid, B, nstreams, Lt, S, T, t_start, weights
+ * generation, FiLM table identity, plane allocation generation}; gates: bit 0 = DHW_PLANE_REUSE on, bit 1 = the all-steps plane in
+ * use, bit 2 = fused bf16 text-side kernels serve the call. */
+int dhw_debug_plane_tag(const int64_t resident[10], const int64_t call[10], int gates);
+
 #ifdef __cplusplus
 }
 #endif
