@@ -3,29 +3,11 @@
 // encode.hip.  No handle, no allocation, no synchronisation, no host read of counts: the call can be captured into a graph.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 
 #include "../../../include/dhw.h"
-#include "../abi_guard.h"
 #include "../host/error.h"
 #include "encode.h"
-
-namespace {
-
-// Errors without a handle are read through dhw_last_error(NULL): the library's one global message slot (host/error.h).
-int efail(int code, const char* fmt, ...) noexcept {
-  va_list ap;
-  va_start(ap, fmt);
-  set_global_error(fmt, ap);
-  va_end(ap);
-  return code;
-}
-// the body of every extern "C" entry point runs inside this: no exception leaves the library (abi_guard.h)
-#define ENCODE_GUARD(fn, R, ...) \
-  return abi_guard<R>(fn, [&](const char* f_, const char* w_) { return efail(DHW_ERR_INTERNAL, "%s: internal error: %s", f_, w_); }, [&]() -> R __VA_ARGS__)
-
-}  // namespace
 
 extern "C" {
 
@@ -33,13 +15,13 @@ size_t dhw_encode_workspace_bytes(int B, int N) { return encode_workspace_bytes(
 
 int dhw_encode(const float* points, const int32_t* counts, int B, int N, int L, int rounds, float max_abs, float* strokes_out,
                int32_t* lens_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  ENCODE_GUARD("dhw_encode", int, {
+  GLOBAL_GUARD("dhw_encode", int, {
     char msg[200];
     if (encode_check_args(points, B, N, L, rounds, max_abs, strokes_out, lens_out, status_out, workspace, workspace_bytes, msg, sizeof msg))
-      return efail(DHW_ERR_ARG, "dhw_encode: %s", msg);
-    if ((uintptr_t)counts & 3) return efail(DHW_ERR_ARG, "dhw_encode: counts must be 4-byte aligned");
+      return global_fail(DHW_ERR_ARG, "dhw_encode: %s", msg);
+    if ((uintptr_t)counts & 3) return global_fail(DHW_ERR_ARG, "dhw_encode: counts must be 4-byte aligned");
     const hipError_t e = launch_encode(points, counts, B, N, L, rounds, max_abs, strokes_out, lens_out, status_out, (hipStream_t)hip_stream);
-    if (e != hipSuccess) return efail(DHW_ERR_HIP, "dhw_encode: launch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return global_fail(DHW_ERR_HIP, "dhw_encode: launch: %s", hipGetErrorString(e));
     return 0;
   });
 }

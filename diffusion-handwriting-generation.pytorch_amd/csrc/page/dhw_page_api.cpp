@@ -3,29 +3,11 @@
 // No handle, no allocation, no synchronisation: the call can be captured into a graph.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 
 #include "../../../include/dhw.h"
-#include "../abi_guard.h"
 #include "../host/error.h"
 #include "page.h"
-
-namespace {
-
-// Errors without a handle are read through dhw_last_error(NULL): the library's one global message slot (host/error.h).
-int pfail(int code, const char* fmt, ...) noexcept {
-  va_list ap;
-  va_start(ap, fmt);
-  set_global_error(fmt, ap);
-  va_end(ap);
-  return code;
-}
-// the body of every extern "C" entry point runs inside this: no exception leaves the library (abi_guard.h)
-#define PAGE_GUARD(fn, R, ...) \
-  return abi_guard<R>(fn, [&](const char* f_, const char* w_) { return pfail(DHW_ERR_INTERNAL, "%s: internal error: %s", f_, w_); }, [&]() -> R __VA_ARGS__)
-
-}  // namespace
 
 extern "C" {
 
@@ -34,19 +16,19 @@ size_t dhw_page_workspace_bytes(int N, int L) { return page_workspace_bytes(N, L
 int dhw_page(const float* strokes, const int32_t* lens, const int32_t* slots, int N, int L, int P, int H, int W, int lines_per_page,
              float margin_left, float margin_top, float pitch, float line_width, float scale, float* pages, float* scale_out,
              float* boxes_out, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  PAGE_GUARD("dhw_page", int, {
+  GLOBAL_GUARD("dhw_page", int, {
     const PageGeometry g{P, H, W, lines_per_page, margin_left, margin_top, pitch, line_width, scale};
     char msg[200];
     if (page_check_args(strokes, N, L, g, pages, scale_out, boxes_out, workspace, workspace_bytes, msg, sizeof msg))
-      return pfail(DHW_ERR_ARG, "dhw_page: %s", msg);
+      return global_fail(DHW_ERR_ARG, "dhw_page: %s", msg);
 
     hipStream_t st = (hipStream_t)hip_stream;
     PageLineHeader* hdr = (PageLineHeader*)workspace;
     float4* segs = (float4*)((char*)workspace + (size_t)N * PAGE_HEADER_BYTES);
     hipError_t e = launch_page_prepare(strokes, lens, slots, N, L, g, hdr, segs, st);
-    if (e != hipSuccess) return pfail(DHW_ERR_HIP, "dhw_page: prepare launch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return global_fail(DHW_ERR_HIP, "dhw_page: prepare launch: %s", hipGetErrorString(e));
     e = launch_page_raster(hdr, segs, N, L, g, pages, scale_out, boxes_out, st);
-    if (e != hipSuccess) return pfail(DHW_ERR_HIP, "dhw_page: raster launch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return global_fail(DHW_ERR_HIP, "dhw_page: raster launch: %s", hipGetErrorString(e));
     return 0;
   });
 }

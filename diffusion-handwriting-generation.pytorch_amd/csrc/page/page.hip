@@ -7,145 +7,25 @@
 //                        page whose placed box meets the tile, then for those lines alone the cull of the line rasteriser
 //                        (ballot + popcount into an LDS chunk) and an exact distance field over the segments of all of them
 // min is exact and commutative and nothing is accumulated with atomics: the pages do not depend on the order of the lines.
-// The scan of the prepare kernel is the one of render/render.hip written again (that file keeps it in an anonymous namespace
-// and is not edited here; DESIGN.md §24 lists the shared header as a later refactor).
+// The scan of a line and the pieces of the raster are those of the line rasteriser: render/line_raster.h.
+#include "../render/line_raster.h"
 #include "page.h"
 
 namespace {
 
-constexpr int LDS_STRIDE = PAGE_ITEMS * 3 + 1;   // 49 floats per thread: odd, so the per-thread reads are conflict-free
-constexpr int WAVES = PAGE_THREADS / 64;
-
-__device__ __forceinline__ float wave_incl_scan(float v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float t = __shfl_up(v, d);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(v, d);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
+using LR = LineRaster<PAGE_THREADS, PAGE_ITEMS, PAGE_TILE_W, PAGE_BAND_H, PAGE_CHUNK>;
 
 __global__ __launch_bounds__(PAGE_THREADS) void page_prepare_kernel(const float* __restrict__ strokes, const int32_t* __restrict__ lens,
                                                                     const int32_t* __restrict__ slots, int L, long long nslots, float pitch,
                                                                     float availw, PageLineHeader* __restrict__ hdr, float4* __restrict__ segs) {
-  __shared__ float s_in[PAGE_THREADS * LDS_STRIDE];
-  __shared__ float s_sum[WAVES][2];
-  __shared__ int s_last[WAVES];
-  __shared__ float s_box[WAVES][4];
-  __shared__ int s_cnt[WAVES];
-
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   int n = lens ? lens[b] : L;
   n = min(max(n, 0), L);   // (the API documents 1 <= n <= L; a bad device-side entry must not read out of bounds)
 
-  // rows at or past n are never read
-  const float* src = strokes + (size_t)b * L * 3;
-  for (int k = tid; k < 3 * n; k += PAGE_THREADS) {
-    const int i = k / 3, c = k - 3 * i;
-    s_in[(i / PAGE_ITEMS) * LDS_STRIDE + (i % PAGE_ITEMS) * 3 + c] = src[k];
-  }
-  __syncthreads();
-
-  // thread t owns strokes [16 t, 16 t + 16): the summation order is a function of the stroke index, not of L, n or N
-  const int i0 = tid * PAGE_ITEMS;
-  float* mine = s_in + tid * LDS_STRIDE;
-  float px[PAGE_ITEMS], py[PAGE_ITEMS];
-  unsigned lift = 0;
-  int last = -1;
-  float sx = 0.f, sy = 0.f;
-#pragma unroll
-  for (int j = 0; j < PAGE_ITEMS; ++j) {
-    if (i0 + j < n) {
-      sx += mine[j * 3];
-      sy += mine[j * 3 + 1];
-      if (rintf(mine[j * 3 + 2]) != 0.f) {   // round-half-to-even, as np.round: 0.5 is not a lift
-        lift |= 1u << j;
-        last = i0 + j;
-      }
-    }
-    px[j] = sx;
-    py[j] = sy;
-  }
-  const float incx = wave_incl_scan(sx, lane), incy = wave_incl_scan(sy, lane);
-  float basex = __shfl_up(incx, 1), basey = __shfl_up(incy, 1);
-  if (lane == 0) basex = basey = 0.f;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) last = max(last, __shfl_xor(last, d));
-  if (lane == 63) {
-    s_sum[wave][0] = incx;
-    s_sum[wave][1] = incy;
-  }
-  if (lane == 0) s_last[wave] = last;
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) {
-    basex += s_sum[w][0];
-    basey += s_sum[w][1];
-  }
-  last = s_last[0];
-#pragma unroll
-  for (int w = 1; w < WAVES; ++w) last = max(last, s_last[w]);
-
-  // positions; each thread leaves its last one in LDS so that segment 16 t starts exactly where segment 16 t - 1 ended
-#pragma unroll
-  for (int j = 0; j < PAGE_ITEMS; ++j) {
-    px[j] += basex;
-    py[j] += basey;
-  }
-  mine[0] = px[PAGE_ITEMS - 1];
-  mine[1] = py[PAGE_ITEMS - 1];
-  __syncthreads();
-  const float prevx = tid ? mine[-LDS_STRIDE] : 0.f, prevy = tid ? mine[1 - LDS_STRIDE] : 0.f;
-
-  // segment i = pos[i-1] -> pos[i] is drawn iff 1 <= i < last and row i is not a lift
-  unsigned drawn = 0;
-  float xmin = 3.0e38f, xmax = -3.0e38f, ymin = 3.0e38f, ymax = -3.0e38f;
-#pragma unroll
-  for (int j = 0; j < PAGE_ITEMS; ++j) {
-    const int i = i0 + j;
-    if (i >= 1 && i < last && !((lift >> j) & 1u)) {
-      drawn |= 1u << j;
-      const float ax = j ? px[j - 1] : prevx, ay = j ? py[j - 1] : prevy;
-      xmin = fminf(xmin, fminf(ax, px[j]));
-      xmax = fmaxf(xmax, fmaxf(ax, px[j]));
-      ymin = fminf(ymin, fminf(ay, py[j]));
-      ymax = fmaxf(ymax, fmaxf(ay, py[j]));
-    }
-  }
-  const int mycnt = __popc(drawn);
-  const int inccnt = wave_incl_scan(mycnt, lane);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    xmin = fminf(xmin, __shfl_xor(xmin, d));
-    xmax = fmaxf(xmax, __shfl_xor(xmax, d));
-    ymin = fminf(ymin, __shfl_xor(ymin, d));
-    ymax = fmaxf(ymax, __shfl_xor(ymax, d));
-  }
-  if (lane == 63) s_cnt[wave] = inccnt;
-  if (lane == 0) {
-    s_box[wave][0] = xmin;
-    s_box[wave][1] = xmax;
-    s_box[wave][2] = ymin;
-    s_box[wave][3] = ymax;
-  }
-  __syncthreads();
-  int off = inccnt - mycnt, total = 0;
-#pragma unroll
-  for (int w = 0; w < WAVES; ++w) {
-    if (w < wave) off += s_cnt[w];
-    total += s_cnt[w];
-    xmin = fminf(xmin, s_box[w][0]);
-    xmax = fmaxf(xmax, s_box[w][1]);
-    ymin = fminf(ymin, s_box[w][2]);
-    ymax = fmaxf(ymax, s_box[w][3]);
-  }
+  LR::Scan sc;
+  LR::scan(strokes + (size_t)b * L * 3, n, sc);
+  const int total = sc.total;
+  const float xmin = sc.xmin, xmax = sc.xmax, ymin = sc.ymin, ymax = sc.ymax;
 
   const int slot = slots ? slots[b] : b;
   if (total == 0 || slot < 0 || (long long)slot >= nslots) {   // draws nothing and takes no part in the scale
@@ -158,21 +38,14 @@ __global__ __launch_bounds__(PAGE_THREADS) void page_prepare_kernel(const float*
   if (ey > 0.f) sn = pitch / ey;                  // one fp32 division each: tests/page_ref.py repeats them bit for bit
   if (ex > 0.f) sn = fminf(sn, availw / ex);
 
-  float4* out = segs + (size_t)b * L + off;
+  float4* out = segs + (size_t)b * L + sc.off;
 #pragma unroll
   for (int j = 0; j < PAGE_ITEMS; ++j) {
-    if ((drawn >> j) & 1u) {
-      const float ax = j ? px[j - 1] : prevx, ay = j ? py[j - 1] : prevy;
-      *out++ = make_float4(ax - xmin, ymax - ay, px[j] - xmin, ymax - py[j]);   // y flipped: image rows go down
-    }
+    if ((sc.drawn >> j) & 1u)
+      *out++ = make_float4(sc.ax(j) - xmin, ymax - sc.ay(j), sc.px[j] - xmin, ymax - sc.py[j]);   // y flipped: image rows go down
   }
   if (tid == 0) hdr[b] = PageLineHeader{total, xmin, ymax, ex, ey, sn, slot, 0};
 }
-
-constexpr int LANES_X = PAGE_TILE_W / 4;                 // 8 lanes across a tile row, four adjacent pixels each
-constexpr int ROWS_PER_PASS = PAGE_THREADS / LANES_X;    // 32
-constexpr int PASSES = PAGE_BAND_H / ROWS_PER_PASS;      // 3
-static_assert(PAGE_CHUNK == PAGE_THREADS, "one cull round of the workgroup fills at most one chunk");
 
 // where a line's ink box lands on its page at scale s: (left, top, right, bottom) in page pixels
 __device__ __forceinline__ float4 place_line(const PageLineHeader& h, float s, int lpp, float margin_left, float margin_top, float pitch) {
@@ -186,18 +59,16 @@ __global__ __launch_bounds__(PAGE_THREADS) void page_raster_kernel(const PageLin
                                                                    float margin_top, float pitch, float line_width, float scale,
                                                                    float* __restrict__ pages, float* __restrict__ scale_out,
                                                                    float* __restrict__ boxes_out) {
-  __shared__ float4 s_seg[PAGE_CHUNK];   // (ax, ay, bx - ax, by - ay) relative to the origin of the tile and band
-  __shared__ float s_inv[PAGE_CHUNK];    // 1 / |b - a|^2, 0 for a zero-length segment (a point)
-  __shared__ int s_cnt[WAVES];
+  __shared__ LR::Chunk s_chunk;          // relative to the origin of the tile and band
   __shared__ int s_line[PAGE_THREADS];   // the lines of one header round that reach this tile, in line order
-  __shared__ int s_lcnt[WAVES];
+  __shared__ int s_lcnt[LR::WAVES];
 
   const int p = blockIdx.x / tiles, tile = blockIdx.x - p * tiles;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int x0 = tile * PAGE_TILE_W, y0 = blockIdx.z * PAGE_BAND_H;
-  const int lx = tid % LANES_X;
+  const int lx = tid % LR::LANES_X;
   const int col = x0 + 4 * lx;
-  const int rloc = tid / LANES_X;        // this lane's row in the first pass, relative to the band
+  const int rloc = tid / LR::LANES_X;       // this lane's row in the first pass, relative to the band
   float* out = pages + (size_t)p * H * W;
 
   // the shared scale: the exact min of s_n over the lines that draw.  Every wave of every workgroup reads all headers (64 at
@@ -240,24 +111,17 @@ __global__ __launch_bounds__(PAGE_THREADS) void page_raster_kernel(const PageLin
   bool any = false;   // (per wave again, and the same in every wave: the white exit below needs no barrier)
   for (int nb = 0; nb < N && !any; nb += 64) any = __ballot(reaches(nb + lane)) != 0ull;
   if (!any) {
-    if (col < W) {
-      const float4 white = make_float4(255.f, 255.f, 255.f, 255.f);
-#pragma unroll
-      for (int q = 0; q < PASSES; ++q) {
-        const int r = y0 + rloc + q * ROWS_PER_PASS;
-        if (r < H) *reinterpret_cast<float4*>(out + (size_t)r * W + col) = white;
-      }
-    }
+    LR::store_white(out, y0 + rloc, col, H, W);
     return;
   }
 
   const float cx = (float)(4 * lx) + 0.5f;   // centre of this lane's first pixel, relative to the tile origin
   // passes of this band that hold a row below H (workgroup-uniform: a scalar branch)
-  const int npass = min(PASSES, (H - y0 + ROWS_PER_PASS - 1) / ROWS_PER_PASS);
+  const int npass = min(LR::PASSES, (H - y0 + LR::ROWS_PER_PASS - 1) / LR::ROWS_PER_PASS);
 
-  float mn[PASSES][4];
+  float mn[LR::PASSES][4];
 #pragma unroll
-  for (int q = 0; q < PASSES; ++q)
+  for (int q = 0; q < LR::PASSES; ++q)
 #pragma unroll
     for (int k = 0; k < 4; ++k) mn[q][k] = 1.0e30f;
 
@@ -269,7 +133,7 @@ __global__ __launch_bounds__(PAGE_THREADS) void page_raster_kernel(const PageLin
     __syncthreads();
     int loff = __popcll(lvote & ((1ull << lane) - 1ull)), nhit = 0;
 #pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
+    for (int w = 0; w < LR::WAVES; ++w) {
       if (w < wave) loff += s_lcnt[w];
       nhit += s_lcnt[w];
     }
@@ -295,65 +159,15 @@ __global__ __launch_bounds__(PAGE_THREADS) void page_raster_kernel(const PageLin
           by = oy + r.w * s;
           keep = fminf(ax, bx) < thi && fmaxf(ax, bx) > tlo && fminf(ay, by) < bhi && fmaxf(ay, by) > blo;
         }
-        const unsigned long long vote = __ballot(keep);
-        if (lane == 0) s_cnt[wave] = __popcll(vote);
-        __syncthreads();
-        int off = __popcll(vote & ((1ull << lane) - 1ull)), kept = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-          if (w < wave) off += s_cnt[w];
-          kept += s_cnt[w];
-        }
-        if (keep) {
-          const float abx = bx - ax, aby = by - ay;
-          const float len2 = abx * abx + aby * aby;
-          s_seg[off] = make_float4(ax - (float)x0, ay - (float)y0, abx, aby);
-          s_inv[off] = len2 > 0.f ? 1.f / len2 : 0.f;
-        }
-        __syncthreads();
-        for (int k = 0; k < kept; ++k) {
-          const float4 a = s_seg[k];   // every lane reads the same address: an LDS broadcast
-          const float inv = s_inv[k];
-          float dx[4], dxab[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            dx[q] = cx + (float)q - a.x;
-            dxab[q] = dx[q] * a.z;
-          }
-#pragma unroll
-          for (int q = 0; q < PASSES; ++q) {
-            if (q >= npass) break;
-            const float dy = (float)(rloc + q * ROWS_PER_PASS) + 0.5f - a.y;
-            const float dyab = dy * a.w;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const float t = fminf(fmaxf((dxab[c] + dyab) * inv, 0.f), 1.f);
-              const float ex = dx[c] - t * a.z, ey = dy - t * a.w;
-              mn[q][c] = fminf(mn[q][c], ex * ex + ey * ey);
-            }
-          }
-        }
+        const int kept = LR::compact(s_chunk, keep, make_float4(ax - (float)x0, ay - (float)y0, bx - ax, by - ay));
+        LR::min_dist2(s_chunk, kept, cx, rloc, npass, mn);
         __syncthreads();   // the next round overwrites the chunk
       }
     }
     __syncthreads();   // the next header round overwrites the line list
   }
 
-  if (col < W) {
-#pragma unroll
-    for (int q = 0; q < PASSES; ++q) {
-      const int r = y0 + rloc + q * ROWS_PER_PASS;
-      if (r < H) {
-        float v[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float cov = fminf(fmaxf(radius - sqrtf(mn[q][c]), 0.f), 1.f);
-          v[c] = 255.f * (1.f - cov);
-        }
-        *reinterpret_cast<float4*>(out + (size_t)r * W + col) = make_float4(v[0], v[1], v[2], v[3]);
-      }
-    }
-  }
+  LR::store_coverage(out, y0 + rloc, col, H, W, radius, mn);
 }
 
 }  // namespace

@@ -3,29 +3,11 @@
 // prep.hip.  No handle, no allocation, no synchronisation, no host read of sizes or boxes: the call can be captured into a graph.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 
 #include "../../../include/dhw.h"
-#include "../abi_guard.h"
 #include "../host/error.h"
 #include "prep.h"
-
-namespace {
-
-// Errors without a handle are read through dhw_last_error(NULL): the library's one global message slot (host/error.h).
-int pfail(int code, const char* fmt, ...) noexcept {
-  va_list ap;
-  va_start(ap, fmt);
-  set_global_error(fmt, ap);
-  va_end(ap);
-  return code;
-}
-// the body of every extern "C" entry point runs inside this: no exception leaves the library (abi_guard.h)
-#define PREP_GUARD(fn, R, ...) \
-  return abi_guard<R>(fn, [&](const char* f_, const char* w_) { return pfail(DHW_ERR_INTERNAL, "%s: internal error: %s", f_, w_); }, [&]() -> R __VA_ARGS__)
-
-}  // namespace
 
 extern "C" {
 
@@ -33,14 +15,14 @@ size_t dhw_prep_workspace_bytes(int B) { return prep_workspace_bytes(B); }
 
 int dhw_prep(const uint8_t* images, const int32_t* sizes, int B, int Hin, int Win, int H, int W, int thresh, float* img_out,
              int32_t* widths_out, int32_t* boxes_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  PREP_GUARD("dhw_prep", int, {
+  GLOBAL_GUARD("dhw_prep", int, {
     char msg[200];
     if (prep_check_args(images, sizes, B, Hin, Win, H, W, thresh, img_out, widths_out, boxes_out, status_out, workspace, workspace_bytes, msg,
                         sizeof msg))
-      return pfail(DHW_ERR_ARG, "dhw_prep: %s", msg);
+      return global_fail(DHW_ERR_ARG, "dhw_prep: %s", msg);
     const hipError_t e = launch_prep(images, sizes, B, Hin, Win, H, W, thresh, img_out, widths_out, boxes_out, status_out, (int32_t*)workspace,
                                      (hipStream_t)hip_stream);
-    if (e != hipSuccess) return pfail(DHW_ERR_HIP, "dhw_prep: launch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return global_fail(DHW_ERR_HIP, "dhw_prep: launch: %s", hipGetErrorString(e));
     return 0;
   });
 }

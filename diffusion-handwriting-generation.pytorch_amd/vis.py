@@ -8,15 +8,17 @@ import numpy as np
 RENDER_CHUNK = 256   # segments per LDS chunk of the raster kernel (csrc/render/render.h RENDER_CHUNK): a tile that keeps more
                      # than this many segments goes through several chunks
 RENDER_TILE_W = 32   # columns per raster tile (csrc/render/render.h RENDER_TILE_W)
-_render_workspaces = {}   # device index -> [uint8 workspace tensors of render_strokes, the newest (largest) last]
+# device index -> [uint8 workspace tensors, the newest (largest) last]: one cache per call, so each keeps its own buffers
+_render_workspaces = {}   # of render_strokes
+_page_workspaces = {}     # of render_page
 
 
-def _render_workspace(dev, need: int):
-    """One workspace per device, grown by doubling.  Outgrown buffers stay referenced (a captured graph may still point at
-    one): at most one per doubling, together smaller than the newest."""
+def _workspace(cache: dict, dev, need: int):
+    """One workspace per device in `cache`, grown by doubling.  Outgrown buffers stay referenced (a captured graph may still
+    point at one): at most one per doubling, together smaller than the newest."""
     import torch
 
-    bufs = _render_workspaces.setdefault(dev.index, [])
+    bufs = cache.setdefault(dev.index, [])
     if not bufs or bufs[-1].numel() < need:
         size = 1 << 16
         while size < need:
@@ -109,7 +111,7 @@ def render_strokes(strokes, lengths=None, height: int = 96, width: int = 1400, l
             if lens.numel() != B:
                 raise ValueError(f"lengths must hold {B} entries")
         need = int(l.dhw_render_workspace_bytes(B, L))
-        ws = _render_workspace(dev, need) if need else None
+        ws = _workspace(_render_workspaces, dev, need) if need else None
         images = torch.empty((B, 1, int(height), int(width)), device=dev, dtype=torch.float32)
         widths = torch.empty((B,), device=dev, dtype=torch.int32)
         st = torch.cuda.current_stream(dev)
@@ -130,20 +132,6 @@ def save_line_png(image, width, name: str) -> None:
 
 
 PAGE_MAX_N = PAGE_MAX_L = 4096   # csrc/page/page_host.h
-_page_workspaces = {}            # device index -> [uint8 workspace tensors of render_page, the newest (largest) last]
-
-
-def _page_workspace(dev, need: int):
-    """As _render_workspace, for render_page: one per device, grown by doubling, outgrown buffers stay referenced."""
-    import torch
-
-    bufs = _page_workspaces.setdefault(dev.index, [])
-    if not bufs or bufs[-1].numel() < need:
-        size = 1 << 16
-        while size < need:
-            size *= 2
-        bufs.append(torch.empty(size, dtype=torch.uint8, device=dev))
-    return bufs[-1]
 
 
 def _page_int(name: str, v, lo: int) -> int:
@@ -276,7 +264,7 @@ def render_page(strokes, lengths=None, slots=None, *, pages=None, height: int = 
 
         lens, slot_t = ints(host_lens, lengths), ints(host_slots, slots)
         need = int(l.dhw_page_workspace_bytes(N, L))
-        ws = _page_workspace(dev, need)
+        ws = _workspace(_page_workspaces, dev, need)
         out = torch.empty((P, 1, g["height"], g["width"]), device=dev, dtype=torch.float32)
         scale_out = torch.empty((1,), device=dev, dtype=torch.float32)
         boxes = torch.empty((N, 4), device=dev, dtype=torch.float32)

@@ -3,12 +3,12 @@
 The drawn set of every line comes from vis.strokes_to_polylines (pinned to the reference's show_strokes by golden/vis.npz).
 Positions, boxes and pixels are float64; the per-line scale limits s_n and the shared scale s are formed with np.float32
 divisions exactly as the header states them, so that the scale can be compared bit for bit on inputs whose prefix sums are
-exact in fp32 (offsets that are multiples of 1/16: ``make_strokes``, the generator of tests/test_gpu_render.py)."""
+exact in fp32 (offsets that are multiples of 1/16: ``make_strokes``, which tests/test_gpu_render.py uses too)."""
 import numpy as np
 
 from dhg_amd import vis
 
-PENS = np.array([0.02, 0.3, 0.5, 0.7, 0.98])   # (the pen values of tests/test_gpu_render.py: none rounds differently in fp32)
+PENS = np.array([0.02, 0.3, 0.5, 0.7, 0.98])   # (none rounds differently in fp32)
 
 
 def make_strokes(rng, B, L, lift_p=0.08):

@@ -1,7 +1,7 @@
 """The page compositor on the GPU (include/dhw.h dhw_page, dhg_amd.render_page / write_page) against tests/page_ref.py, the
 float64 brute-force statement of the rules whose drawn set comes from vis.strokes_to_polylines.
 
-Inputs (page_ref.make_strokes, the generator of tests/test_gpu_render.py): offsets are multiples of 1/16, pen values come from
+Inputs (page_ref.make_strokes, as tests/test_gpu_render.py): offsets are multiples of 1/16, pen values come from
 {0.02, 0.3, 0.5, 0.7, 0.98}; margins and pitch are multiples of 1/16.  Every fp32 prefix sum, box and extent is therefore
 exact in any summation order, the two fp32 divisions behind the scale are the reference's, and the shared scale is compared
 bit for bit.  Every page is below 512 px on a side, so what is left of the fp32 error is the derivation of
@@ -165,18 +165,54 @@ def test_shapes_off_the_tile_grid():
 # ---------------------------------------------------------------- 7: cull and chunk stress
 def test_cull_and_chunk_stress():
     geo = dict(pages=1, height=96, width=128, lines_per_page=2, margin_left=4.0, margin_top=4.0, pitch=44.0)
-    L = 1024
-    st = page_ref.make_strokes(np.random.default_rng(15), 2, L, lift_p=0.03)
+    L, L2 = 1024, 1040
+    st = np.full((3, L2, 3), np.nan, np.float32)                       # rows past each length are never read
+    st[:2, :L] = page_ref.make_strokes(np.random.default_rng(15), 2, L, lift_p=0.03)
     i = np.arange(L)
-    st[0, :, 0] = np.where(i % 2 == 0, 5.0, -5.0)                      # a zig-zag: ~1000 segments inside a dozen columns
-    st[0, :, 1] = np.where((i // 100) % 2 == 0, 0.25, -0.25)
-    st[0, :, 2] = 0.3
+    st[0, :L, 0] = np.where(i % 2 == 0, 5.0, -5.0)                      # a zig-zag: ~1000 segments inside a dozen columns
+    st[0, :L, 1] = np.where((i // 100) % 2 == 0, 0.25, -0.25)
+    st[0, :L, 2] = 0.3
     st[0, [500, L - 1], 2] = [0.7, 0.98]
-    lens = [L, 60]
     st[1, 59, 2] = 0.98
-    im, ref, boxes_ref, counts = check_against_ref(st, lens, None, geo, label="stress")
+    # line 2: 1040 strokes, so thread 64 — the first of the second wave — takes part in the scan: its positions start from the
+    # first wave's sum, the last lift sits in it, and segments are drawn on both sides of stroke 1024.  (The generator's
+    # offsets less the mean of dx and divided by 4: on the 1/64 grid with sums below 2^11, still exact in fp32, and small
+    # enough that line 0 keeps setting the scale.)
+    st[2] = page_ref.make_strokes(np.random.default_rng(151), 1, L2, lift_p=0.03)[0]
+    st[2, :, :2] = (st[2, :, :2] - np.float32([0.625, 0.0])) / 4
+    st[2, 1016:1036, 2] = 0.3                                          # pen down across the wave boundary ...
+    st[2, [1036, L2 - 1], 2] = [0.7, 0.98]                             # ... then a lift, and one on the last stroke
+    lens, slots = [L, 60, L2], [0, 1, 1]
+    pages, sc, boxes = got = dhg_amd.render_page(st, lens, slots, **geo)
+    im, ref, boxes_ref, counts = check_against_ref(st, lens, slots, geo, label="stress", got=got)
     assert counts[0] > 3 * 256 and counts[1] > 0                       # more than any one LDS chunk holds ...
     assert boxes_ref[0, 2] + 1.5 < 32                                  # ... all of it in the first 32-column tile
+    lifts = np.round(st[2, :, 2]) != 0
+    assert not lifts[1016:1036].any() and lifts[1036] and lifts[1039] and counts[2] > 900   # segments 1016..1035 are drawn
+    alone, sc1, box1 = dhg_amd.render_page(st[2:3].copy(), None, [1], scale=float(sc[0]), **geo)   # the line alone at L = 1040
+    others, _, _ = dhg_amd.render_page(st[:2, :L].copy(), lens[:2], slots[:2], scale=float(sc[0]), **geo)
+    assert torch.equal(box1[0], boxes[2]) and torch.equal(torch.minimum(alone, others), pages)
+
+
+def test_second_header_round_is_the_min_of_its_lines_alone():
+    """260 lines on one page: the raster kernel takes the headers 256 at a time, so lines 256..259 come in a second round."""
+    geo = dict(pages=1, height=96, width=128, lines_per_page=4, margin_left=4.0, margin_top=4.0, pitch=22.0)
+    N, L, s = 260, 8, 4.0
+    st = page_ref.make_strokes(np.random.default_rng(17), N, L, lift_p=0.0)
+    st[:, L - 1, 2] = 0.98
+    st[257, :, 0] = 3.0                                                # one line of the second round reaches past all others
+    slots = [n % 4 for n in range(N)]
+    pages, sc, boxes = got = dhg_amd.render_page(st, None, slots, scale=s, **geo)
+    im, ref, boxes_ref, counts = check_against_ref(st, None, slots, geo, scale=s, label="260 lines", got=got)
+    assert all(c == L - 2 for c in counts) and boxes_ref[257, 2] > boxes_ref[:256, 2].max() + 4
+    want = torch.full_like(pages, 255.0)
+    for n in range(N):
+        if n == 256:
+            assert not torch.equal(want, pages)                        # the first round alone is not the page
+        alone, _, box1 = dhg_amd.render_page(st[n:n + 1], None, [slots[n]], scale=s, **geo)
+        assert torch.equal(box1[0], boxes[n])
+        want = torch.minimum(want, alone)
+    assert torch.equal(want, pages)                                    # bit for bit
 
 
 # ---------------------------------------------------------------- 8: graph capture

@@ -5,6 +5,8 @@ Inputs: offsets are multiples of 1/16 (dx = round(N(0.6,1) 16)/16, dy = round(N(
 {0.02, 0.3, 0.5, 0.7, 0.98}, so every fp32 prefix sum and the box are exact in any summation order.  What is left of the
 fp32 error is a handful of roundings on pixel coordinates below 512, each at most 3e-5 px: about 0.07 grey levels in the
 worst case.  The image tolerance is max abs diff <= 0.5 grey levels (~7x that bound); widths agree within +-1."""
+import os
+import sys
 import warnings
 
 import numpy as np
@@ -14,10 +16,12 @@ import torch
 import dhg_amd
 from dhg_amd import spec, vis
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from page_ref import make_strokes  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 TOL = 0.5
-PENS = np.array([0.02, 0.3, 0.5, 0.7, 0.98])
 
 
 def ref_render(strokes, n, H, W, lw=2.0):
@@ -59,13 +63,6 @@ def ref_render(strokes, n, H, W, lw=2.0):
     d = np.sqrt(d2).reshape(H, W)
     img = 255.0 * (1 - np.clip(lw / 2 + 0.5 - d, 0, 1))
     return img, min(W, int(np.ceil(ex * sc + 2 * m))), len(A), voff
-
-
-def make_strokes(rng, B, L, lift_p=0.08):
-    dx = np.round(rng.normal(0.6, 1.0, (B, L)) * 16) / 16
-    dy = np.round(rng.normal(0.0, 1.0, (B, L)) * 16) / 16
-    pen = np.where(rng.random((B, L)) < lift_p, rng.choice(PENS[3:], (B, L)), rng.choice(PENS[:3], (B, L)))
-    return np.stack([dx, dy, pen], -1).astype(np.float32)
 
 
 def check_against_ref(strokes, lens, images, widths, H, W, lw=2.0, label=""):
@@ -146,19 +143,26 @@ def test_degenerate_rows_in_one_batch():
 
 
 _stress = {}
+STRESS_LENS = [1000, 1000, 1040]
 
 
 def _stress_batch():
     """Row 0: a zig-zag whose ~1000 drawn segments all fall inside about 24 columns — several LDS chunks for one tile, the
     running minimum must survive the chunk boundaries.  Row 1: a left-to-right line with two segments that run across half
-    the picture (several tile borders each).  Rendered once, shared by the two cases."""
+    the picture (several tile borders each).  Row 2: 1040 strokes, so thread 64 — the first of the second wave — takes part
+    in the scan: its positions start from the first wave's sum, the last lift sits in it, and segments are drawn on both
+    sides of stroke 1024.  Rendered once, shared by the three cases."""
     if not _stress:
-        B, L, H, W = 2, 1000, 96, 512
-        st = make_strokes(np.random.default_rng(4), B, L, lift_p=0.03)
+        L, L2, H, W = 1000, 1040, 96, 512
+        st = np.full((3, L2, 3), np.nan, np.float32)                   # rows past each length are never read
+        st[:2, :L] = make_strokes(np.random.default_rng(4), 2, L, lift_p=0.03)
+        st[2] = make_strokes(np.random.default_rng(41), 1, L2, lift_p=0.03)[0]
+        st[2, 1016:1036, 2] = 0.3                                      # pen down across the wave boundary ...
+        st[2, [1036, L2 - 1], 2] = [0.7, 0.98]                         # ... then a lift, and one on the last stroke
         i = np.arange(L)
-        st[0, :, 0] = np.where(i % 2 == 0, 5.0, -5.0)
-        st[0, :, 1] = np.where((i // 100) % 2 == 0, 0.25, -0.25)
-        st[0, :, 2] = 0.3
+        st[0, :L, 0] = np.where(i % 2 == 0, 5.0, -5.0)
+        st[0, :L, 1] = np.where((i // 100) % 2 == 0, 0.25, -0.25)
+        st[0, :L, 2] = 0.3
         st[0, [500, L - 1], 2] = [0.7, 0.98]
         st[1, L - 1, 2] = 0.98
         st[1, 498:503, 2] = 0.3
@@ -166,18 +170,24 @@ def _stress_batch():
         assert back > 100
         st[1, 500, :2] = [-back, 0.0]                                  # pen down, back to the start of the line ...
         st[1, 501, :2] = [back, 0.0]                                   # ... and forth again
-        _stress["v"] = (st, *dhg_amd.render_strokes(st, height=H, width=W), H, W)
+        _stress["v"] = (st, *dhg_amd.render_strokes(st, STRESS_LENS, height=H, width=W), H, W)
     return _stress["v"]
 
 
-@pytest.mark.parametrize("row", [0, 1])
+@pytest.mark.parametrize("row", [0, 1, 2])
 def test_cull_and_chunk_stress(row):
     st, img, wd, H, W = _stress_batch()
-    (_, wref, nseg, _), = check_against_ref(st[row:row + 1], None, img[row:row + 1], wd[row:row + 1], H, W, label=f"stress[{row}]")
+    (_, wref, nseg, _), = check_against_ref(st[row:row + 1], STRESS_LENS[row:row + 1], img[row:row + 1], wd[row:row + 1], H, W,
+                                            label=f"stress[{row}]")
     if row == 0:
         assert nseg > 3 * vis.RENDER_CHUNK and wref <= 28              # more than any one chunk holds, all in one tile
-    else:
+    elif row == 1:
         assert wref == W and nseg > 900                                # row 1 spans every tile
+    else:
+        lifts = np.round(st[2, :, 2]) != 0
+        assert not lifts[1016:1036].any() and lifts[1036] and lifts[1039] and nseg > 900   # segments 1016..1035 are drawn
+        alone, walone = dhg_amd.render_strokes(st[2:3].copy(), height=H, width=W)          # the line alone at L = 1040
+        assert torch.equal(alone[0], img[2]) and int(walone[0]) == int(wd[2])
 
 
 def test_graph_capture_on_a_side_stream_replays_bit_identically():
