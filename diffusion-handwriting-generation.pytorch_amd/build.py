@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdhw_hip.so")
 # (the slowest units first: the pool takes them in this order, and the longest compile bounds a clean build)
 SOURCES = ["train/sgemm_f32.hip", "train/sgemm_bf16.hip", "train/sgemm_group.hip", "convblock.hip", "ragged/convblock_ragged.hip", "enclayer.hip",
-           "ragged/enclayer_ragged.hip", "gemm.hip", "ragged/gemm_ragged.hip", "ragged/attn_ragged.hip", "persist.hip", "attn.hip", "misc.hip", "style.hip", "textside.hip",
+           "ragged/enclayer_ragged.hip", "policy/convblock_policy.hip", "policy/enclayer_policy.hip", "gemm.hip", "ragged/gemm_ragged.hip", "ragged/attn_ragged.hip", "persist.hip", "attn.hip", "misc.hip", "style.hip", "textside.hip",
            "train.hip", "train/sgemm_launch.hip", "train/elementwise.hip", "train/film_table.hip", "render/render.hip", "cond/cond.hip", "score/score.hip", "attnmap/attnmap.hip",
            "dhw_api.cpp", "dhw_style_api.cpp", "dhw_train_api.cpp",
            "render/dhw_render_api.cpp", "cond/dhw_cond_api.cpp", "score/dhw_score_api.cpp", "attnmap/dhw_attnmap_api.cpp", "sampler/weights.cpp", "sampler/workspace.cpp", "sampler/denoiser.cpp", "sampler/sample.cpp", "sampler/debug.cpp",
@@ -49,7 +49,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         src = os.path.join(CSRC, s)
         obj = _obj(objdir, s)
         # ragged/<f>_ragged.hip: <f>.hip compiled with per-sample lengths (csrc/dhw_kernels.h, DHW_LENS)
-        base = [os.path.join(CSRC, os.path.basename(s).replace("_ragged", ""))] if s.startswith("ragged/") else []
+        # policy/<f>_policy.hip: <f>.hip compiled with the copy-outs' store policy read at run time (DHW_STORE_RT)
+        base = [os.path.join(CSRC, os.path.basename(s).replace("_ragged", "").replace("_policy", ""))] if s.startswith(("ragged/", "policy/")) else []
         if force or _stale(obj, [src] + base + headers):
             cmd = [hipcc, *FLAGS, "-x", "hip", "-c", src, "-o", obj]
             jobs.append(cmd)

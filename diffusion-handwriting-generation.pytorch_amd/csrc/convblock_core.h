@@ -443,7 +443,7 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
     CB_BARRIER();
     // (ping-pong, fp32 tile: both halves stored in the same slot — the leading half waited in front of it)
     if (p.out)
-      tile_copy_out<float>(smem, SO, reinterpret_cast<float*>(p.out) + (size_t)(b * p.L + m0) * CO, CO, rows_valid, CO, tid, NTHR);
+      tile_copy_out<float>(smem, SO, reinterpret_cast<float*>(p.out) + (size_t)(b * p.L + m0) * CO, CO, rows_valid, CO, tid, NTHR, DHW_STORE_OF(p.store, 0));
     if (p.fuse_heads) {
       // eps / pen heads (model.py:179-182) + scheduler step straight from the fp32 tile: 4 lanes per stroke row
       const int r = tid >> 2, q = tid & 3;
@@ -470,6 +470,7 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
       }
       if (r < rows_valid && q == 0) heads_finish(p.hp, (long)b * p.L + m0 + r, a0, a1, a2);
     }
+    if (DHW_STORE_OF(p.store, 0) == STORE_EARLY && p.out) tile_release_early(tid);
   } else {
     if (act2) {
 #pragma unroll
@@ -481,9 +482,10 @@ DHW_DEV void convblock_body(const P& p, const X& nx, const int b, const int m0, 
     CB_BARRIER();
     if constexpr (PPX) { if (pp_lead) CB_BARRIER(); }   // the trailing half stores its rows one slot later
     if constexpr (!(DHW_ABL & 16))
-    tile_copy_out<T>(smem, SH2, reinterpret_cast<T*>(p.out) + (size_t)(b * p.L + m0) * CO, CO, rows_valid, CO, tid, NTHR);
+    tile_copy_out<T>(smem, SH2, reinterpret_cast<T*>(p.out) + (size_t)(b * p.L + m0) * CO, CO, rows_valid, CO, tid, NTHR, DHW_STORE_OF(p.store, 0));
     if (p.pool && !(DHW_ABL & 16))   // AvgPool1d(2) side output (model.py:93); m0 and rows_valid are even
-      tile_copy_out_pool<T>(smem, SH2, reinterpret_cast<T*>(p.pool) + ((size_t)b * (p.L / 2) + m0 / 2) * CO, CO, rows_valid, CO, tid, NTHR);
+      tile_copy_out_pool<T>(smem, SH2, reinterpret_cast<T*>(p.pool) + ((size_t)b * (p.L / 2) + m0 / 2) * CO, CO, rows_valid, CO, tid, NTHR, DHW_STORE_OF(p.store, 0));
+    if (DHW_STORE_OF(p.store, 0) == STORE_EARLY) tile_release_early(tid);
     if constexpr (CH == 1) {
       // the output tile (rows [m0, m0 + rows_valid), row stride SH2 = tile_stride(CO)) is the next layer's x tile
       static_assert(NW == 8 && sizeof(T) == 2, "enc_a_body runs on 8 waves");

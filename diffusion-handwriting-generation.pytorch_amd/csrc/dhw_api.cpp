@@ -100,6 +100,15 @@ int dhw_create(dhw_handle** out, const dhw_dims* dims, int device) {
     if (const char* e = getenv("DHW_PERSIST")) h->persist = atoi(e) != 0;
     if (const char* e = getenv("DHW_PLANE_REUSE")) h->plane_reuse = atoi(e) != 0;
     if (const char* e = getenv("DHW_TEXT_PAIRS")) h->text_pairs = atoi(e) == 1 ? 1 : atoi(e) == 2 ? 2 : 0;
+    if (const char* e = getenv("DHW_STORE_POLICY")) {
+      const long v = strtol(e, nullptr, 0);
+      bool ok = v >= 0 && v < 64;
+      for (int cls = 0; ok && cls < 3; ++cls) ok = store_policy_of((int)v, cls) != 3;
+      if (!ok && !rc) rc = fail(h, DHW_ERR_ARG, "DHW_STORE_POLICY=%s: two bits per output class (C, A, B from bit 0), each 0 = plain, 1 = write-through, 2 = early release", e);
+      if (ok) h->store_policy = (int)v;
+    }
+    if (!rc && h->store_policy != DHW_STORE_DEFAULT && (enclayer_init_policy() != hipSuccess || convblock_init_policy() != hipSuccess))
+      rc = fail(h, DHW_ERR_HIP, "kernel attribute setup failed: %s", hipGetErrorString(hipGetLastError()));
     if (h->padded) h->fuse = false;   // (pad_weights: the fused block kernels have compile-time LayerNorm widths)
     if (!rc && h->prec == PREC_BF16 && h->persist) {
       hipDeviceProp_t prop;

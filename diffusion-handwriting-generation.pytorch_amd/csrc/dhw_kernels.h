@@ -13,6 +13,26 @@ enum { PREC_BF16 = 0, PREC_F32 = 1 };
 #define DHW_LENS 0
 #endif
 
+// How a stroke kernel's tile copy-out stores its 16-byte pieces (gemm_core.h tile_copy_out); the stored bytes never differ.
+// One value per output class (dhw_create reads DHW_STORE_POLICY, two bits per class: C = bits 0-1, A = bits 2-3, B = bits 4-5):
+//   C  ConvBlock out / pool;  A  enc_a's x2 and qk2 rows;  B  enc_bc's out / pool and the chained att_dense output.
+enum { STORE_PLAIN = 0, STORE_WT = 1, STORE_EARLY = 2 };
+constexpr int store_policy_of(int word, int cls) { return (word >> (2 * cls)) & 3; }   // cls: 0 = C, 1 = A, 2 = B
+// DHW_STORE_DEFAULT: the policy word of a handle created without DHW_STORE_POLICY — every class write-through (measured).
+// The stroke kernels are compiled twice, like the ragged ones: convblock.hip / enclayer.hip with that word COMPILED IN (no selection in
+// the kernels: a run-time branch around the copy loops cost more than the policy gains), and policy/*_policy.hip — with
+// ragged/*_ragged.hip and persist.hip — with DHW_STORE_RT, where the copy-outs select on the parameter blocks' fields (the launchers
+// there carry a _policy suffix; denoiser.cpp picks them for a handle whose word is not the default).
+#define DHW_STORE_DEFAULT 21
+#ifdef DHW_STORE_RT
+#define DHW_STORE_OF(field, cls) (field)
+#else
+#ifndef DHW_STORE_FIXED
+#define DHW_STORE_FIXED DHW_STORE_DEFAULT   // (-DDHW_STORE_FIXED=<word>: A/B builds of another compiled-in word)
+#endif
+#define DHW_STORE_OF(field, cls) store_policy_of(DHW_STORE_FIXED, cls)
+#endif
+
 // ---------------------------------------------------------------- fused GEMM
 // out[b, m, n] = epilogue( sum_seg sum_tap sum_c  act_seg[b, m + tap - halo, c] * W_seg[n][tap*C + c] )
 // All activations are C-last [B, L, C] of the handle's element type.
@@ -112,11 +132,14 @@ struct ConvBlockParams {
   unsigned long long* stamps;         // diagnostics only: per-stage s_memrealtime of workgroup 0, or null
   int stagger;                        // two-workgroups-per-CU variants: the second half of the grid starts this many x 0.5 us late
   const int* lens; int lsh;           // per-sample lengths (GemmParams.lens): sample b has lens[b] >> lsh rows, or null = L; tiles past it exit
+  int store;                          // STORE_* of out / pool (class C)
 };
 hipError_t launch_convblock(int prec, const ConvBlockParams& p, hipStream_t st);
 hipError_t convblock_init();
 hipError_t launch_convblock_ragged(int prec, const ConvBlockParams& p, hipStream_t st);   // p.lens honoured (ragged/convblock_ragged.hip)
 hipError_t convblock_init_ragged();
+hipError_t launch_convblock_policy(int prec, const ConvBlockParams& p, hipStream_t st);   // p.store honoured (policy/convblock_policy.hip)
+hipError_t convblock_init_policy();
 
 // ---------------------------------------------------------------- fused EncoderLayer stroke side (model.py:37-58), two launches
 struct EncLayerParams {
@@ -135,6 +158,7 @@ struct EncLayerParams {
   int dbg;                                         // diagnostics only: bit0 = skip the attention stage (a = q)
   unsigned long long* stamps;                      // diagnostics only: per-stage s_memrealtime of workgroup 0 (16 slots per kernel) or null
   const int* lens; int lsh;                        // per-sample lengths (GemmParams.lens): sample b has lens[b] >> lsh rows and as many keys, or null = Lk
+  int store_a, store_bc;                           // STORE_* of enc_a's x2 / qk2 rows (class A) and of enc_bc's out / pool (class B)
 };
 // What an enc_bc (or ConvBlock) workgroup goes on to compute for its own rows after its own block — the stages up to the
 // next self-attention are row-local, so they need no launch boundary:
@@ -144,12 +168,13 @@ struct EncChain {
   int mode;                  // 0 = none
   EncLayerParams a;          // the next layer (a.x unused: the tile is already in LDS)
   const void* w_dense; const float* b_dense;   // mode 2: packed weight [a.d x d], bias [a.d]
-  void* dense_out;           // mode 2: Linear output [B*Lk/2, a.d] (kept for debug taps)
+  void* dense_out;           // mode 2: Linear output [B*Lk/2, a.d] (kept for debug taps and dhw_attention); stored under the launching layer's store_bc
 };
 // A ConvBlock whose output feeds an EncoderLayer continues into that layer's enc_a on its own output tile (mode 1).
 bool convblock_chain_supported(int prec, const ConvBlockParams& p, const EncChain& chain);
 hipError_t launch_convblock_chain(int prec, const ConvBlockParams& p, const EncChain& chain, hipStream_t st);
 hipError_t launch_convblock_chain_ragged(int prec, const ConvBlockParams& p, const EncChain& chain, hipStream_t st);
+hipError_t launch_convblock_chain_policy(int prec, const ConvBlockParams& p, const EncChain& chain, hipStream_t st);
 bool convblock_chain_auto(const ConvBlockParams& p);   // the chain is a measured win for this launch geometry (enc4 on the asymmetric 32-row tiles)
 bool enclayer_supported(int prec, int d, int heads);
 // whether enc_bc of a (d, B, Lk) layer can continue with `mode`; mode 2 needs EncLayerParams.bm_min = 32 on that layer
@@ -158,6 +183,8 @@ hipError_t launch_enclayer(int prec, const EncLayerParams& p, int which, hipStre
 hipError_t enclayer_init();
 hipError_t launch_enclayer_ragged(int prec, const EncLayerParams& p, int which, hipStream_t st, const EncChain* chain);   // p.lens honoured
 hipError_t enclayer_init_ragged();
+hipError_t launch_enclayer_policy(int prec, const EncLayerParams& p, int which, hipStream_t st, const EncChain* chain);   // p.store_a / store_bc honoured
+hipError_t enclayer_init_policy();
 
 // ---------------------------------------------------------------- attention
 struct AttnParams {

@@ -351,9 +351,10 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
   }
   lds_barrier();
   const int rows_valid = min(BM, Ls - m0);
-  tile_copy_out<T>(R3, S, reinterpret_cast<T*>(p.out) + (size_t)(b * p.Lk + m0) * DM, DM, rows_valid, DM, tid, 512);
+  tile_copy_out<T>(R3, S, reinterpret_cast<T*>(p.out) + (size_t)(b * p.Lk + m0) * DM, DM, rows_valid, DM, tid, 512, DHW_STORE_OF(p.store_bc, 2));
   if (p.pool)
-    tile_copy_out_pool<T>(R3, S, reinterpret_cast<T*>(p.pool) + ((size_t)b * (p.Lk / 2) + m0 / 2) * DM, DM, rows_valid, DM, tid, 512);
+    tile_copy_out_pool<T>(R3, S, reinterpret_cast<T*>(p.pool) + ((size_t)b * (p.Lk / 2) + m0 / 2) * DM, DM, rows_valid, DM, tid, 512, DHW_STORE_OF(p.store_bc, 2));
+  if (NEXT != 2 && DHW_STORE_OF(p.store_bc, 2) == STORE_EARLY) tile_release_early(tid);   // (NEXT == 2: behind the att_dense copy-out below)
   STAMP(24);
   WST(24);
   DHW_STAMP_IF(p.stamps && blockIdx.x == 0 && threadIdx.x == 0, 41, __builtin_amdgcn_s_memtime());
@@ -403,7 +404,8 @@ DHW_DEV void enc_bc_body(const P& p, const X& nx, const int b, const int m0, cha
     }
     lds_barrier();
     const int m02 = m0 / 2, rows2 = rows_valid / 2;
-    tile_copy_out<T>(XN, SN, reinterpret_cast<T*>(nx.dense_out) + (size_t)(b * (p.Lk / 2) + m02) * DN, DN, rows2, DN, tid, 512);
+    tile_copy_out<T>(XN, SN, reinterpret_cast<T*>(nx.dense_out) + (size_t)(b * (p.Lk / 2) + m02) * DN, DN, rows2, DN, tid, 512, DHW_STORE_OF(p.store_bc, 2));
+    if (DHW_STORE_OF(p.store_bc, 2) == STORE_EARLY) tile_release_early(tid);
     EncALds m;
     m.XR = XN; m.QR = XN + BN2 * SN; m.red = red;
     m.KT = reinterpret_cast<char*>(red) + 2 * 8 * BM * sizeof(float);

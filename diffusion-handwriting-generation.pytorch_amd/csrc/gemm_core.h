@@ -3,6 +3,7 @@
 // LDS tile geometry, and the cross-wave LayerNorm.
 #pragma once
 #include "dhw_common.h"
+#include "dhw_kernels.h"
 #include "epilogue.h"
 
 // An activation tile in LDS: `rows` rows of C elements, row stride padded by 16 bytes so the
@@ -289,22 +290,77 @@ DHW_DEV void mainloop(f32x4 (&acc)[NT][MT], const T* __restrict__ wbase, const c
 // <1 us through LDS).
 // The loop stays rolled: with every piece read from LDS before the first store the stores start later and each carries its own bounds join
 // (measured slower).
+//
+// policy (dhw_kernels.h STORE_*, wave-uniform; the branch goes around the whole loop, never around a piece): HOW the pieces are stored.
+//   STORE_PLAIN  plain stores: the lines stay dirty in the XCD's write-back L2 until the end-of-kernel release writes them back.
+//   STORE_WT     the same 16-byte pieces as write-through (sc1) buffer stores: every row and row stride in use is a multiple of
+//                128 B, so one store instruction writes whole lines, and they drain while the workgroup and its neighbours still
+//                run.  The descriptor covers exactly the tile (its range check drops anything past it).
+//   STORE_EARLY  plain stores; the workgroup calls tile_release_early() once behind its last copy-out.
+// The stored bytes are the same under every policy.
+DHW_DEV __amdgpu_buffer_rsrc_t tile_rsrc(const void* base, unsigned bytes) {
+  // (the tile's base is workgroup-uniform, but derived from values the compiler cannot prove uniform: one readfirstlane per half)
+  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+DHW_DEV void store16_wt(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off, const uint4& v) {
+  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+  __builtin_amdgcn_raw_buffer_store_b128((u32x4_t){v.x, v.y, v.z, v.w}, rsrc, byte_off, 0, 16);   // aux 16 = sc1
+}
+// STORE_EARLY: every wave waits for its own global stores, and behind the barrier ONE lane releases at agent scope — the L2's dirty
+// lines start their way to memory with the first finishing workgroup instead of after the last; they stay valid in L2 for a same-XCD
+// consumer.  Contains a barrier: every wave of the workgroup calls it.
+DHW_DEV void tile_release_early(int tid) {
+  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+}
+
 template <typename T>
-DHW_DEV void tile_copy_out(const char* lds, int S, T* gdst, int gs, int rows_valid, int C, int tid, int nthreads) {
+DHW_DEV void tile_copy_out(const char* lds, int S, T* gdst, int gs, int rows_valid, int C, int tid, int nthreads, int policy = STORE_PLAIN) {
   constexpr int ES = sizeof(T), EPV = 16 / ES;
   const int cpr = C / EPV;
   const int total = rows_valid * cpr;
+  if (policy == STORE_WT) {
+    if (total <= 0) return;
+    const __amdgpu_buffer_rsrc_t rsrc = tile_rsrc(gdst, (unsigned)(((rows_valid - 1) * gs + C) * ES));
+    for (int id = tid; id < total; id += nthreads) {
+      const int r = id / cpr, cc = id - r * cpr;
+      store16_wt(rsrc, (unsigned)((r * gs + cc * EPV) * ES), *reinterpret_cast<const uint4*>(lds + r * S + cc * 16));
+    }
+    return;
+  }
   for (int id = tid; id < total; id += nthreads) {
     const int r = id / cpr, cc = id - r * cpr;
     *reinterpret_cast<uint4*>(gdst + (size_t)r * gs + cc * EPV) = *reinterpret_cast<const uint4*>(lds + r * S + cc * 16);
   }
 }
 // same, but averaging row pairs (AvgPool1d(2), model.py:93): output row r = mean(tile rows 2r, 2r+1)
+// (the averaging is written out in both loops on purpose: behind a shared helper the plain loop was scheduled differently and the
+// register allocation of whole kernels moved with it)
 template <typename T>
-DHW_DEV void tile_copy_out_pool(const char* lds, int S, T* gdst, int gs, int rows_valid_in, int C, int tid, int nthreads) {
+DHW_DEV void tile_copy_out_pool(const char* lds, int S, T* gdst, int gs, int rows_valid_in, int C, int tid, int nthreads, int policy = STORE_PLAIN) {
   constexpr int ES = sizeof(T), EPV = 16 / ES;
   const int cpr = C / EPV;
   const int total = (rows_valid_in / 2) * cpr;
+  if (policy == STORE_WT) {
+    if (total <= 0) return;
+    const __amdgpu_buffer_rsrc_t rsrc = tile_rsrc(gdst, (unsigned)(((rows_valid_in / 2 - 1) * gs + C) * ES));
+    for (int id = tid; id < total; id += nthreads) {
+      const int r = id / cpr, cc = id - r * cpr;
+      uint4 a = *reinterpret_cast<const uint4*>(lds + (2 * r) * S + cc * 16);
+      const uint4 b = *reinterpret_cast<const uint4*>(lds + (2 * r + 1) * S + cc * 16);
+      T* ea = reinterpret_cast<T*>(&a);
+      const T* eb = reinterpret_cast<const T*>(&b);
+#pragma unroll
+      for (int k = 0; k < EPV; ++k) ea[k] = from_f<T>(0.5f * (to_f(ea[k]) + to_f(eb[k])));
+      store16_wt(rsrc, (unsigned)((r * gs + cc * EPV) * ES), a);
+    }
+    return;
+  }
   for (int id = tid; id < total; id += nthreads) {
     const int r = id / cpr, cc = id - r * cpr;
     uint4 a = *reinterpret_cast<const uint4*>(lds + (2 * r) * S + cc * 16);

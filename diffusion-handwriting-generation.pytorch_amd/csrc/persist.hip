@@ -1,6 +1,7 @@
 // persist.hip — the persistent per-step kernel (see persist.h): the fused block bodies of convblock_core.h / enc_bc_core.h run
 // as phases of one launch, tiles handed out by per-XCD tickets, hand-offs through per-sample counters.
 #define DHW_OPAQUE_TID 1
+#define DHW_STORE_RT 1   // (the bodies read the store policy from the recorded parameter blocks: dhw_kernels.h)
 #include "persist.h"
 #include "convblock_core.h"
 #include "enc_bc_core.h"

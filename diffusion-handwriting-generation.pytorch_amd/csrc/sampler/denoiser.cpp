@@ -131,6 +131,7 @@ static void conv_block(Ctx& c, int id, const ConvBlockW& w, const void* x, int L
     q.f1 = w.f1; q.f2 = w.f2; q.f3 = w.f3;
     q.out = out; q.out_f32 = out_f32; q.pool = pool;
     q.lens = c.lens; q.lsh = level_shift(c.L, L);
+    q.store = store_policy_of(h->store_policy, 0);
     if (c.fhp && id == CB_DEC1) {
       q.fuse_heads = 1;
       q.hp = *c.fhp;
@@ -163,7 +164,10 @@ static void conv_block(Ctx& c, int id, const ConvBlockW& w, const void* x, int L
       Launch l(h, c.st, ch ? "convblock.fused+a" : "convblock.fused", 2.0 * rows * (4.5 * w.cin * w.cout + 2.5 * w.cout * w.cout + upf) + chf,
                rows * ((up ? up->cin + 0.5 * w.cin : w.cin) * h->es + w.cout * (out_f32 ? 4.0 : (double)h->es) * (pool ? 1.5 : 1.0)) +
                    (4.5 * w.cin * w.cout + 2.5 * w.cout * w.cout + upf) * h->es + chb);
+      // (a handle with another store policy than the compiled-in default: the launchers that read it from the parameter blocks)
+      const bool pol = h->store_policy != DHW_STORE_DEFAULT;
       hipError_t e = q.lens ? (ch ? launch_convblock_chain_ragged(h->prec, q, *chain, c.st) : launch_convblock_ragged(h->prec, q, c.st))
+                     : pol  ? (ch ? launch_convblock_chain_policy(h->prec, q, *chain, c.st) : launch_convblock_policy(h->prec, q, c.st))
                             : (ch ? launch_convblock_chain(h->prec, q, *chain, c.st) : launch_convblock(h->prec, q, c.st));
       if (e != hipSuccess) c.err = fail(h, DHW_ERR_HIP, "convblock %s: %s", n, hipGetErrorString(e));
     }
@@ -269,6 +273,7 @@ EncLayerParams enc_params(Ctx& c, int li, const EncLayerW& w, const void* x, int
   q.x2 = ELB(c, li, x2); q.qk2 = ELB(c, li, qk2); q.vt2 = ELB(c, li, vt2); q.lpadX = lpad;
   q.out = ELB(c, li, out); q.pool = pool;
   q.lens = c.lens; q.lsh = level_shift(c.L, Lk);
+  q.store_a = store_policy_of(h->store_policy, 1); q.store_bc = store_policy_of(h->store_policy, 2);
   return q;
 }
 
@@ -315,7 +320,8 @@ static void enc_layer(Ctx& c, int li, const EncLayerW& w, const void* x, int Lk,
         by += r2 * d2 * 5 * h->es + 5.0 * d2 * d2 * h->es;
       }
       Launch l(h, c.st, which == 0 ? "enc.fused_a" : (ch && ch->mode ? "enc.fused_bc+a" : "enc.fused_bc"), fl, by);
-      hipError_t e = q.lens ? launch_enclayer_ragged(h->prec, q, which, c.st, ch) : launch_enclayer(h->prec, q, which, c.st, ch);
+      hipError_t e = q.lens ? launch_enclayer_ragged(h->prec, q, which, c.st, ch)
+                     : h->store_policy != DHW_STORE_DEFAULT ? launch_enclayer_policy(h->prec, q, which, c.st, ch) : launch_enclayer(h->prec, q, which, c.st, ch);
       if (e != hipSuccess) c.err = fail(h, DHW_ERR_HIP, "enclayer %s/%d: %s", h->el_name[li].c_str(), which, hipGetErrorString(e));
     }
     tap(c, tap_el(li, 1), ELB(c, li, x2), Lk, d);

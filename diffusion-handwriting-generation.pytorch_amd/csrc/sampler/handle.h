@@ -147,6 +147,10 @@ struct dhw_handle {
   bool chain = true;            // row-local stages continue across layer boundaries inside one launch (env DHW_CHAIN=0 -> off)
   bool fuse = true;             // fused block kernels (env DHW_FUSE=0 -> one launch per GEMM, for A/B runs)
   bool fuse_text = true;        // fused text-side kernels (textside.hip; env DHW_FUSE_TEXT=0 -> generic GEMM / attention launches)
+  // how the stroke kernels' tile copy-outs store (dhw_kernels.h STORE_*): two bits per output class, C | A << 2 | B << 4
+  // (env DHW_STORE_POLICY, read once at dhw_create; part of the graph / plan key like the switches above).  The default word is
+  // compiled into convblock.hip / enclayer.hip; any other runs the *_policy launchers, which read it from the parameter blocks.
+  int store_policy = DHW_STORE_DEFAULT;
   int text_pairs = 0;           // (step, prompt) pairs per workgroup of text_layer_kernel: 0 = by size, env DHW_TEXT_PAIRS = 1 / 2 forces one form
   std::map<std::vector<uint64_t>, hipGraphExec_t> graphs;
   std::map<std::vector<uint64_t>, uint64_t> graph_plane_gen;   // per cached graph: plane_gen when it was captured (it keeps those ".T" buffers)

@@ -441,7 +441,7 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
     // Plane reuse: the host's half of the verdict.  The tag stays cleared until this call has been enqueued, so any
     // error return below leaves it cleared.  A graph keeps the ".T" buffers it was captured with: its generation is the one then.
     const bool graph = h->use_graph && !h->prof && !h->teach_every;
-    const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)Lt, (uint64_t)T, (uint64_t)mode, (uint64_t)(noise != nullptr), (uint64_t)h->nstreams, (uint64_t)h->plane, (uint64_t)h->fuse_heads, (uint64_t)h->fuse_up, (uint64_t)h->chain, (uint64_t)h->persist,
+    const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)Lt, (uint64_t)T, (uint64_t)mode, (uint64_t)(noise != nullptr), (uint64_t)h->nstreams, (uint64_t)h->plane, (uint64_t)h->fuse_heads, (uint64_t)h->fuse_up, (uint64_t)h->chain, (uint64_t)h->persist, (uint64_t)h->store_policy,
                                          (uint64_t)ragged,   // (ragged: the kernels read the lengths from h->d_lens at replay)
                                          // conditioned calls: known / keep / cond_noise are read from the staging buffers at replay,
                                          // so one graph serves every mask; the iterations it holds depend on t_start
