@@ -285,15 +285,7 @@ hipError_t launch_loss(const float* eps, const float* pred, const float* pen, co
 hipError_t launch_sqnorm(const float* g, long n, float* out, hipStream_t st);
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float wd, int step,
                        const float* sqnorm, float max_norm, hipStream_t st);
-hipError_t launch_film_silu_fwd(const float* u, const float* film, long film_bs, int goff, int boff, int B, int L, int C, float* a, float* h, hipStream_t st);
-hipError_t launch_film_bwd(const float* d, const float* a, const float* u, const float* film, long film_bs, int goff, int B, int L, int C, int act,
-                           float* du, float* dfilm, long dfilm_bs, int dgoff, int dboff, hipStream_t st);
-hipError_t launch_silu_bwd_add(const float* d_sx, const float* x, long n, float* dx, hipStream_t st);
-hipError_t launch_silu_fwd(const float* x, long n, float* out, hipStream_t st);
-hipError_t launch_add(const float* a, const float* b, long n, float* out, hipStream_t st);
 hipError_t launch_colsum(const float* dy, long rows, int C, float* db, hipStream_t st);
-hipError_t launch_wgrad(const float* dy, const float* x, int B, int L, int Cout, int Cin, int taps, float* dw, hipStream_t st);
-hipError_t launch_film_linear_bwd(const float* dfilm, const float* sigma, const float* wcat, int B, int cols, float* dw, float* db, float* dsigma, hipStream_t st);
 
 // generic fp32 ops of the training step (train.hip, train/): see include/dhw_train.h (dhw_op_*)
 struct OpGemm {

@@ -1,10 +1,11 @@
-// dhw_train_api.cpp — C-ABI of the training step's first slice (include/dhw_train.h): loss / perturbation / optimizer
-// kernels and the ConvBlock forward + backward built from the generic MFMA GEMM (forward and data-gradient
-// convolutions, the latter with transposed / tap-flipped packed weights) and the kernels of train.hip and train/.
+// dhw_train_api.cpp — C-ABI of the training step (include/dhw_train.h): the loss / perturbation / optimizer / draw kernels of
+// train.hip, the generic dhw_op_* operations of train/, and dhw_train_convblock — one ConvBlock forward + backward issued on those
+// same generic launchers (strided GEMM, SiLU, FiLM backward), the way train_model.py's TrainModel._convblock chains them.
 #include <hip/hip_runtime.h>
 #include <map>
 #include <mutex>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -43,52 +44,47 @@ struct Scratch {
     hipDeviceSynchronize();
     arena.free_all();
   }
-  float* f32(size_t n) {
+  float* f32(size_t n) {   // not zeroed
     void* p = nullptr;
-    return arena.alloc(&p, n * sizeof(float)) == hipSuccess ? (float*)p : nullptr;
+    return arena.alloc(&p, n * sizeof(float), false) == hipSuccess ? (float*)p : nullptr;
   }
-  float* upload(const std::vector<float>& v) {
+  float* upload(const float* host, size_t n) {
     float* p = nullptr;
-    return arena.upload_f32(v, &p) == hipSuccess ? p : nullptr;
-  }
-  // row-major Wf[N][K] -> MFMA-fragment order, fp32 (host/convert.h pack_mfma)
-  float* packed(const std::vector<float>& wf, int N, int K) {
-    void* p = nullptr;
-    return arena.upload_packed(wf, N, K, false, &p) == hipSuccess ? (float*)p : nullptr;
+    return arena.upload_f32(std::vector<float>(host, host + n), &p) == hipSuccess ? p : nullptr;
   }
 };
 
-// forward convolution matrix: Wf[co][tap * cin + ci] = W[co][ci][tap]
-std::vector<float> fwd_matrix(const float* w, int cout, int cin, int taps) {
-  std::vector<float> f((size_t)cout * cin * taps);
-  for (int o = 0; o < cout; ++o)
-    for (int i = 0; i < cin; ++i)
-      for (int t = 0; t < taps; ++t) f[(size_t)o * cin * taps + t * cin + i] = w[((size_t)o * cin + i) * taps + t];
-  return f;
+// The three GEMMs of a Conv1d(k = 3, 'same' padding inside each sample of L rows) / nn.Linear (taps = 1) on C-last rows, W in torch
+// layout [cout][cin][taps] — the descriptors Tape.conv3 / Tape.linear build (train_model.py).
+// y[R, cout] = conv(x[R, cin]) + b
+OpGemm fwd_gemm(const float* x, const float* W, const float* b, float* y, int R, int L, int cin, int cout, int taps) {
+  OpGemm g{};
+  g.A = x; g.sam = cin; g.sak = 1;
+  g.B = W; g.sbk = taps; g.sbn = (long)cin * taps; g.sbt = 1;
+  g.C = y; g.scm = cout; g.scn = 1;
+  g.M = R; g.N = cout; g.K = taps * cin; g.nzo = g.nzi = 1; g.taps = taps; g.bias = b; g.alpha = 1.f;
+  if (taps == 3) { g.a_shift = -1; g.a_tap_shift = 1; g.lr = L; }
+  return g;
 }
-// data-gradient matrix: dX[r][ci] = sum_{tap', co} dY[r + tap' - 1][co] * W[co][ci][taps - 1 - tap']  =>  Wd[ci][tap' * cout + co]
-std::vector<float> dgrad_matrix(const float* w, int cout, int cin, int taps) {
-  std::vector<float> f((size_t)cout * cin * taps);
-  for (int i = 0; i < cin; ++i)
-    for (int t = 0; t < taps; ++t)
-      for (int o = 0; o < cout; ++o) f[(size_t)i * cout * taps + t * cout + o] = w[((size_t)o * cin + i) * taps + (taps - 1 - t)];
-  return f;
+// dW[cout][cin][tap] += dy^T x[r + tap - 1] (the taps as the inner batch index), db += column sums of dy: both zeroed by the caller
+OpGemm wgrad_gemm(const float* dy, const float* x, float* dW, float* db, int R, int L, int cin, int cout, int taps) {
+  OpGemm g{};
+  g.A = dy; g.sam = 1; g.sak = cout;
+  g.B = x; g.sbk = cin; g.sbn = 1;
+  g.C = dW; g.scm = (long)cin * taps; g.scn = taps; g.sczi = 1;
+  g.M = cout; g.N = cin; g.K = R; g.nzo = 1; g.nzi = taps; g.taps = 1; g.alpha = 1.f; g.accumulate = 1; g.rowsum = db;
+  if (taps == 3) { g.b_shift = -1; g.b_z_shift = 1; g.lr = L; }
+  return g;
 }
-
-int conv_gemm(const float* in, int B, int L, int C, int taps, const float* w_packed, const float* bias, int N, float* out, hipStream_t st) {
-  GemmParams p{};
-  p.nseg = 1;
-  p.seg[0] = GemmSeg{in, w_packed, C, taps, 0};
-  p.B = B;
-  p.L = L;
-  p.N = N;
-  p.n_store = N;
-  p.bias0 = bias;
-  p.film_div = 1;
-  p.out = out;
-  hipError_t e = launch_gemm(PREC_F32, p, st);
-  if (e != hipSuccess) return tfail(DHW_ERR_HIP, "conv gemm %d x%d -> %d: %s", C, taps, N, hipGetErrorString(e));
-  return 0;
+// dx[R, cin] (+)= sum_tap dy[r - (tap - 1)] W[:, :, tap], times SiLU'(dsilu_of) where the layer's input was SiLU(dsilu_of)
+OpGemm dgrad_gemm(const float* dy, const float* W, float* dx, int accumulate, const float* dsilu_of, int R, int L, int cin, int cout, int taps) {
+  OpGemm g{};
+  g.A = dy; g.sam = cout; g.sak = 1;
+  g.B = W; g.sbk = (long)cin * taps; g.sbn = taps; g.sbt = 1;
+  g.C = dx; g.scm = cin; g.scn = 1;
+  g.M = R; g.N = cin; g.K = taps * cout; g.nzo = g.nzi = 1; g.taps = taps; g.alpha = 1.f; g.accumulate = accumulate; g.dsilu_of = dsilu_of;
+  if (taps == 3) { g.a_shift = 1; g.a_tap_shift = -1; g.lr = L; }
+  return g;
 }
 
 }  // namespace
@@ -151,84 +147,63 @@ int dhw_train_convblock(int device, int B, int L, int cin, int cout, const float
     if (!x || !sigma || !dout || !w || !out || !dx || !dsigma || !g) return tfail(DHW_ERR_ARG, "dhw_train_convblock: null pointer");
     const int c1 = cout / 2;
     if (B < 1 || L < 2 || (L & 1) || cin % 32 || c1 % 32 || cout % 64) return tfail(DHW_ERR_ARG, "dhw_train_convblock: unsupported shape B=%d L=%d %d -> %d", B, L, cin, cout);
+    const long rows = (long)B * L;
+    // (the strided GEMM addresses its operands with 32-bit element offsets)
+    if (rows * std::max(cin, cout) >= (1L << 31)) return tfail(DHW_ERR_ARG, "dhw_train_convblock: unsupported shape B=%d L=%d %d -> %d", B, L, cin, cout);
     THIP(hipSetDevice(device));
-    if (gemm_init() != hipSuccess) return tfail(DHW_ERR_HIP, "kernel attribute setup failed");
     hipStream_t st = (hipStream_t)hip_stream;
     Scratch s;
-    const long rows = (long)B * L, slack = 64;
-    const int tot = c1 + 2 * cout, cols = 2 * tot;          // FiLM table columns: gamma1|gamma2|gamma3|beta1|beta2|beta3
+    const int R = (int)rows, tot = c1 + 2 * cout, cols = 2 * tot;   // FiLM table columns: gamma1|gamma2|gamma3|beta1|beta2|beta3
     const int go[3] = {0, c1, c1 + cout}, bo[3] = {tot, tot + c1, tot + c1 + cout};
+    const size_t n1 = (size_t)c1 * cin * 3, n2 = (size_t)cout * c1 * 3, nf = (size_t)cout * cout, ns = (size_t)cout * cin * 3, nw = (size_t)cols * 32;
 
-    // ---- weights: forward and data-gradient matrices in MFMA-fragment order
-    float* wf1 = s.packed(fwd_matrix(w->conv1_w, c1, cin, 3), c1, 3 * cin);
-    float* wf2 = s.packed(fwd_matrix(w->conv2_w, cout, c1, 3), cout, 3 * c1);
-    float* wff = s.packed(fwd_matrix(w->fc_w, cout, cout, 1), cout, cout);
-    float* wfs = s.packed(fwd_matrix(w->skip_w, cout, cin, 3), cout, 3 * cin);
-    float* wd1 = s.packed(dgrad_matrix(w->conv1_w, c1, cin, 3), cin, 3 * c1);
-    float* wd2 = s.packed(dgrad_matrix(w->conv2_w, cout, c1, 3), c1, 3 * cout);
-    float* wdf = s.packed(dgrad_matrix(w->fc_w, cout, cout, 1), cout, cout);
-    float* wds = s.packed(dgrad_matrix(w->skip_w, cout, cin, 3), cin, 3 * cout);
-    float* b1 = s.upload(std::vector<float>(w->conv1_b, w->conv1_b + c1));
-    float* b2 = s.upload(std::vector<float>(w->conv2_b, w->conv2_b + cout));
-    float* bf = s.upload(std::vector<float>(w->fc_b, w->fc_b + cout));
-    float* bsk = s.upload(std::vector<float>(w->skip_b, w->skip_b + cout));
-    float* wcat = s.upload(std::vector<float>(w->film_w, w->film_w + (size_t)cols * 32));
-    float* bcat = s.upload(std::vector<float>(w->film_b, w->film_b + cols));
-    // ---- activations kept for the backward pass (every buffer with slack rows for the GEMM tiles)
-    auto act = [&](int C) { return s.f32((size_t)(rows + slack) * C); };
-    float *xs = act(cin), *sx = act(cin), *u1 = act(c1), *a1 = act(c1), *h1 = act(c1), *u2 = act(cout), *a2 = act(cout), *h2 = act(cout),
-          *u3 = act(cout), *a3 = act(cout), *sk = act(cout), *dos = act(cout);
-    float *du3 = act(cout), *dh2 = act(cout), *du2 = act(cout), *dh1 = act(c1), *du1 = act(c1), *dsx = act(cin), *dxs = act(cin);
-    float* film = s.f32((size_t)B * cols);
-    float* dfilm = s.f32((size_t)B * cols);
-    float* zb = s.f32(cout);   // zero bias for the data-gradient convolutions
-    if (!wf1 || !wf2 || !wff || !wfs || !wd1 || !wd2 || !wdf || !wds || !b1 || !b2 || !bf || !bsk || !wcat || !bcat || !dxs || !film || !dfilm || !zb)
+    // ---- weights as the caller holds them (torch layouts: the GEMM takes strides), activations kept for the backward pass
+    float *w1 = s.upload(w->conv1_w, n1), *b1 = s.upload(w->conv1_b, c1), *w2 = s.upload(w->conv2_w, n2), *b2 = s.upload(w->conv2_b, cout);
+    float *wfc = s.upload(w->fc_w, nf), *bfc = s.upload(w->fc_b, cout), *wsk = s.upload(w->skip_w, ns), *bsk = s.upload(w->skip_b, cout);
+    float *wfilm = s.upload(w->film_w, nw), *bfilm = s.upload(w->film_b, cols);
+    auto act = [&](int C) { return s.f32((size_t)rows * C); };
+    float *xa = act(cin), *sk = act(cout), *u1 = act(c1), *h1 = act(c1), *u2 = act(cout), *h2 = act(cout), *u3 = act(cout);
+    float *du3 = act(cout), *dh2 = act(cout), *du2 = act(cout), *dh1 = act(c1), *du1 = act(c1);
+    float *film = s.f32((size_t)B * cols), *dfilm = s.f32((size_t)B * cols);
+    if (!w1 || !b1 || !w2 || !b2 || !wfc || !bfc || !wsk || !bsk || !wfilm || !bfilm || !xa || !sk || !u1 || !h1 || !u2 || !h2 || !u3 || !du3 || !dh2 ||
+        !du2 || !dh1 || !du1 || !film || !dfilm)
       return tfail(DHW_ERR_HIP, "dhw_train_convblock: out of device memory");
-    THIP(hipMemcpyAsync(xs, x, rows * cin * 4, hipMemcpyDeviceToDevice, st));      // (the caller's buffers carry no slack rows)
-    THIP(hipMemcpyAsync(dos, dout, rows * cout * 4, hipMemcpyDeviceToDevice, st));
-    int rc;
+    // FiLM k (+ SiLU) (+ addend) of a GEMM's result as a further output of its pass
+    auto rider = [&](OpGemm gm, int k, int silu, const float* addend, float* to) {
+      gm.film_g = film + go[k]; gm.film_b = film + bo[k]; gm.film_ps = cols; gm.film_rows = L; gm.film_act = silu; gm.film_add = addend; gm.film_out = to;
+      return gm;
+    };
+    auto film_bwd = [&](const float* dy, const float* u, int k, int C, int silu, float* du) {
+      return launch_film_act_bwd(dy, u, film + go[k], film + bo[k], cols, B, L, C, silu, du, 0, dfilm + go[k], dfilm + bo[k], st);
+    };
 
-    // ---- forward (cnn.py:64-87), every pre-activation kept
-    THIP(launch_film(sigma, B, wcat, bcat, cols, film, st));
-    THIP(launch_silu_fwd(xs, rows * cin, sx, st));
-    if ((rc = conv_gemm(sx, B, L, cin, 3, wf1, b1, c1, u1, st))) return rc;
-    THIP(launch_film_silu_fwd(u1, film, cols, go[0], bo[0], B, L, c1, a1, h1, st));
-    if ((rc = conv_gemm(h1, B, L, c1, 3, wf2, b2, cout, u2, st))) return rc;
-    THIP(launch_film_silu_fwd(u2, film, cols, go[1], bo[1], B, L, cout, a2, h2, st));
-    if ((rc = conv_gemm(h2, B, L, cout, 1, wff, bf, cout, u3, st))) return rc;
-    THIP(launch_film_silu_fwd(u3, film, cols, go[2], bo[2], B, L, cout, a3, nullptr, st));
-    if ((rc = conv_gemm(xs, B, L, cin, 3, wfs, bsk, cout, sk, st))) return rc;
-    THIP(launch_add(a3, sk, rows * cout, out, st));
+    // ---- forward (cnn.py:64-87) as TrainModel._convblock chains it: every affine rides on the GEMM in front of it
+    THIP(launch_sgemm(fwd_gemm(sigma, wfilm, bfilm, film, B, 0, 32, cols, 1), st));
+    THIP(launch_unary(0, x, rows * cin, xa, st));
+    const OpGemm both[2] = {fwd_gemm(x, wsk, bsk, sk, R, L, cin, cout, 3), rider(fwd_gemm(xa, w1, b1, u1, R, L, cin, c1, 3), 0, 1, nullptr, h1)};
+    THIP(launch_sgemm_group(both, 2, st));
+    THIP(launch_sgemm(rider(fwd_gemm(h1, w2, b2, u2, R, L, c1, cout, 3), 1, 1, nullptr, h2), st));
+    THIP(launch_sgemm(rider(fwd_gemm(h2, wfc, bfc, u3, R, 0, cout, cout, 1), 2, 0, sk, out), st));
 
-    // ---- backward
-    const size_t n1 = (size_t)c1 * cin * 3, n2 = (size_t)cout * c1 * 3, nf = (size_t)cout * cout, ns = (size_t)cout * cin * 3;
+    // ---- backward: weight gradient (bias gradient riding on it) and data gradient of a layer as a pair; both add into zeroed buffers
     THIP(hipMemsetAsync(g->conv1_w, 0, n1 * 4, st)); THIP(hipMemsetAsync(g->conv1_b, 0, c1 * 4, st));
     THIP(hipMemsetAsync(g->conv2_w, 0, n2 * 4, st)); THIP(hipMemsetAsync(g->conv2_b, 0, cout * 4, st));
     THIP(hipMemsetAsync(g->fc_w, 0, nf * 4, st));    THIP(hipMemsetAsync(g->fc_b, 0, cout * 4, st));
     THIP(hipMemsetAsync(g->skip_w, 0, ns * 4, st));  THIP(hipMemsetAsync(g->skip_b, 0, cout * 4, st));
+    THIP(hipMemsetAsync(g->film_w, 0, nw * 4, st));  THIP(hipMemsetAsync(g->film_b, 0, cols * 4, st));
+    THIP(hipMemsetAsync(dfilm, 0, (size_t)B * cols * 4, st));   // (film_act_bwd adds the per-sample gamma / beta gradients into it)
     // out = FiLM3(fc(h2)) + conv_skip(x): both branches see dout
-    THIP(launch_film_bwd(dos, nullptr, u3, film, cols, go[2], B, L, cout, 0, du3, dfilm, cols, go[2], bo[2], st));
-    THIP(launch_wgrad(du3, h2, B, L, cout, cout, 1, g->fc_w, st));
-    THIP(launch_colsum(du3, rows, cout, g->fc_b, st));
-    if ((rc = conv_gemm(du3, B, L, cout, 1, wdf, zb, cout, dh2, st))) return rc;
+    THIP(film_bwd(dout, u3, 2, cout, 0, du3));
+    THIP(launch_sgemm_pair(wgrad_gemm(du3, h2, g->fc_w, g->fc_b, R, 0, cout, cout, 1), dgrad_gemm(du3, wfc, dh2, 0, nullptr, R, 0, cout, cout, 1), st));
     // h2 = SiLU(FiLM2(conv2(h1)))
-    THIP(launch_film_bwd(dh2, a2, u2, film, cols, go[1], B, L, cout, 1, du2, dfilm, cols, go[1], bo[1], st));
-    THIP(launch_wgrad(du2, h1, B, L, cout, c1, 3, g->conv2_w, st));
-    THIP(launch_colsum(du2, rows, cout, g->conv2_b, st));
-    if ((rc = conv_gemm(du2, B, L, cout, 3, wd2, zb, c1, dh1, st))) return rc;
-    // h1 = SiLU(FiLM1(conv1(SiLU(x))))
-    THIP(launch_film_bwd(dh1, a1, u1, film, cols, go[0], B, L, c1, 1, du1, dfilm, cols, go[0], bo[0], st));
-    THIP(launch_wgrad(du1, sx, B, L, c1, cin, 3, g->conv1_w, st));
-    THIP(launch_colsum(du1, rows, c1, g->conv1_b, st));
-    if ((rc = conv_gemm(du1, B, L, c1, 3, wd1, zb, cin, dsx, st))) return rc;
-    // skip branch, then dx = conv_skip^T(dout) + conv1^T(..) * SiLU'(x)
-    THIP(launch_wgrad(dos, xs, B, L, cout, cin, 3, g->skip_w, st));
-    THIP(launch_colsum(dos, rows, cout, g->skip_b, st));
-    if ((rc = conv_gemm(dos, B, L, cout, 3, wds, zb, cin, dxs, st))) return rc;
-    THIP(launch_silu_bwd_add(dsx, xs, rows * cin, dxs, st));
-    THIP(hipMemcpyAsync(dx, dxs, rows * cin * 4, hipMemcpyDeviceToDevice, st));
+    THIP(film_bwd(dh2, u2, 1, cout, 1, du2));
+    THIP(launch_sgemm_pair(wgrad_gemm(du2, h1, g->conv2_w, g->conv2_b, R, L, c1, cout, 3), dgrad_gemm(du2, w2, dh1, 0, nullptr, R, L, c1, cout, 3), st));
+    // h1 = SiLU(FiLM1(conv1(SiLU(x)))): the data gradient takes SiLU'(x) along and writes dx; the skip branch adds to it
+    THIP(film_bwd(dh1, u1, 0, c1, 1, du1));
+    THIP(launch_sgemm_pair(wgrad_gemm(du1, xa, g->conv1_w, g->conv1_b, R, L, cin, c1, 3), dgrad_gemm(du1, w1, dx, 0, x, R, L, cin, c1, 3), st));
+    THIP(launch_sgemm_pair(wgrad_gemm(dout, x, g->skip_w, g->skip_b, R, L, cin, cout, 3), dgrad_gemm(dout, wsk, dx, 1, nullptr, R, L, cin, cout, 3), st));
     // the six FiLM Linears
-    THIP(launch_film_linear_bwd(dfilm, sigma, wcat, B, cols, g->film_w, g->film_b, dsigma, st));
+    THIP(launch_sgemm_pair(wgrad_gemm(dfilm, sigma, g->film_w, g->film_b, B, 0, 32, cols, 1), dgrad_gemm(dfilm, wfilm, dsigma, 0, nullptr, B, 0, 32, cols, 1), st));
     THIP(hipStreamSynchronize(st));
     return 0;
   });

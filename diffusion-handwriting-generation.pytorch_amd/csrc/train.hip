@@ -1,12 +1,9 @@
 // train.hip — the training step's own kernels (reference train.py:26-67): the forward-diffusion
 // perturbation, the loss and its gradient, gradient-norm clipping + Adam over flat parameter buffers, the step's Philox
-// draws and keep masks; and the "first slice" backward pieces of a ConvBlock (cnn.py:64-87) behind dhw_train_convblock
-// that are not plain GEMMs — FiLM / SiLU backward with its per-sample reductions, the weight-gradient contraction over
-// stroke rows on the exact-f32 MFMA, bias gradients, the FiLM Linear backward.  fp32 throughout (the gradients are
-// checked against the reference's autograd at fp32 tolerances).
+// draws and keep masks, and the stand-alone bias gradient (colsum, behind dhw_op_colsum).  fp32 throughout.
 // The rest of the training kernels lives under train/: the strided GEMM (sgemm_core.h, its instantiations sgemm_f32 /
 // sgemm_bf16 / sgemm_group .hip and the planner sgemm_launch.hip), the element-wise / LayerNorm / softmax / pool /
-// embedding passes (elementwise.hip) and the FiLM table (film_table.hip).
+// embedding passes (elementwise.hip) and the FiLM table (film_table.hip); dhw_train_convblock runs on those too.
 #include <cstdlib>
 
 #include "dhw_common.h"
@@ -186,57 +183,6 @@ __global__ __launch_bounds__(256) void keep_mask_kernel(const uint64_t* rng, uin
     if (e + k < n) keep[e + k] = ((float)(c[k] >> 8) + 0.5f) * (1.0f / 16777216.0f) >= p ? 1.0f : 0.0f;
 }
 
-// a = u * gamma[b] + beta[b];  h = SiLU(a)   (rows C-last [B*L, C]; gamma/beta [B][cols] at column offset)
-__global__ __launch_bounds__(256) void film_silu_fwd_kernel(const float* u, const float* film, long film_bs, int goff, int boff, int L, int C,
-                                                             long n4, float* a_out, float* h_out) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const long e = i * 4, r = e / C;
-  const int c = (int)(e - r * C), b = (int)(r / L);
-  const f32x4 x = *reinterpret_cast<const f32x4*>(u + e);
-  const f32x4 ga = *reinterpret_cast<const f32x4*>(film + b * film_bs + goff + c), be = *reinterpret_cast<const f32x4*>(film + b * film_bs + boff + c);
-  f32x4 a = x * ga + be, h;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) h[k] = silu_f(a[k]);
-  *reinterpret_cast<f32x4*>(a_out + e) = a;
-  if (h_out) *reinterpret_cast<f32x4*>(h_out + e) = h;
-}
-
-// Backward of a = u gamma + beta (and, with act, of h = SiLU(a)): given d = dL/dh (or dL/da), writes dL/du = d' gamma and
-// accumulates dgamma[b][c] = sum_l d' u, dbeta[b][c] = sum_l d'  (d' = d * SiLU'(a) with act).  One thread per (b, c):
-// lanes run along the contiguous channel axis, the loop over the sample's L rows is sequential (deterministic).
-__global__ __launch_bounds__(64) void film_bwd_kernel(const float* d, const float* a, const float* u, const float* film, long film_bs, int goff,
-                                                       int L, int C, int act, float* du, float* dfilm, long dfilm_bs, int dgoff, int dboff) {
-  const int c = blockIdx.x * 64 + threadIdx.x, b = blockIdx.y;
-  if (c >= C) return;
-  const float ga = film[b * film_bs + goff + c];
-  float sg = 0.f, sb = 0.f;
-  for (int l = 0; l < L; ++l) {
-    const long e = ((long)b * L + l) * C + c;
-    float dd = d[e];
-    if (act) dd *= dsilu_f(a[e]);
-    sg += dd * u[e];
-    sb += dd;
-    du[e] = dd * ga;
-  }
-  dfilm[b * dfilm_bs + dgoff + c] = sg;
-  dfilm[b * dfilm_bs + dboff + c] = sb;
-}
-
-// dx += d_sx * SiLU'(x)   (the conv1 branch reads SiLU(x); the skip branch's dx is already in dx)
-__global__ __launch_bounds__(256) void silu_bwd_add_kernel(const float* d_sx, const float* x, long n, float* dx) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) dx[i] += d_sx[i] * dsilu_f(x[i]);
-}
-__global__ __launch_bounds__(256) void silu_fwd_kernel(const float* x, long n, float* out) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = silu_f(x[i]);
-}
-__global__ __launch_bounds__(256) void add_kernel(const float* a, const float* b, long n, float* out) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = a[i] + b[i];
-}
-
 // db[c] += sum over all rows of dy[r][c]: block = 64 channels x 4 row groups over a chunk of rows, one atomic per (block, channel)
 __global__ __launch_bounds__(256) void colsum_kernel(const float* dy, long rows, int C, int rows_per_block, float* db) {
   const int c = blockIdx.x * 64 + (threadIdx.x & 63), rg = threadIdx.x >> 6;
@@ -248,61 +194,6 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* dy, long rows,
   red[threadIdx.x] = s;
   __syncthreads();
   if (rg == 0 && c < C) atomicAdd(db + c, red[threadIdx.x] + red[threadIdx.x + 64] + red[threadIdx.x + 128] + red[threadIdx.x + 192]);
-}
-
-// Weight gradient of Conv1d(k = taps, 'same' zero padding inside each sample) / Linear (taps = 1), torch layout:
-//   dW[co][ci][tap] += sum_{b,l} dY[b,l,co] * X[b, l + tap - taps/2, ci]
-// a [Cout x Cin] contraction over the B*L stroke rows per tap, on the exact-f32 MFMA (16x16x4 f32: bitwise an fmaf chain).
-// One wave = one 16 x 16 (co, ci) tile of one tap over a 256-row chunk; lane (i = lane & 15, g = lane >> 4) feeds
-// dY[row 8g + j][co0 + i] as the A operand and X[row 8g + j + shift][ci0 + i] as the B operand (16 lanes read 64
-// contiguous bytes of a row).  Chunks accumulate with fp32 atomics (<= rows / 256 adds per element).
-__global__ __launch_bounds__(64) void wgrad_kernel(const float* dy, const float* x, int B, int L, int Cout, int Cin, int taps, float* dw) {
-  const int lane = threadIdx.x, i = lane & 15, g = lane >> 4;
-  const int ci_tiles = Cin / 16;
-  int t = blockIdx.x;
-  const int tap = t % taps; t /= taps;
-  const int ci0 = (t % ci_tiles) * 16, co0 = (t / ci_tiles) * 16;
-  const long rows = (long)B * L, r_begin = (long)blockIdx.y * 256;
-  const int shift = tap - taps / 2;
-  f32x4 acc = (f32x4){0, 0, 0, 0};
-  for (int s = 0; s < 8; ++s) {
-    Frag<float> fa, fb;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const long r = r_begin + s * 32 + 8 * g + j;
-      float va = 0.f, vb = 0.f;
-      if (r < rows) {
-        va = dy[r * Cout + co0 + i];
-        const int l = (int)(r % L) + shift;
-        if (l >= 0 && l < L) vb = x[(r + shift) * Cin + ci0 + i];
-      }
-      if (j < 4) { fa.lo[j] = va; fb.lo[j] = vb; } else { fa.hi[j - 4] = va; fb.hi[j - 4] = vb; }
-    }
-    mma32(acc, fa, fb);
-  }
-  // acc[r] = dW tile[co = 4g + r][ci = i]
-#pragma unroll
-  for (int r = 0; r < 4; ++r) atomicAdd(dw + ((size_t)(co0 + 4 * g + r) * Cin + ci0 + i) * taps + tap, acc[r]);
-}
-
-// FiLM Linears (conditioning.py:16-18): film[b][c] = Wcat[c][:] . sigma[b] + bcat[c].  Backward, all of a block's 6 Linears:
-// dW[c][k] = sum_b dfilm[b][c] sigma[b][k], db[c] = sum_b dfilm[b][c], dsigma[b][k] = sum_c dfilm[b][c] W[c][k].
-__global__ __launch_bounds__(256) void film_linear_bwd_kernel(const float* dfilm, const float* sigma, const float* wcat, int B, int cols,
-                                                               float* dw, float* db, float* dsigma) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx < cols * 32) {
-    const int c = idx / 32, k = idx % 32;
-    float s = 0.f, sb = 0.f;
-    for (int b = 0; b < B; ++b) { s += dfilm[(long)b * cols + c] * sigma[b * 32 + k]; sb += dfilm[(long)b * cols + c]; }
-    dw[idx] = s;
-    if (k == 0) db[c] = sb;
-  }
-  if (idx < B * 32) {
-    const int b = idx / 32, k = idx % 32;
-    float s = 0.f;
-    for (int c = 0; c < cols; ++c) s += dfilm[(long)b * cols + c] * wcat[c * 32 + k];
-    dsigma[idx] = s;
-  }
 }
 
 }  // namespace
@@ -345,39 +236,8 @@ hipError_t launch_adam_dev(float* p, const float* g, float* m, float* v, long n,
   hipLaunchKernelGGL(adam_dev_kernel, dim3(nb(n)), dim3(256), 0, st, p, g, m, v, n, hyper, sqnorm);
   return hipGetLastError();
 }
-hipError_t launch_film_silu_fwd(const float* u, const float* film, long film_bs, int goff, int boff, int B, int L, int C, float* a, float* h, hipStream_t st) {
-  const long n4 = (long)B * L * C / 4;
-  hipLaunchKernelGGL(film_silu_fwd_kernel, dim3(nb(n4)), dim3(256), 0, st, u, film, film_bs, goff, boff, L, C, n4, a, h);
-  return hipGetLastError();
-}
-hipError_t launch_film_bwd(const float* d, const float* a, const float* u, const float* film, long film_bs, int goff, int B, int L, int C, int act,
-                           float* du, float* dfilm, long dfilm_bs, int dgoff, int dboff, hipStream_t st) {
-  hipLaunchKernelGGL(film_bwd_kernel, dim3(nb(C, 64), B), dim3(64), 0, st, d, a, u, film, film_bs, goff, L, C, act, du, dfilm, dfilm_bs, dgoff, dboff);
-  return hipGetLastError();
-}
-hipError_t launch_silu_bwd_add(const float* d_sx, const float* x, long n, float* dx, hipStream_t st) {
-  hipLaunchKernelGGL(silu_bwd_add_kernel, dim3(nb(n)), dim3(256), 0, st, d_sx, x, n, dx);
-  return hipGetLastError();
-}
-hipError_t launch_silu_fwd(const float* x, long n, float* out, hipStream_t st) {
-  hipLaunchKernelGGL(silu_fwd_kernel, dim3(nb(n)), dim3(256), 0, st, x, n, out);
-  return hipGetLastError();
-}
-hipError_t launch_add(const float* a, const float* b, long n, float* out, hipStream_t st) {
-  hipLaunchKernelGGL(add_kernel, dim3(nb(n)), dim3(256), 0, st, a, b, n, out);
-  return hipGetLastError();
-}
 hipError_t launch_colsum(const float* dy, long rows, int C, float* db, hipStream_t st) {   // db zeroed by the caller
   const int rpb = 64;
   hipLaunchKernelGGL(colsum_kernel, dim3(nb(C, 64), nb(rows, rpb)), dim3(256), 0, st, dy, rows, C, rpb, db);
-  return hipGetLastError();
-}
-hipError_t launch_wgrad(const float* dy, const float* x, int B, int L, int Cout, int Cin, int taps, float* dw, hipStream_t st) {   // dw zeroed by the caller
-  if (Cout % 16 || Cin % 16 || (taps != 1 && taps != 3)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(wgrad_kernel, dim3((Cout / 16) * (Cin / 16) * taps, nb((long)B * L, 256)), dim3(64), 0, st, dy, x, B, L, Cout, Cin, taps, dw);
-  return hipGetLastError();
-}
-hipError_t launch_film_linear_bwd(const float* dfilm, const float* sigma, const float* wcat, int B, int cols, float* dw, float* db, float* dsigma, hipStream_t st) {
-  hipLaunchKernelGGL(film_linear_bwd_kernel, dim3(nb(std::max((long)cols * 32, (long)B * 32))), dim3(256), 0, st, dfilm, sigma, wcat, B, cols, dw, db, dsigma);
   return hipGetLastError();
 }

@@ -193,14 +193,15 @@ def convblock_forward_backward(sd: dict, x: torch.Tensor, sigma: torch.Tensor, d
           "fc_w": host["fc.weight"], "fc_b": host["fc.bias"], "skip_w": host["conv_skip.weight"], "skip_b": host["conv_skip.bias"],
           "film_w": film_w, "film_b": film_b}
     w = _lib.ConvBlockWeights(**{k: hw[k].data_ptr() for k in _CB_FIELDS})
-    gd = {k: torch.zeros(hw[k].shape, device=dev) for k in _CB_FIELDS}
+    nan = float("nan")       # (every output is WRITTEN by the call, whatever it held: a NaN left over would show in any comparison)
+    gd = {k: torch.full(tuple(hw[k].shape), nan, device=dev) for k in _CB_FIELDS}
     g = _lib.ConvBlockWeights(**{k: gd[k].data_ptr() for k in _CB_FIELDS})
     xd = _f32(x.permute(0, 2, 1).reshape(B * L, cin), dev)
     dd = _f32(dout.permute(0, 2, 1).reshape(B * L, cout), dev)
     sg = _f32(sigma.reshape(B, 32), dev)
-    out = torch.empty(B * L, cout, device=dev)
-    dx = torch.empty(B * L, cin, device=dev)
-    dsig = torch.empty(B, 32, device=dev)
+    out = torch.full((B * L, cout), nan, device=dev)
+    dx = torch.full((B * L, cin), nan, device=dev)
+    dsig = torch.full((B, 32), nan, device=dev)
     _tcheck(_lib.lib().dhw_train_convblock(dev.index or 0, B, L, cin, cout, xd.data_ptr(), sg.data_ptr(), dd.data_ptr(), C.byref(w), out.data_ptr(),
                                            dx.data_ptr(), dsig.data_ptr(), C.byref(g), _stream(dev)))
     tot = c1 + 2 * cout

@@ -7,13 +7,14 @@
  *   dhw_train_loss       <- loss_fn (loss.py:5-37) and d loss / d(score_pred, pen_lifts_pred)     (loss.backward())
  *   dhw_train_adam       <- clip_grad_norm_(max_norm) (utils/clip_grad.py:42-43) + torch.optim.Adam (configs/best.yml:33-38)
  *   dhw_train_convblock  <- ConvBlock.forward + its autograd backward (cnn.py:64-87): the first block of the denoiser's
- *                           backward pass as ONE fused entry point (weights packed per call).
+ *                           backward pass as ONE entry point, issued on the generic operations below (weights uploaded per call,
+ *                           in torch layout).
  *   dhw_op_*             <- the generic fp32 operations from which dhg_amd/train_model.py assembles the WHOLE
  *                           DiffusionModel forward (train mode) and backward — every parameter gradient of the
  *                           reference's loss.backward() (train.py:55-60).
  *
  * fp32; activations are C-last [B*L, C] device buffers; weights of dhw_train_convblock are HOST pointers in torch layouts
- * (packed per call: this entry point is a gradient-parity vehicle, not yet a tuned trainer).
+ * (uploaded per call as they are: this entry point is a gradient-parity vehicle for exactly the kernels the training step runs).
  */
 #ifndef DHW_TRAIN_H
 #define DHW_TRAIN_H
@@ -68,7 +69,9 @@ typedef struct {   /* DEVICE pointers, the same layouts */
 } dhw_convblock_grads;
 
 /* out = ConvBlock(x, sigma) and, for the upstream gradient dout, dx, dsigma and every parameter gradient.
- * x [B*L,Cin], sigma [B,32], dout / out [B*L,C], dx [B*L,Cin], dsigma [B,32]: device, f32.  L even, Cin and C/2 multiples of 32. */
+ * x [B*L,Cin], sigma [B,32], dout / out [B*L,C], dx [B*L,Cin], dsigma [B,32]: device, f32.  L even, Cin and C/2 multiples of 32, and
+ * B*L*max(Cin, C) < 2^31 (the GEMM's element offsets).  Every output — out, dx, dsigma and the ten gradient buffers — is written,
+ * whatever it held; x and dout are read in place.  The stream is synchronised before the call returns. */
 int dhw_train_convblock(int device, int B, int L, int cin, int cout, const float* x, const float* sigma, const float* dout,
                         const dhw_convblock_weights* w, float* out, float* dx, float* dsigma, const dhw_convblock_grads* g,
                         void* hip_stream);
