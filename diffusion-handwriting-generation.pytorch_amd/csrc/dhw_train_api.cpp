@@ -16,6 +16,7 @@
 #include "abi_guard.h"
 #include "dhw_kernels.h"
 #include "host/device_arena.h"
+#include "train/train_common.h"
 
 namespace {
 
@@ -226,6 +227,45 @@ int dhw_train_draw(const uint64_t* rng, int B, int L, float* eps, long long n_ke
     if (!rng || !eps || !keep || B < 1 || L < 1 || n_keep < 1 || keep_per_sample < 4 || keep_per_sample % 4 || n_keep % keep_per_sample || p < 0.f || p >= 1.f)
       return tfail(DHW_ERR_ARG, "dhw_train_draw: bad argument");
     THIP(launch_train_draw(rng, B, L, eps, n_keep, keep_per_sample, p, keep, (hipStream_t)hip_stream));
+    return 0;
+  });
+}
+
+int dhw_train_batch_draw(const uint64_t* rng, int N, int B, const float* abar, int T, const int32_t* grp_start, const int32_t* grp_size,
+                         const int32_t* grp_pos, const int32_t* members, int32_t* idx, int32_t* style_src, float* alphas, float* sigma, void* hip_stream) {
+  TRAIN_GUARD("dhw_train_batch_draw", int, {
+    if (N < 1) return tfail(DHW_ERR_ARG, "dhw_train_batch_draw: N = %d must be >= 1", N);
+    if (B < 1) return tfail(DHW_ERR_ARG, "dhw_train_batch_draw: B = %d must be >= 1", B);
+    if (T < 2) return tfail(DHW_ERR_ARG, "dhw_train_batch_draw: T = %d must be >= 2", T);
+    const void* need[] = {rng, abar, idx, style_src, alphas, sigma};
+    const char* names[] = {"rng", "abar", "idx", "style_src", "alphas", "sigma"};
+    for (int i = 0; i < 6; ++i)
+      if (!need[i]) return tfail(DHW_ERR_ARG, "dhw_train_batch_draw: %s is NULL", names[i]);
+    const int given = !!grp_start + !!grp_size + !!grp_pos + !!members;
+    if (given != 0 && given != 4) return tfail(DHW_ERR_ARG, "dhw_train_batch_draw: the group tables (grp_start, grp_size, grp_pos, members) are all NULL or all set");
+    THIP(launch_batch_draw(rng, N, B, abar, T, grp_start, grp_size, grp_pos, members, idx, style_src, alphas, sigma, (hipStream_t)hip_stream));
+    return 0;
+  });
+}
+
+int dhw_train_batch_gather(const float* strokes, const int64_t* text, const float* style, const int32_t* idx, const int32_t* style_src, int N, int B, int L,
+                           int Lt, int S, float* x, float* pen, int64_t* ids, float* mask, float* style_out, void* hip_stream) {
+  TRAIN_GUARD("dhw_train_batch_gather", int, {
+    if (N < 1) return tfail(DHW_ERR_ARG, "dhw_train_batch_gather: N = %d must be >= 1", N);
+    if (B < 1) return tfail(DHW_ERR_ARG, "dhw_train_batch_gather: B = %d must be >= 1", B);
+    if (L < 8 || L % 8) return tfail(DHW_ERR_ARG, "dhw_train_batch_gather: L = %d must be a positive multiple of 8", L);
+    if (Lt < 1) return tfail(DHW_ERR_ARG, "dhw_train_batch_gather: Lt = %d must be >= 1", Lt);
+    if (S < 1) return tfail(DHW_ERR_ARG, "dhw_train_batch_gather: S = %d must be >= 1", S);
+    const void* need[] = {strokes, text, style, idx, style_src, x, pen, ids, mask, style_out};
+    const char* names[] = {"strokes", "text", "style", "idx", "style_src", "x", "pen", "ids", "mask", "style_out"};
+    const unsigned align[] = {16, 8, 16, 4, 4, 16, 16, 8, 4, 16};   // the kernel moves style and stroke rows in 16-byte pieces, tokens in 8
+    for (int i = 0; i < 10; ++i) {
+      if (!need[i]) return tfail(DHW_ERR_ARG, "dhw_train_batch_gather: %s is NULL", names[i]);
+      if ((uintptr_t)need[i] % align[i]) return tfail(DHW_ERR_ARG, "dhw_train_batch_gather: %s must be %u-byte aligned", names[i], align[i]);
+    }
+    const long long per = (long long)S * 320 + L / 4 + Lt;   // 16-byte pieces and tokens of one sample, one thread each
+    if (per > 0x7fffff00LL || (per + 255) / 256 * B > 0x7fffffffLL) return tfail(DHW_ERR_ARG, "dhw_train_batch_gather: B * S = %d * %d is too large for one launch", B, S);
+    THIP(launch_batch_gather(strokes, text, style, idx, style_src, N, B, L, Lt, S, x, pen, ids, mask, style_out, (hipStream_t)hip_stream));
     return 0;
   });
 }

@@ -12,3 +12,9 @@ DHW_DEV f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 inline unsigned nb(long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace dhw_train
+
+// train/batch.hip: the batch of one update drawn and gathered from a dataset resident on the device (include/dhw_train.h)
+hipError_t launch_batch_draw(const uint64_t* rng, int N, int B, const float* abar, int T, const int* grp_start, const int* grp_size, const int* grp_pos,
+                             const int* members, int* idx, int* style_src, float* alphas, float* sigma, hipStream_t st);
+hipError_t launch_batch_gather(const float* strokes, const int64_t* text, const float* style, const int* idx, const int* style_src, int N, int B, int L, int Lt,
+                               int S, float* x, float* pen, int64_t* ids, float* mask, float* style_out, hipStream_t st);

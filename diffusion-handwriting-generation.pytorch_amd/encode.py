@@ -120,12 +120,13 @@ def encode_strokes(lines, L=None, rounds: int = 3, max_abs: float = 15.0, device
     return strokes, lengths, status
 
 
-def make_batches(lines, texts, style, max_seq_len: int = 480, max_text_len: int = 50) -> dict:
+def make_batches(lines, texts, style, max_seq_len: int = 480, max_text_len: int = 50, writers=None) -> dict:
     """Training samples in the form train.py --data reads: {"strokes" f32 [K,max_seq_len,3], "text" int64 [K,max_text_len],
     "style" f32 [K,14,1280], "kept": the indices of the K samples kept}, on the host.  Lines are encoded by encode_strokes at
     L = max_seq_len, texts tokenised and zero-padded; a sample whose line has a non-zero status or whose
     len(text) >= max_text_len is dropped, as the reference's IAMDataset drops it.  style: [B,14,1280] from load_style /
-    StyleExtractor, one per line."""
+    StyleExtractor, one per line.  ``writers``: one integer writer id per line; the dict then also holds "writer" (int64 [K], the
+    kept lines'), from which train.py --resident takes each sample's style from another line of the same writer."""
     import torch
 
     from .tokenizer import Tokenizer
@@ -137,6 +138,10 @@ def make_batches(lines, texts, style, max_seq_len: int = 480, max_text_len: int 
     style = torch.as_tensor(style)
     if tuple(style.shape) != (len(lines), 14, 1280):
         raise ValueError(f"style must be [{len(lines)}, 14, 1280], got {tuple(style.shape)}")
+    if writers is not None:
+        w = np.asarray(writers.cpu() if isinstance(writers, torch.Tensor) else writers)
+        if w.shape != (len(lines),) or w.dtype.kind not in "iu":
+            raise ValueError(f"writers must hold {len(lines)} integer ids, got shape {tuple(w.shape)} dtype {w.dtype}")
     strokes, _, status = encode_strokes(lines, L=max_seq_len)
     status = status.cpu().tolist()
     kept = [i for i, t in enumerate(texts) if status[i] == 0 and len(t) < max_text_len]
@@ -146,4 +151,7 @@ def make_batches(lines, texts, style, max_seq_len: int = 480, max_text_len: int 
         ids = tk.encode(texts[i])
         text[r, :len(ids)] = torch.tensor(ids, dtype=torch.int64)
     idx = torch.tensor(kept, dtype=torch.int64)
-    return {"strokes": strokes.cpu()[idx], "text": text, "style": style.detach().cpu().float()[idx], "kept": kept}
+    out = {"strokes": strokes.cpu()[idx], "text": text, "style": style.detach().cpu().float()[idx], "kept": kept}
+    if writers is not None:
+        out["writer"] = torch.from_numpy(w.astype(np.int64))[idx]
+    return out

@@ -925,18 +925,117 @@ def train_step(model: TrainModel, optimizer: Adam, batch: dict, alpha_set: torch
     return out
 
 
+def group_tables(writers):
+    """The four int32 tables ``dhw_train_batch_draw`` picks a style source from, on the host: for ``writers`` = one integer id per
+    sample [N] -> (grp_start [N], grp_size [N], grp_pos [N], members [N]).  ``members`` lists the samples writer by writer (each
+    group in ascending sample order); sample n's group is ``members[grp_start[n] : grp_start[n] + grp_size[n]]`` and n itself sits
+    at ``grp_pos[n]`` in it."""
+    w = np.asarray(writers.cpu() if isinstance(writers, torch.Tensor) else writers)
+    if w.ndim != 1 or w.size < 1 or w.dtype.kind not in "iu":
+        raise ValueError(f"writers must be a non-empty 1-D integer array, got shape {tuple(w.shape)} dtype {w.dtype}")
+    if w.size >= 2 ** 31:
+        raise ValueError(f"{w.size} samples: the group tables are int32")
+    n = w.size
+    members = np.argsort(w, kind="stable")                                  # writer by writer, ascending sample index inside one
+    sw = w[members]
+    first = np.flatnonzero(np.concatenate(([True], sw[1:] != sw[:-1])))    # where each group starts in members
+    sizes = np.diff(np.concatenate((first, [n])))
+    start_of = np.repeat(first, sizes)                                      # per position in members: its group's start
+    grp_start, grp_size, grp_pos = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+    grp_start[members] = start_of
+    grp_size[members] = np.repeat(sizes, sizes)
+    grp_pos[members] = np.arange(n) - start_of
+    return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)) for a in (grp_start, grp_size, grp_pos, members))
+
+
+class ResidentData:
+    """A training set resident on the device: what ``train.py --data`` reads — {"strokes" f32 [N,L,3], "text" int64 [N,Lt], "style"
+    f32 [N,S,1280]} and optionally ``writers`` (default ``data.get("writer")``), one integer id per sample — uploaded ONCE, for a
+    ``GraphedTrainStep`` that draws and gathers its batch inside the replayed graph (dhw_train_batch_draw / _gather).  With writers
+    the step takes each sample's style from a random OTHER line of the same writer at every update (reference dataset.py:110-115).
+    Shapes, dtypes and every token id are checked here, once, before the device is touched; the upload is refused with both
+    numbers when the bytes do not fit the device's free memory.  The tensors must not be written or replaced afterwards: captured
+    graphs hold their addresses."""
+
+    def __init__(self, data: dict, device=None, writers=None):
+        from . import spec
+        for k in ("strokes", "text", "style"):
+            if k not in data or not isinstance(data[k], torch.Tensor):
+                raise ValueError(f"data[`{k}`] must be a torch tensor")
+        st, tx, sy = data["strokes"], data["text"], data["style"]
+        if st.dim() != 3 or st.shape[2] != 3 or st.dtype != torch.float32:
+            raise ValueError(f"`strokes` must be float32 [N, L, 3], got {st.dtype} {tuple(st.shape)}")
+        N, L = int(st.shape[0]), int(st.shape[1])
+        if N < 1 or N >= 2 ** 31:
+            raise ValueError(f"the dataset must hold 1 to 2^31 - 1 samples, got {N}")
+        if L < 8 or L % 8:
+            raise ValueError(f"the stroke length must be a positive multiple of 8 (three AvgPool1d(2) stages), got {L}")
+        if tx.dim() != 2 or tx.shape[0] != N or tx.shape[1] < 1 or tx.dtype != torch.int64:
+            raise ValueError(f"`text` must be int64 [{N}, Lt], got {tx.dtype} {tuple(tx.shape)}")
+        if sy.dim() != 3 or sy.shape[0] != N or sy.shape[1] < 1 or sy.shape[2] != 1280 or sy.dtype != torch.float32:
+            raise ValueError(f"`style` must be float32 [{N}, S, 1280], got {sy.dtype} {tuple(sy.shape)}")
+        if int(tx.min()) < 0 or int(tx.max()) >= spec.VOCAB:
+            raise ValueError(f"token id out of the embedding's range [0, {spec.VOCAB})")
+        if writers is None:
+            writers = data.get("writer")
+        tables = None
+        if writers is not None:
+            w = np.asarray(writers.cpu() if isinstance(writers, torch.Tensor) else writers)
+            if w.shape != (N,) or w.dtype.kind not in "iu":
+                raise ValueError(f"writers must be an integer array [{N}], got shape {tuple(w.shape)} dtype {w.dtype}")
+            tables = group_tables(w)
+        self.N, self.L, self.Lt, self.S = N, L, int(tx.shape[1]), int(sy.shape[1])
+        self.max_token = int(tx.max())
+        need = sum(t.numel() * t.element_size() for t in (st, tx, sy)) + (16 * N if tables else 0)
+        # ---- the device, from here on
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        free, _ = torch.cuda.mem_get_info(dev)
+        if need > free:
+            raise ValueError(f"the dataset needs {need} bytes on {dev}, which has {free} bytes free")
+        self.dev, self.nbytes = dev, need
+        self._strokes, self._text, self._style = (t.contiguous().to(dev) for t in (st, tx, sy))
+        self._tables = tuple(t.to(dev) for t in tables) if tables else None
+
+    strokes = property(lambda self: self._strokes)
+    text = property(lambda self: self._text)
+    style = property(lambda self: self._style)
+    tables = property(lambda self: self._tables)       # (grp_start, grp_size, grp_pos, members) on the device, or None
+
+
 class GraphedTrainStep:
     """``train_step`` with its gradient computation captured once into a hipGraph and replayed: the ~1100 kernel launches of
     an update (draws, perturbation, forward, loss, backward) become one graph launch, which takes the host off the critical
     path; the gradient all-reduce (multi-rank) and clip + Adam follow as three eager launches.  The batch
     lives in static device buffers that each call overwrites; the step's learning rate and Adam bias corrections are 8 floats
-    in device memory rewritten before every replay.  One instance serves one batch shape (B, L, Lt, S)."""
+    in device memory rewritten before every replay.  One instance serves one batch shape (B, L, Lt, S).
+
+    With ``data`` (a ``ResidentData``) the batch never crosses the bus: the step's first two launches draw B sample indices, the
+    noise levels and the style sources (dhw_train_batch_draw) and gather the rows into the static buffers (dhw_train_batch_gather),
+    inside the graph; the host sends the draw index and the optimizer's scalars only, and the call is ``step(step=n)``."""
 
     def __init__(self, model: TrainModel, optimizer: Adam, B: int, L: int, Lt: int, S: int = 14, d_model: int = 256, warmup: int = 10000,
-                 lr_mul: float = 1.0, device_rng: bool = True, seed: int = 0):
+                 lr_mul: float = 1.0, device_rng: bool = True, seed: int = 0, data: "ResidentData | None" = None, alpha_set=None):
         """``device_rng``: eps and the style Dropout mask are drawn inside the step by the library's Philox generator (as the
-        reference draws them on its device, train.py:39, text_style.py:97); False: the caller passes them (tests)."""
+        reference draws them on its device, train.py:39, text_style.py:97); False: the caller passes them (tests).
+        ``data`` with ``alpha_set`` (the schedule's cumulative products, uploaded here): train from the resident dataset; the step
+        keeps ``data`` alive, since the captured graph holds its addresses."""
+        if data is not None:
+            if not device_rng:
+                raise ValueError("a step that draws its batch from resident data draws eps and the masks on the device too (device_rng=True)")
+            if (data.L, data.Lt, data.S) != (L, Lt, S):
+                raise ValueError(f"the resident data holds strokes [N, {data.L}, 3], text [N, {data.Lt}], style [N, {data.S}, 1280]; "
+                                 f"this step is built for L = {L}, Lt = {Lt}, S = {S}")
+            if alpha_set is None or len(alpha_set) < 2:
+                raise ValueError("a step on resident data needs alpha_set (at least two cumulative products) at construction")
+            if data.max_token >= model.p["text_style_model.emb.weight"].d.shape[0]:
+                raise ValueError("token id out of the embedding's range")
+            index = lambda d: torch.cuda.current_device() if torch.device(d).index is None else torch.device(d).index   # noqa: E731
+            if index(data.dev) != index(model.dev):
+                raise ValueError(f"the resident data lives on {data.dev}, the model on {model.dev}")
+        elif alpha_set is not None:
+            raise ValueError("alpha_set at construction belongs to a step on resident data; a host-fed step takes it per call")
         dev = model.dev
+        self.data = data
         self.device_rng, self.seed = device_rng, seed
         self.rng = model.rng           # one generator state for the eps / style draws and the model's dropout sites
         self.model, self.opt = model, optimizer
@@ -950,6 +1049,11 @@ class GraphedTrainStep:
         fields = [("ids", (B, Lt), torch.int64), ("rng", (2,), torch.int64), ("x", (B, L, 2), torch.float32), ("pen", (B, L), torch.float32),
                   ("alphas", (B,), torch.float32), ("sigma", (B, 1), torch.float32), ("mask", (B, Lt), torch.float32),
                   ("hyper", (9,), torch.float32), ("style", (B, S, 1280), torch.float32)]
+        if data is not None:       # the batch is gathered on the device: the block is the draw index and the optimizer's scalars, 64 bytes
+            resident = {name: torch.zeros(shape, dtype=dt, device=dev) for name, shape, dt in fields if name not in ("rng", "hyper")}
+            fields = [f for f in fields if f[0] in ("rng", "hyper")]
+            self.idx, self.style_src = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
+            self.abar = torch.as_tensor(alpha_set, dtype=torch.float32).contiguous().to(dev)
         if not device_rng:
             fields += [("eps", (B, L, 2), torch.float32), ("keep", (B, S, 1280), torch.float32)]
         offs, off = {}, 0
@@ -963,7 +1067,7 @@ class GraphedTrainStep:
         self._stage_turn = 0
         carve = lambda buf: {k: buf[o:o + n].view(dt).view(shape) for k, (o, n, shape, dt) in offs.items()}   # noqa: E731
         self._dv, self._hv = carve(self._stage_dev), [carve(h) for h in self._stage_host]
-        d = self._dv
+        d = self._dv if data is None else {**self._dv, **resident}
         self.x, self.pen, self.alphas, self.sigma, self.ids, self.mask, self.style, self.hyper = (d[k] for k in ("x", "pen", "alphas", "sigma", "ids", "mask", "style", "hyper"))
         self.eps = d["eps"] if not device_rng else z(B, L, 2)
         self.keep = d["keep"] if not device_rng else z(B, S, 1280)
@@ -982,6 +1086,14 @@ class GraphedTrainStep:
         x_pert = torch.empty_like(self.x)
         lib = _lib.lib()
         st = _stream(m.dev)
+        if self.data is not None:
+            dt, tb = self.data, self.data.tables or (None,) * 4
+            ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+            _tcheck(lib.dhw_train_batch_draw(self.rng.data_ptr(), dt.N, B, self.abar.data_ptr(), self.abar.numel(), *(ptr(t) for t in tb), self.idx.data_ptr(),
+                                             self.style_src.data_ptr(), self.alphas.data_ptr(), self.sigma.data_ptr(), st))
+            _tcheck(lib.dhw_train_batch_gather(dt.strokes.data_ptr(), dt.text.data_ptr(), dt.style.data_ptr(), self.idx.data_ptr(), self.style_src.data_ptr(),
+                                               dt.N, B, L, dt.Lt, dt.S, self.x.data_ptr(), self.pen.data_ptr(), self.ids.data_ptr(), self.mask.data_ptr(),
+                                               self.style.data_ptr(), st))
         if self.device_rng:
             _tcheck(lib.dhw_train_draw(self.rng.data_ptr(), B, L, self.eps.data_ptr(), self.keep.numel(), self.keep.numel() // B,
                                        TrainModel.STYLE_DROP, self.keep.data_ptr(), st))
@@ -1042,14 +1154,32 @@ class GraphedTrainStep:
             raise RuntimeError(f"captured {len(segs)} graph segments for {N_BUCKETS} gradient buckets")
         return segs
 
-    def __call__(self, batch: dict, alpha_set, step: int, *, eps=None, alphas=None, style_keep=None, graph: bool = True):
+    def last_draw(self):
+        """The device tensors (idx int32 [B], style_src int32 [B], alphas f32 [B]) of the last update of a step on resident data:
+        the samples it trained on, where each one's style row came from, and the noise levels."""
+        if self.data is None:
+            raise ValueError("this step is fed from the host: it draws no batch")
+        return self.idx, self.style_src, self.alphas
+
+    def __call__(self, batch: dict | None = None, alpha_set=None, step: int | None = None, *, eps=None, alphas=None, style_keep=None, graph: bool = True):
+        """Host-fed: ``step(batch, alpha_set, n)``.  On resident data: ``step(step=n)`` — the batch, the noise levels, eps and the
+        masks are all drawn on the device from (seed, n), so passing any of them is an error."""
+        if self.data is not None:
+            given = [k for k, v in (("batch", batch), ("alpha_set", alpha_set), ("alphas", alphas), ("eps", eps), ("style_keep", style_keep)) if v is not None]
+            if given:
+                raise ValueError(f"this step draws its batch from resident data: call step(step=n) without {', '.join(given)}")
+        if step is None:
+            raise ValueError("step (the update number, >= 1) is required")
         B, L, Lt, S = self.shape
-        strokes3 = batch["strokes"]
-        if tuple(strokes3.shape) != (B, L, 3) or tuple(batch["text"].shape) != (B, Lt) or tuple(batch["style"].shape) != (B, S, 1280):
-            raise ValueError(f"this step was built for strokes {(B, L, 3)}, text {(B, Lt)}, style {(B, S, 1280)}")
-        self.model.check_tokens(batch["text"])
-        if alphas is None:
-            alphas = get_alphas(B, alpha_set)
+        if self.data is None:
+            if batch is None:
+                raise ValueError("a host-fed step needs a batch")
+            strokes3 = batch["strokes"]
+            if tuple(strokes3.shape) != (B, L, 3) or tuple(batch["text"].shape) != (B, Lt) or tuple(batch["style"].shape) != (B, S, 1280):
+                raise ValueError(f"this step was built for strokes {(B, L, 3)}, text {(B, Lt)}, style {(B, S, 1280)}")
+            self.model.check_tokens(batch["text"])
+            if alphas is None:
+                alphas = get_alphas(B, alpha_set)
         rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
         world = torch.distributed.get_world_size() if torch.distributed.is_available() and torch.distributed.is_initialized() else 1
         turn = self._stage_turn
@@ -1064,13 +1194,14 @@ class GraphedTrainStep:
         else:
             hv["eps"].copy_(eps if eps is not None else torch.randn(B, L, 2))
             hv["keep"].copy_(style_keep if style_keep is not None else (torch.rand(B, S, 1280) >= TrainModel.STYLE_DROP).float())
-        hv["x"].copy_(strokes3[:, :, :2])
-        hv["pen"].copy_(strokes3[:, :, 2])
-        hv["alphas"].copy_(alphas.reshape(B))
-        hv["sigma"].copy_(torch.sqrt(alphas).reshape(B, 1))
-        hv["ids"].copy_(batch["text"])
-        hv["mask"].copy_(batch["text"] == 0)
-        hv["style"].copy_(batch["style"])
+        if self.data is None:
+            hv["x"].copy_(strokes3[:, :, :2])
+            hv["pen"].copy_(strokes3[:, :, 2])
+            hv["alphas"].copy_(alphas.reshape(B))
+            hv["sigma"].copy_(torch.sqrt(alphas).reshape(B, 1))
+            hv["ids"].copy_(batch["text"])
+            hv["mask"].copy_(batch["text"] == 0)
+            hv["style"].copy_(batch["style"])
         hv["hyper"].copy_(torch.tensor(self.opt.hyper(noam_lr(step, *self.sched), 1.0 / world), dtype=torch.float32))
         self._gscale = 1.0 / world
         self._stage_dev.copy_(self._stage_host[turn], non_blocking=True)
@@ -1144,7 +1275,7 @@ def read_train_config(config_path) -> dict:
             "seed": int((cfg.get("experiment") or {}).get("seed", 0))}
 
 
-def fit(config_path, data_path=None, out_dir="runs/exp", steps=None, init=None, seed=0, log=print, precision="fp32"):
+def fit(config_path, data_path=None, out_dir="runs/exp", steps=None, init=None, seed=0, log=print, precision="fp32", resident=False):
     """The reference's ``TrainingLoop.train`` (train.py:84-134): updates until ``training_args.steps``, a log line every
     ``log_freq`` updates (mean losses since the last line), ``checkpoint_<n>.pth`` every ``save_freq``, ``model_final.pth`` at
     the end.  Cadence and numbering are the reference's own (train.py:111-126): after update number ``count`` it tests
@@ -1153,11 +1284,16 @@ def fit(config_path, data_path=None, out_dir="runs/exp", steps=None, init=None, 
     gradients averaged by RCCL); rank 0 logs and saves.  ``training_args.batch_size`` is the PER-RANK batch (the reference is
     single-process, so its 96 is one GPU's batch): N ranks train on a global batch of N x batch_size — divide it in the config to
     keep the reference's global batch.  ``precision``: "fp32" (the reference's) or "bf16" (bf16-rounded GEMM operands, fp32
-    accumulation and fp32 master weights / optimizer state).  Returns the trained ``TrainModel``."""
+    accumulation and fp32 master weights / optimizer state).  ``resident``: upload the dataset of ``data_path`` once
+    (``ResidentData``, with its "writer" key if it has one) and let every update draw and gather its batch on the device — no
+    per-update host work beyond the draw index; every rank keeps the whole set and draws with its own index step * world + rank.
+    Returns the trained ``TrainModel``."""
     import os
     import time
     from . import spec
     from .checkpoint import read_state_dict
+    if resident and not data_path:
+        raise ValueError("resident=True trains from a dataset on the device: it needs data_path")
     cfg = read_train_config(config_path)
     n_steps = steps if steps is not None else cfg["steps"]
     # the host side draws abar and assembles batches with small torch CPU ops: with one thread per VISIBLE core on a box whose
@@ -1183,7 +1319,6 @@ def fit(config_path, data_path=None, out_dir="runs/exp", steps=None, init=None, 
     sd = read_state_dict(init) if init else spec.synthetic_state_dict(cfg["num_layers"], cfg["c1"], cfg["c2"], cfg["c3"], seed=seed)
     model = TrainModel(sd, num_layers=cfg["num_layers"], device=dev, drop_rate=cfg["dropout"], seed=seed, precision=precision)
     opt = Adam(model.parameters(), betas=cfg["betas"], weight_decay=cfg["weight_decay"], max_norm=cfg["clip_grad"] or 0.0)
-    step_fn = GraphedTrainStep(model, opt, B, L, Lt, d_model=2 * cfg["c1"], warmup=cfg["warmup"], seed=seed)
     alpha_set = torch.cumprod(1 - (0.02 + torch.exp(torch.linspace(math.log(1e-5), math.log(0.4), 60))), dim=0)   # utils/nn.py:19-39
     gen = torch.Generator().manual_seed(cfg["seed"] * 1000 + rank)
     data = None
@@ -1192,6 +1327,8 @@ def fit(config_path, data_path=None, out_dir="runs/exp", steps=None, init=None, 
         for k, shape in (("strokes", (L, 3)), ("text", (Lt,)), ("style", (14, 1280))):
             if k not in data or tuple(data[k].shape[1:]) != shape:
                 raise ValueError(f"{data_path}: `{k}` must be [N, {', '.join(map(str, shape))}]")
+    rd = ResidentData(data, dev) if resident else None
+    step_fn = GraphedTrainStep(model, opt, B, L, Lt, d_model=2 * cfg["c1"], warmup=cfg["warmup"], seed=seed, data=rd, alpha_set=alpha_set if resident else None)
 
     def next_batch():
         if data is not None:                      # a random batch, as `next(iter(shuffled loader))` gives (train.py:99)
@@ -1204,7 +1341,7 @@ def fit(config_path, data_path=None, out_dir="runs/exp", steps=None, init=None, 
     os.makedirs(out_dir, exist_ok=True)
     acc, t0 = [], time.time()
     for count in range(1, n_steps + 1):
-        acc.append(step_fn(next_batch(), alpha_set, count).clone())
+        acc.append((step_fn(step=count) if resident else step_fn(next_batch(), alpha_set, count)).clone())
         if (count + 1) % cfg["log_freq"] == 0:      # (train.py:111: the reference's own off-by-one, reproduced)
             m = torch.stack(acc).mean(0).tolist()   # (one host sync per log line)
             acc = []

@@ -56,6 +56,29 @@ int dhw_train_adam_dev(int nbuf, float* const* p, const float* const* g, float* 
  * draw index}; sample b of draw d is stream d * B + b, so ranks pass disjoint draw indices.  Capturable. */
 int dhw_train_draw(const uint64_t* rng, int B, int L, float* eps, long long n_keep, int keep_per_sample, float p, float* keep, void* hip_stream);
 
+/* The training batch of one update drawn on the device, for a dataset that is resident there (N samples): one Philox block per
+ * batch sample b — key = the seed rng[0], counter = (stream rng[1] * B + b, 0, 0); word 3 of the counter is 0 here, 1 for eps, 2 for
+ * the style mask, >= 3 for the dropout sites — whose four output words w0..w3 give
+ *   idx[b]       = (w0 * N) >> 32                a sample in [0, N), with replacement (next(iter(train_loader)), train.py:98)
+ *   alphas[b]    = u (abar[i+1] - abar[i]) + abar[i], i = (w1 * (T - 1)) >> 32, u = ((w2 >> 8) + 0.5) 2^-24: get_alphas' formula
+ *                  (utils/nn.py:42-61) in three separately rounded fp32 operations; sigma[b] = sqrt(alphas[b]), correctly rounded
+ *   style_src[b] = idx[b] without group tables; with them a uniform draw (w3) over the OTHER members of idx[b]'s group — a different line
+ *                  of the same writer (dataset.py:110-115) —, idx[b] itself in a group of one.
+ * The multiply-high mapping onto [0, n) is biased by at most n / 2^32.  abar: DEVICE f32 [T], the schedule's cumulative products.
+ * Group tables (DEVICE int32, all NULL or all set): grp_start / grp_size / grp_pos [N] = where sample n's group starts in members, how
+ * many members it has, and n's position among them; members [N] = the samples group by group.  They are trusted: every entry must
+ * lie in [0, N) and grp_start[n] + grp_size[n] <= N.  idx, style_src: int32 [B]; alphas, sigma: f32 [B].  Capturable. */
+int dhw_train_batch_draw(const uint64_t* rng, int N, int B, const float* abar, int T, const int32_t* grp_start, const int32_t* grp_size,
+                         const int32_t* grp_pos, const int32_t* members, int32_t* idx, int32_t* style_src, float* alphas, float* sigma, void* hip_stream);
+
+/* Rows of the resident dataset into a step's input buffers: strokes [N,L,3] row idx[b] -> x [B,L,2] and pen [B,L]; text int64 [N,Lt] row
+ * idx[b] -> ids [B,Lt] and mask f32 [B,Lt] (1 where the id is 0); style [N,S,1280] row style_src[b] -> style_out [B,S,1280].  L is a
+ * multiple of 8; strokes, style, x, pen and style_out are 16-byte aligned, text and ids 8-byte.  idx / style_src are DEVICE int32 [B], so
+ * a bad one cannot be reported: a sample whose idx or style_src lies outside [0, N) is never dereferenced — all its outputs are zeros and
+ * its mask is 1 everywhere.  Capturable. */
+int dhw_train_batch_gather(const float* strokes, const int64_t* text, const float* style, const int32_t* idx, const int32_t* style_src, int N, int B, int L,
+                           int Lt, int S, float* x, float* pen, int64_t* ids, float* mask, float* style_out, void* hip_stream);
+
 typedef struct {   /* HOST pointers, torch layouts */
   const float *conv1_w, *conv1_b;   /* [C/2, Cin, 3], [C/2] */
   const float *conv2_w, *conv2_b;   /* [C, C/2, 3], [C] */

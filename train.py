@@ -12,6 +12,8 @@ dataset.py:143-157; read with weights_only=True); without it, synthetic batches 
 runs — the IAM corpus and its preprocessing are outside this package).  Writes checkpoint_<n>.pth in save_checkpoint's form
 ({"meta": None, "state_dict": ...}, reference checkpoint.py:244) and model_final.pth as the bare state_dict (train.py:131),
 both with the reference's 323 keys; cadence and numbering follow the reference ((count + 1) % freq, see fit()).
+`--resident` uploads the --data set once (with its optional "writer" key, int [N]) and draws and gathers every batch on the GPU inside
+the replayed graph; a sample's style then comes from a random other line of the same writer (dataset.py:110-115).
 --precision bf16 selects the mixed-precision GEMMs (fp32 master weights and optimizer state); batch_size is per rank."""
 import argparse
 
@@ -22,13 +24,14 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True)
     ap.add_argument("--data")
+    ap.add_argument("--resident", action="store_true", help="keep the --data set on the GPU and draw every batch there (style from another line of the same writer)")
     ap.add_argument("--out", default="runs/exp")
     ap.add_argument("--steps", type=int, help="override training_args.steps")
     ap.add_argument("--init", help="state_dict to start from (.pth)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"], help="GEMM operand precision (fp32 = the reference's)")
     a = ap.parse_args(argv)
-    dhg_amd.train_model.fit(a.config, a.data, a.out, steps=a.steps, init=a.init, seed=a.seed, precision=a.precision)
+    dhg_amd.train_model.fit(a.config, a.data, a.out, steps=a.steps, init=a.init, seed=a.seed, precision=a.precision, resident=a.resident)
 
 
 if __name__ == "__main__":
