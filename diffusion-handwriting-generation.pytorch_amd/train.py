@@ -4,7 +4,7 @@ HIP (include/dhw_train.h): the forward-diffusion perturbation, ``loss_fn`` with 
 Adam on flat buffers, ConvBlock forward + backward as one call.  Host logic mirrored here: ``get_alphas`` (the reference's
 torch RNG calls, in its order), the Noam learning-rate schedule, and the data-parallel gradient all-reduce
 (``torch.distributed``: RCCL over xGMI on the GPU ranks).  The whole model's forward / backward and the complete update
-are in ``train_model.py``.
+are in the ``train_model`` package.
 """
 from __future__ import annotations
 
@@ -105,6 +105,14 @@ class Adam:
         sizes = (C.c_int64 * n)(*[p.numel() for p in self.params])
         _tcheck(_lib.lib().dhw_train_adam_dev(n, arr(self.params), arr(grads), arr(self.m), arr(self.v), sizes, hyper_dev.data_ptr(),
                                               sqnorm_dev.data_ptr(), _stream(dev)))
+
+
+def dist_state():
+    """(a process group is active, this rank, world size); (False, 0, 1) without one.  A one-rank group counts as active: it takes
+    the same code path as a larger one."""
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        return True, torch.distributed.get_rank(), torch.distributed.get_world_size()
+    return False, 0, 1
 
 
 def allreduce_grads(flat_grads, world_size: int | None = None, average: bool = True):

@@ -1,4 +1,4 @@
-"""The whole training step in HIP (dhg_amd/train_model.py over include/dhw_train.h dhw_op_*): each generic operation against
+"""The whole training step in HIP (dhg_amd/train_model/ over include/dhw_train.h dhw_op_*): each generic operation against
 torch's CPU operator + autograd on the same seeded inputs, then DiffusionModel forward + loss.backward() against the fixture
 the imported reference generated (tests/golden/model_grad.npz, oracle/make_golden_r2.py model_grad_fixture): outputs, losses
 and ALL 323 parameter gradients (norm + projection on a fixed random direction each, a few small ones element-wise)."""
@@ -250,7 +250,7 @@ def test_gemm_entry_points_reach_the_right_kernel_instantiation():
             y[:, -s:] = xv[:, :L + s]
         return y.reshape(x.shape)
 
-    # Conv1d(k = 3, 'same') on C-last rows, weights [tap][Cout][Cin] (conv3 of train_model.py): forward, weight gradient, data gradient
+    # Conv1d(k = 3, 'same') on C-last rows, weights [tap][Cout][Cin] (Tape.conv3, train_model/tape.py): forward, weight gradient, data gradient
     def conv_fwd(x, W, L, y, bf16=0, a_off=0):
         (R, Cin), Cout = x.shape, W.shape[1]
         d = desc(dev(x, a_off), Cin, 1, dev(W), 1, Cin, y, R, Cout, 3 * Cin, bf16=bf16, taps=3, a_shift=-1, a_tap_shift=1, sbt=Cout * Cin, lr=L)

@@ -22,7 +22,7 @@ if mode in ("seg_bucketed", "flat", "seg_noreduce"):
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29581")
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
 if mode == "flat":
-    tm.GRAD_BUCKETS = False
+    tm.step.GRAD_BUCKETS = False
 B, L, Lt = 32, 480, 50
 sd = spec.synthetic_state_dict(2, 128, 192, 256, seed=0)
 model = tm.TrainModel(sd, num_layers=2, device=dev)
