@@ -68,6 +68,11 @@ SIGNATURES = {
     "dhw_ddim_invert": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
                                   _P, _P]),
     "dhw_ddim_update": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
+    "dhw_guided_ddim_sample": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                         C.POINTER(C.c_float), _P, C.c_uint64, C.c_int64, _P, _P, _P]),
+    "dhw_guided_sample": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_float), _P,
+                                    C.c_uint64, C.c_int64, _P, _P]),
+    "dhw_guide_update": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
     "dhw_attention_shape": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dhw_attention": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _P, _P, _P, _P, _P, _P]),
     "dhw_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
@@ -119,6 +124,7 @@ SIGNATURES = {
     "dhw_train_draw": (C.c_int, [_P, C.c_int, C.c_int, _P, _LL, C.c_int, C.c_float, _P, _P]),
     "dhw_train_batch_draw": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dhw_train_batch_gather": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "dhw_train_cond_drop": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P]),
     "dhw_train_convblock": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.POINTER(ConvBlockWeights), _P, _P, _P,
                                       C.POINTER(ConvBlockWeights), _P]),
     "dhw_train_last_error": (C.c_char_p, []),

@@ -270,6 +270,26 @@ int dhw_train_batch_gather(const float* strokes, const int64_t* text, const floa
   });
 }
 
+int dhw_train_cond_drop(const uint64_t* rng, int B, int Lt, int S, float p, int64_t* ids, float* mask, float* style, int32_t* dropped, void* hip_stream) {
+  TRAIN_GUARD("dhw_train_cond_drop", int, {
+    if (B < 1) return tfail(DHW_ERR_ARG, "dhw_train_cond_drop: B = %d must be >= 1", B);
+    if (Lt < 1) return tfail(DHW_ERR_ARG, "dhw_train_cond_drop: Lt = %d must be >= 1", Lt);
+    if (S < 1) return tfail(DHW_ERR_ARG, "dhw_train_cond_drop: S = %d must be >= 1", S);
+    if (!(p >= 0.f && p <= 1.f)) return tfail(DHW_ERR_ARG, "dhw_train_cond_drop: p = %g must lie in [0, 1]", (double)p);
+    const void* need[] = {rng, ids, mask, style, dropped};
+    const char* names[] = {"rng", "ids", "mask", "style", "dropped"};
+    const unsigned align[] = {8, 8, 4, 16, 4};   // the kernel moves style rows in 16-byte pieces, tokens in 8
+    for (int i = 0; i < 5; ++i) {
+      if (!need[i]) return tfail(DHW_ERR_ARG, "dhw_train_cond_drop: %s is NULL", names[i]);
+      if ((uintptr_t)need[i] % align[i]) return tfail(DHW_ERR_ARG, "dhw_train_cond_drop: %s must be %u-byte aligned", names[i], align[i]);
+    }
+    const long long per = (long long)S * 320 + Lt;   // 16-byte pieces and tokens of one sample, one thread each
+    if (per > 0x7fffff00LL || (per + 255) / 256 * B > 0x7fffffffLL) return tfail(DHW_ERR_ARG, "dhw_train_cond_drop: B * S = %d * %d is too large for one launch", B, S);
+    THIP(launch_cond_drop(rng, B, Lt, S, p, ids, mask, style, dropped, (hipStream_t)hip_stream));
+    return 0;
+  });
+}
+
 int dhw_op_keep_mask(const uint64_t* rng, int site, long long n, int per_sample, float p, float* keep, void* hip_stream) {
   TRAIN_GUARD("dhw_op_keep_mask", int, {
     if (!rng || !keep || site < 3 || n < 1 || per_sample < 4 || per_sample % 4 || n % per_sample || p < 0.f || p >= 1.f)

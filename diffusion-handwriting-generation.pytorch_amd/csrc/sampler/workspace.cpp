@@ -186,5 +186,7 @@ void destroy_impl(dhw_handle* h) {
   if (h->h_lens_pin) hipHostFree(h->h_lens_pin);
   if (h->h_prof_skip) hipHostFree(h->h_prof_skip);
   if (h->lens_ev) hipEventDestroy(h->lens_ev);
+  if (h->h_guide_scale_pin) hipHostFree(h->h_guide_scale_pin);
+  if (h->guide_ev) hipEventDestroy(h->guide_ev);
   delete h;
 }

@@ -18,3 +18,5 @@ hipError_t launch_batch_draw(const uint64_t* rng, int N, int B, const float* aba
                              const int* members, int* idx, int* style_src, float* alphas, float* sigma, hipStream_t st);
 hipError_t launch_batch_gather(const float* strokes, const int64_t* text, const float* style, const int* idx, const int* style_src, int N, int B, int L, int Lt,
                                int S, float* x, float* pen, int64_t* ids, float* mask, float* style_out, hipStream_t st);
+// train/cond_drop.hip: conditioning dropout on a step's input buffers (include/dhw_train.h)
+hipError_t launch_cond_drop(const uint64_t* rng, int B, int Lt, int S, float p, int64_t* ids, float* mask, float* style, int* dropped, hipStream_t st);

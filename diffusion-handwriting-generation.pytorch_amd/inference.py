@@ -3,6 +3,8 @@ loop (reference inference.py:80-96) for a whole prompt batch; ``infer`` wraps it
 the tokenizer and the stroke-length heuristic (inference.py:65-78)."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -44,10 +46,96 @@ def _check_strokes(strokes, name: str = "strokes"):
     return int(strokes.shape[0]), int(strokes.shape[1])
 
 
+# ---------------------------------------------------------------- classifier-free guidance (include/dhw.h dhw_guided_*)
+MAX_GUIDANCE = 64.0
+
+
+def null_condition(B: int, Lt: int, S: int = 14):
+    """The condition guided sampling extrapolates away from and conditioning dropout trains (include/dhw_train.h
+    dhw_train_cond_drop): ``text`` int64 [B,Lt] with every row ``[1, 0, 0, ...]`` — ``Tokenizer().encode("")``, the end token,
+    then padding (not an all-padding row) — and ``style`` f32 [B,S,1280] of zeros."""
+    B, Lt, S = _check_int("B", B, 1), _check_int("Lt", Lt, 1), _check_int("S", S, 1)
+    ids = Tokenizer().encode("")
+    if len(ids) > Lt:
+        raise ValueError(f"Lt = {Lt} is shorter than the empty prompt's {len(ids)} token(s)")
+    text = torch.zeros((B, Lt), dtype=torch.int64)
+    text[:, :len(ids)] = torch.tensor(ids, dtype=torch.int64)
+    return text, torch.zeros((B, S, 1280), dtype=torch.float32)
+
+
+def _guided_kw(guidance, candidates: int, B: int | None = None) -> dict:
+    """What a front end passes on for its ``guidance`` argument: nothing for None (the unguided calls stay as they are, argument
+    for argument); refused next to best-of-N, whose candidates are scored as unguided samples."""
+    if guidance is None:
+        return {}
+    if candidates > 1:
+        raise ValueError("guidance cannot be combined with candidates > 1 (best-of-N ranks unguided samples by score)")
+    if B is not None:
+        _check_guidance(guidance, B)
+    return {"guidance": guidance}
+
+
+def _check_guidance(guidance, B: int) -> list:
+    """``guidance`` (a real number, or B of them as a sequence or tensor) -> B floats, each finite and in [0, MAX_GUIDANCE]."""
+    if isinstance(guidance, torch.Tensor):
+        guidance = guidance.detach().cpu().tolist()
+    if isinstance(guidance, np.ndarray):
+        guidance = guidance.tolist()
+    is_num = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))   # noqa: E731
+    if is_num(guidance):
+        seq = [guidance] * B
+    else:
+        try:
+            seq = list(guidance)
+        except TypeError:
+            raise ValueError(f"guidance must be a number or a sequence of B = {B} numbers, got {type(guidance).__name__}") from None
+        if len(seq) != B:
+            raise ValueError(f"guidance has {len(seq)} entries, B = {B} are needed")
+    for b, v in enumerate(seq):
+        if not is_num(v):
+            raise ValueError(f"guidance[{b}] = {v!r} is not a number")
+        if not (0.0 <= float(np.float32(v)) <= MAX_GUIDANCE):    # (a NaN fails the range test)
+            raise ValueError(f"guidance[{b}] = {v!r} must be finite and lie in [0, {MAX_GUIDANCE:g}]")
+    return [float(np.float32(v)) for v in seq]
+
+
+def _guided_pair(text, style_vector, uncond_text, uncond_style):
+    """The 2B-row condition of a guided call, checked on the host: rows [0, B) the real condition, rows [B, 2B) the guidance
+    condition (each half of ``null_condition`` unless given) -> (text2 int64 [2B,Lt], style2 f32 [2B,S,1280])."""
+    B, Lt = text.shape
+    if not isinstance(style_vector, torch.Tensor) or style_vector.dim() != 3 or style_vector.shape[0] != B or style_vector.shape[2] != 1280:
+        raise ValueError(f"style_vector must be a tensor [B = {B}, S, 1280]")
+    if text.dtype.is_floating_point or text.dtype == torch.bool:
+        raise ValueError("text must be an integer tensor [B, Lt]")
+    S = int(style_vector.shape[1])
+    nt, ns = null_condition(B, Lt, S)
+    if uncond_text is not None:
+        if not isinstance(uncond_text, torch.Tensor) or uncond_text.dtype.is_floating_point or uncond_text.dtype == torch.bool:
+            raise ValueError("uncond_text must be an integer tensor [B, Lt]")
+        if tuple(uncond_text.shape) != (B, Lt):
+            raise ValueError(f"uncond_text must be [B,Lt] = {(B, Lt)}, got {tuple(uncond_text.shape)}")
+        nt = uncond_text
+    if uncond_style is not None:
+        if not isinstance(uncond_style, torch.Tensor) or not uncond_style.dtype.is_floating_point:
+            raise ValueError("uncond_style must be a floating-point tensor [B,S,1280]")
+        if tuple(uncond_style.shape) != (B, S, 1280):
+            raise ValueError(f"uncond_style must be [B,S,1280] = {(B, S, 1280)}, got {tuple(uncond_style.shape)}")
+        ns = uncond_style
+    dev = next((t.device for t in (text, style_vector, nt, ns) if t.is_cuda), text.device)
+    text2 = torch.cat((text.to(dev, torch.int64), nt.to(dev, torch.int64)), dim=0)
+    style2 = torch.cat((style_vector.to(dev, torch.float32), ns.to(dev, torch.float32)), dim=0)
+    return text2, style2
+
+
+def _scale_array(scale):
+    return (C.c_float * len(scale))(*scale)
+
+
 def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor, L: int | None = None, T: int = 60,
            diffusion_mode: str = "new", noise: torch.Tensor | None = None, seed: int = 0,
            first_sample: int = 0, lengths=None, known: torch.Tensor | None = None, keep: torch.Tensor | None = None,
-           t_start: int | None = None, cond_noise: torch.Tensor | None = None) -> torch.Tensor:
+           t_start: int | None = None, cond_noise: torch.Tensor | None = None, guidance=None, uncond_text: torch.Tensor | None = None,
+           uncond_style: torch.Tensor | None = None) -> torch.Tensor:
     """Reverse-sample a batch.  text int [B,Lt] (0 = pad), style_vector [B,S,1280] -> [B,L,3] = (dx, dy, pen).
 
     ``lengths`` (optional, B ints, multiples of 8 in [8, L]; ``L`` then defaults to max(lengths)): a ragged batch — prompts
@@ -65,9 +153,23 @@ def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor
     iterations run, from ``known`` noised to that level (restyling: the line keeps its layout, ``style_vector`` decides the
     hand; see ``restyle``).  ``cond_noise`` f32 [T,B,L,2]: the draws that re-noise the kept rows, required exactly when both
     ``noise`` and ``keep`` are given.  Rows of ``known`` that are neither kept nor (``t_start`` < T) seeded are never read.
+
+    Classifier-free guidance (include/dhw.h dhw_guided_sample).  ``guidance``: a scale, or B of them; every step
+    asks the denoiser under the real condition and under the guidance condition (``uncond_text`` / ``uncond_style``, each
+    defaulting to its half of ``null_condition``; ``uncond_style=style_vector`` guides on the text alone) in ONE forward of 2B
+    rows and moves along ``e_c + (guidance - 1) (e_c - e_u)``.  1 is the ordinary sample, 0 the guidance condition's.  The call
+    launches eagerly (no graph), draws the same noise as the unguided call, and is refused together with the conditioning
+    arguments.  ``None``: today's path, argument for argument.
     """
     if diffusion_mode not in ("new", "standard"):
         raise ValueError("diffusion_mode must be 'new' or 'standard'")
+    if guidance is None and (uncond_text is not None or uncond_style is not None):
+        raise ValueError("uncond_text / uncond_style belong to a guided call (guidance is None)")
+    if guidance is not None:
+        given = [k for k, v in (("known", known), ("keep", keep), ("t_start", t_start), ("cond_noise", cond_noise)) if v is not None]
+        if given:
+            raise ValueError(f"guidance cannot be combined with conditioned sampling ({', '.join(given)})")
+        return _sample_guided(model, text, style_vector, L, T, diffusion_mode, noise, seed, first_sample, lengths, guidance, uncond_text, uncond_style)
     B, Lt = text.shape
     lens = None
     if lengths is not None:
@@ -97,6 +199,34 @@ def sample(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor
             c.run("dhw_sample", *head, T, mode, c.ptr(nz), seed, first_sample, out.data_ptr())
         else:
             c.run("dhw_sample_ragged", *head, c.lens(lens), T, mode, c.ptr(nz), seed, first_sample, out.data_ptr())
+    return out.to(text.device)
+
+
+def _sample_guided(model, text, style_vector, L, T, diffusion_mode, noise, seed, first_sample, lengths, guidance, uncond_text, uncond_style):
+    """``sample(..., guidance=...)``: every rule on the host first, then dhw_guided_sample on a handle that holds 2B rows."""
+    if not isinstance(text, torch.Tensor) or text.dim() != 2:
+        raise ValueError("text must be an integer tensor [B, Lt]")
+    B, Lt = text.shape
+    lens = _check_ddim_common(text, style_vector, B, lengths, L)
+    if L is None:
+        L = max(lens) if lens is not None else stroke_length(Lt)
+    L = _check_int("L", L, 8)
+    if L % 8:
+        raise ValueError(f"L = {L} must be a multiple of 8")
+    T = _check_int("T", T, 1, 2 ** 29)
+    seed, first_sample = _check_int("seed", seed, 0, 2 ** 64 - 1), _check_int("first_sample", first_sample, -2 ** 63, 2 ** 63 - 1)
+    if noise is not None:
+        if not isinstance(noise, torch.Tensor) or not noise.dtype.is_floating_point:
+            raise ValueError("noise must be a floating-point tensor [T+1,B,L,2]")
+        if tuple(noise.shape) != (T + 1, B, L, 2):
+            raise ValueError(f"noise must be [T+1,B,L,2] = {(T + 1, B, L, 2)}")
+    scale = _check_guidance(guidance, B)
+    text2, style2 = _guided_pair(text, style_vector, uncond_text, uncond_style)
+    with model._device_call("guide", text2, (text2, style2) if noise is None else (text2, style2, noise), 2 * B, L, style2.shape[1]) as c:
+        t, sv, nz = c.to(text2, torch.int64), c.to(style2), c.to(noise)
+        out = c.empty((B, L, 3))
+        c.run("dhw_guided_sample", t.data_ptr(), sv.data_ptr(), B, L, Lt, c.lens(lens), T, 0 if diffusion_mode == "new" else 1, _scale_array(scale),
+              c.ptr(nz), seed, first_sample, out.data_ptr())
     return out.to(text.device)
 
 
@@ -145,16 +275,18 @@ def restyle(strokes: torch.Tensor, text: torch.Tensor, style_vector: torch.Tenso
 
 
 def infer(prompt: str, style_vector: torch.Tensor, model: DiffusionModel, diffusion_mode: str = "new", T: int = 60,
-          seed: int = 0, steps: int | None = None) -> np.ndarray:
+          seed: int = 0, steps: int | None = None, guidance=None) -> np.ndarray:
     """Single-prompt convenience wrapper with the reference's front end: tokenise, L = 16 per token rounded up
     to a multiple of 8, sample, return the [L,3] stroke array that the reference hands to ``show_strokes``.
-    ``steps``: sample deterministically at that many levels instead (``sample_ddim``; ``diffusion_mode`` then plays no part)."""
+    ``steps``: sample deterministically at that many levels instead (``sample_ddim``; ``diffusion_mode`` then plays no part).
+    ``guidance``: a classifier-free guidance scale against ``null_condition`` (``sample`` / ``sample_ddim``); None: unguided."""
+    guided = _guided_kw(guidance, 1, 1)
     ids = Tokenizer().encode(prompt)
     text = torch.tensor([ids], dtype=torch.int64)
     if steps is not None:
-        out = sample_ddim(model, text, style_vector, L=stroke_length(len(ids)), T=T, levels=ddim_levels(T, steps), seed=seed)
+        out = sample_ddim(model, text, style_vector, L=stroke_length(len(ids)), T=T, levels=ddim_levels(T, steps), seed=seed, **guided)
         return out[0].detach().cpu().numpy()
-    out = sample(model, text, style_vector, L=stroke_length(len(ids)), T=T, diffusion_mode=diffusion_mode, seed=seed)
+    out = sample(model, text, style_vector, L=stroke_length(len(ids)), T=T, diffusion_mode=diffusion_mode, seed=seed, **guided)
     return out[0].detach().cpu().numpy()
 
 
@@ -254,7 +386,8 @@ def _check_ddim_common(text, style_vector, B: int, lengths, L):
 
 def sample_ddim(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor, L: int | None = None, T: int = 60,
                 steps: int | None = None, levels=None, latent: torch.Tensor | None = None, seed: int = 0, first_sample: int = 0,
-                lengths=None, return_latent: bool = False):
+                lengths=None, return_latent: bool = False, guidance=None, uncond_text: torch.Tensor | None = None,
+                uncond_style: torch.Tensor | None = None):
     """Deterministic (DDIM, eta = 0) sampling over a sub-sequence of the schedule (include/dhw.h dhw_ddim_sample): one
     denoiser call per level and no noise after the start, so the line is a function of its start latent alone.
 
@@ -262,9 +395,14 @@ def sample_ddim(model: DiffusionModel, text: torch.Tensor, style_vector: torch.T
     themselves, strictly decreasing.  ``latent`` f32 [B,L,2]: the start (from ``invert``, ``slerp``, or an earlier call's
     ``return_latent=True``); without it the generator draws the x_T ``sample`` would draw for (seed, first_sample + b).
     ``lengths``: a ragged batch, as in ``sample``.  Returns [B,L,3] = (dx, dy, pen of the last call), or (strokes, latent [B,L,2])
-    with ``return_latent=True``.  The calls launch eagerly; they leave ``sample``'s cached graphs and generator state alone."""
+    with ``return_latent=True``.  The calls launch eagerly; they leave ``sample``'s cached graphs and generator state alone.
+
+    ``guidance`` (a scale, or B of them; ``uncond_text`` / ``uncond_style`` as in ``sample``): classifier-free guidance
+    (include/dhw.h dhw_guided_ddim_sample) over the same levels, from the same latent; ``None`` is today's call."""
     if not isinstance(text, torch.Tensor) or text.dim() != 2:
         raise ValueError("text must be an integer tensor [B, Lt]")
+    if guidance is None and (uncond_text is not None or uncond_style is not None):
+        raise ValueError("uncond_text / uncond_style belong to a guided call (guidance is None)")
     B, Lt = text.shape
     if latent is not None:
         if not isinstance(latent, torch.Tensor) or not latent.dtype.is_floating_point:
@@ -280,6 +418,15 @@ def sample_ddim(model: DiffusionModel, text: torch.Tensor, style_vector: torch.T
         raise ValueError(f"L = {L} must be a multiple of 8")
     lv = _check_ddim_levels(levels, steps, T)
     seed, first_sample = _check_int("seed", seed, 0, 2 ** 64 - 1), _check_int("first_sample", first_sample, -2 ** 63, 2 ** 63 - 1)
+    if guidance is not None:
+        scale = _check_guidance(guidance, B)
+        text2, style2 = _guided_pair(text, style_vector, uncond_text, uncond_style)
+        with model._device_call("guide", text2, (text2, style2) if latent is None else (text2, style2, latent), 2 * B, L, style2.shape[1]) as c:
+            t, sv, lat = c.to(text2, torch.int64), c.to(style2), c.to(latent)
+            lat_out, out = c.empty((B, L, 2), wanted=return_latent), c.empty((B, L, 3))
+            c.run("dhw_guided_ddim_sample", t.data_ptr(), sv.data_ptr(), B, L, Lt, c.lens(lens), T, c.lens(lv), len(lv), _scale_array(scale), c.ptr(lat),
+                  seed, first_sample, out.data_ptr(), c.ptr(lat_out))
+        return (out.to(text.device), lat_out.to(text.device)) if return_latent else out.to(text.device)
     tensors = (text, style_vector) if latent is None else (text, style_vector, latent)
     with model._device_call("ddim", text, tensors, B, L, style_vector.shape[1]) as c:
         t, sv, lat = c.to(text, torch.int64), c.to(style_vector), c.to(latent)
@@ -503,7 +650,7 @@ def _encode_batch(who: str, prompts, style_vector):
 
 
 def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diffusion_mode: str = "new", T: int = 60,
-                seed: int = 0, first_sample: int = 0, candidates: int = 1, levels=None, steps: int | None = None) -> list:
+                seed: int = 0, first_sample: int = 0, candidates: int = 1, levels=None, steps: int | None = None, guidance=None) -> list:
     """Many prompts in ONE ragged sampler call: prompt i is tokenised, gets its own ``L_i = stroke_length(n_i)`` and is padded
     with token 0 to the longest prompt.  ``style_vector`` is [1,S,1280] (one writer for every prompt) or [B,S,1280].  Returns a
     list of [L_i, 3] arrays; entry i equals ``sample(model, text_i, style_i, L=L_i, seed=seed, first_sample=first_sample + i)``.
@@ -514,16 +661,20 @@ def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diff
     (ties: the lower j).
 
     ``steps``: every line is sampled deterministically at that many levels (``sample_ddim`` with ``ddim_levels(T, steps)``)
-    instead; ``diffusion_mode`` then plays no part."""
+    instead; ``diffusion_mode`` then plays no part.
+
+    ``guidance``: a classifier-free guidance scale, or one per prompt, against ``null_condition`` (each call is then one forward
+    of 2B rows per step); refused together with ``candidates > 1``."""
     candidates = _check_candidates(candidates)
+    guided = _guided_kw(guidance, candidates)
     if steps is None:
         def draw(tx, st, ln, first):
-            return sample(model, tx, st, L=max(lens), T=T, diffusion_mode=diffusion_mode, seed=seed, first_sample=first, lengths=ln)
+            return sample(model, tx, st, L=max(lens), T=T, diffusion_mode=diffusion_mode, seed=seed, first_sample=first, lengths=ln, **guided)
     else:
         ddim = ddim_levels(T, steps)
 
         def draw(tx, st, ln, first):
-            return sample_ddim(model, tx, st, L=max(lens), T=T, levels=ddim, seed=seed, first_sample=first, lengths=ln)
+            return sample_ddim(model, tx, st, L=max(lens), T=T, levels=ddim, seed=seed, first_sample=first, lengths=ln, **guided)
     text, lens, sv = _encode_batch("infer_batch", prompts, style_vector)
     B = len(lens)
     if candidates == 1:
@@ -639,20 +790,22 @@ def _check_renderer(renderer: str) -> None:
 def infer_file(prompt: str, source, config_path: str | None = None, checkpoint_path: str | None = None,
                experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *, precision: str = "bf16",
                seed: int = 0, render: bool = True, style_weights: str | None = None, renderer: str = "matplotlib",
-               candidates: int = 1, steps: int | None = None) -> np.ndarray:
+               candidates: int = 1, steps: int | None = None, guidance=None) -> np.ndarray:
     """The reference's command-line entry (inference.py:19-27) around this build's sampler: resolve config / checkpoint
     (directly or inside ``experiment_path``), load the model, sample one prompt, write ``./<output>.png`` (``renderer``:
     "matplotlib" = the reference's figure, "gpu" = the 96-row grey line image of ``render_strokes``).
     ``candidates = N > 1``: the best of N samples by ``score`` (``infer_batch``).  ``steps``: deterministic sampling at that
-    many levels (``sample_ddim``).  Returns the [L,3] strokes."""
+    many levels (``sample_ddim``).  ``guidance``: a classifier-free guidance scale (``sample``).  Returns the [L,3] strokes."""
     from .checkpoint import load_model
 
     _check_renderer(renderer)
     candidates = _check_candidates(candidates)
     ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}   # (no steps: today's calls, argument for argument)
+    ddim.update(_guided_kw(guidance, candidates, 1))
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
-    model = load_model(config_path, checkpoint_path, precision=precision, max_B=_rounds_capacity(1, candidates), style_rows=style.shape[1])
+    model = load_model(config_path, checkpoint_path, precision=precision, max_B=2 if guidance is not None else _rounds_capacity(1, candidates),
+                       style_rows=style.shape[1])
     if candidates > 1:
         (strokes,) = infer_batch([prompt], style, model, diffusion_mode=diffusion_mode, seed=seed, candidates=candidates, **ddim)
     else:
@@ -706,21 +859,22 @@ def _open_lines(who: str, prompts, strokes_path, source, config_path, checkpoint
 def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint_path: str | None = None,
                      experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
                      precision: str = "bf16", seed: int = 0, render: bool = True, style_weights: str | None = None,
-                     renderer: str = "matplotlib", candidates: int = 1, steps: int | None = None) -> list:
+                     renderer: str = "matplotlib", candidates: int = 1, steps: int | None = None, guidance=None) -> list:
     """``infer_file`` for many prompts of one writer: one ragged sampler call (``infer_batch``), ``./<output>_<i>.png`` per
     prompt (``renderer="gpu"``: every line rasterised in one ``render_strokes`` call).  ``candidates = N > 1``: every line is
-    the best of N samples by ``score``.  ``steps``: deterministic sampling at that many levels (``sample_ddim``).  Returns the
-    list of [L_i, 3] strokes."""
+    the best of N samples by ``score``.  ``steps``: deterministic sampling at that many levels (``sample_ddim``).  ``guidance``: a
+    classifier-free guidance scale, or one per prompt (``infer_batch``).  Returns the list of [L_i, 3] strokes."""
     from .checkpoint import load_model
 
     _check_renderer(renderer)
     candidates = _check_candidates(candidates)
     ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}
     prompts = list(prompts)
+    ddim.update(_guided_kw(guidance, candidates, max(1, len(prompts))))
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
-    model = load_model(config_path, checkpoint_path, precision=precision, max_B=_rounds_capacity(max(1, len(prompts)), candidates),
-                       style_rows=style.shape[1])
+    model = load_model(config_path, checkpoint_path, precision=precision,
+                       max_B=_rounds_capacity(max(1, len(prompts)), candidates) * (2 if guidance is not None else 1), style_rows=style.shape[1])
     strokes = infer_batch(prompts, style, model, diffusion_mode=diffusion_mode, seed=seed, candidates=candidates, **ddim)
     if render:
         _save_lines(strokes, [f"{output}_{i}" for i in range(len(strokes))], renderer)
@@ -765,14 +919,15 @@ def wrap_text(text: str, max_chars: int = 40):
 
 def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, max_chars: int = 40, diffusion_mode: str = "new",
                T: int = 60, seed: int = 0, first_sample: int = 0, candidates: int = 1, levels=None, steps: int | None = None,
-               pages=None, height: int = 1980, width: int = 1400, lines_per_page: int = 20, margin_left: float = 70.0,
+               guidance=None, pages=None, height: int = 1980, width: int = 1400, lines_per_page: int = 20, margin_left: float = 70.0,
                margin_top: float = 70.0, pitch: float = 92.0, line_width: float = 2.0, scale=None):
     """Write a text: ``wrap_text`` to lines, ``infer_batch`` for their strokes, ``render_page`` onto pages at one shared scale.
 
     ``style_vector`` is [1,S,1280] (one writer).  The lines are sampled in rounds of at most the model's batch capacity
     (``max_B``): the round that starts at line i0 is ``infer_batch(..., first_sample=first_sample + i0 * candidates)``, so with
     ``candidates = 1`` line i uses generator index ``first_sample + i`` however the rounds fall, and the rounds of a best-of-N
-    run never share an index.  The sampler arguments are ``infer_batch``'s, the page arguments ``render_page``'s; all are
+    run never share an index.  ``guidance`` (one scale for every line): a guided round is one forward of twice its lines, so the
+    rounds are half as long.  The sampler arguments are ``infer_batch``'s, the page arguments ``render_page``'s; all are
     checked, with ValueError, before a device is touched.
 
     Returns (pages f32 [P,1,height,width] on the GPU, the list of [L_i,3] stroke arrays, one per wrapped line)."""
@@ -788,6 +943,7 @@ def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, 
         ddim_levels(T, steps)
     if candidates > 1:
         _check_levels(levels, T)
+    guided = _guided_kw(guidance, candidates, 1)
     if diffusion_mode not in ("new", "standard"):
         raise ValueError(f"diffusion_mode must be 'new' or 'standard', got {diffusion_mode!r}")
     g = check_page_geometry(pages, height, width, lines_per_page, margin_left, margin_top, pitch, line_width, scale)
@@ -798,11 +954,11 @@ def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, 
         raise ValueError(f"style_vector must be [1,S,1280], got {tuple(sv.shape)}")
     _encode_batch("write_page", lines, sv)   # (an empty or untokenisable line is refused here, before the first round)
 
-    cap = max(1, int(model._cap["max_B"]))
+    cap = max(1, int(model._cap["max_B"]) // (2 if guided else 1))
     strokes = []
     for i0 in range(0, len(lines), cap):
         strokes += infer_batch(lines[i0:i0 + cap], sv, model, diffusion_mode=diffusion_mode, T=T, seed=seed,
-                               first_sample=first_sample + i0 * candidates, candidates=candidates, levels=levels, steps=steps)
+                               first_sample=first_sample + i0 * candidates, candidates=candidates, levels=levels, steps=steps, **guided)
     out, _, _ = render_page(pad_strokes(strokes), [len(s) for s in strokes], slots, pages=pages, height=height, width=width,
                             lines_per_page=lines_per_page, margin_left=margin_left, margin_top=margin_top, pitch=pitch,
                             line_width=line_width, scale=scale)
@@ -812,7 +968,7 @@ def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, 
 def write_page_file(text: str, source, config_path: str | None = None, checkpoint_path: str | None = None,
                     experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
                     precision: str = "bf16", seed: int = 0, style_weights: str | None = None, candidates: int = 1,
-                    steps: int | None = None, **page_kwargs) -> list:
+                    steps: int | None = None, guidance=None, **page_kwargs) -> list:
     """``infer.py --page-file``: resolve config / checkpoint as ``infer_file`` does, ``write_page`` the text in the hand of
     ``source`` and save ``./<output>_p<k>.png`` per page (``vis.save_page_png``).  Returns the list of [L_i,3] strokes."""
     from .checkpoint import load_model
@@ -823,6 +979,7 @@ def write_page_file(text: str, source, config_path: str | None = None, checkpoin
         raise ValueError("write_page_file: the text holds no word")
     candidates = _check_candidates(candidates)
     ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}
+    ddim.update(_guided_kw(guidance, candidates, 1))
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
     model = load_model(config_path, checkpoint_path, precision=precision, max_B=_rounds_capacity(min(len(lines), 64), candidates),

@@ -9,7 +9,7 @@ import torch
 from ..train import Adam, dist_state
 from .data import ResidentData
 from .net import TrainModel
-from .step import GraphedTrainStep
+from .step import GraphedTrainStep, check_cond_drop
 
 
 def _granted_cores() -> int:
@@ -44,7 +44,7 @@ def read_train_config(config_path) -> dict:
             "seed": int((cfg.get("experiment") or {}).get("seed", 0))}
 
 
-def fit(config_path, data_path=None, out_dir="runs/exp", steps=None, init=None, seed=0, log=print, precision="fp32", resident=False):
+def fit(config_path, data_path=None, out_dir="runs/exp", steps=None, init=None, seed=0, log=print, precision="fp32", resident=False, cond_drop=0.0):
     """The reference's ``TrainingLoop.train`` (train.py:84-134): updates until ``training_args.steps``, a log line every
     ``log_freq`` updates (mean losses since the last line), ``checkpoint_<n>.pth`` every ``save_freq``, ``model_final.pth`` at
     the end.  Cadence and numbering are the reference's own (train.py:111-126): after update number ``count`` it tests
@@ -56,12 +56,15 @@ def fit(config_path, data_path=None, out_dir="runs/exp", steps=None, init=None, 
     accumulation and fp32 master weights / optimizer state).  ``resident``: upload the dataset of ``data_path`` once
     (``ResidentData``, with its "writer" key if it has one) and let every update draw and gather its batch on the device — no
     per-update host work beyond the draw index; every rank keeps the whole set and draws with its own index step * world + rank.
+    ``cond_drop``: the probability with which a sample trains under ``null_condition`` instead of its prompt and writer
+    (``GraphedTrainStep``), which gives the checkpoint the unconditional branch that guided sampling needs; 0.1 is customary.
     Returns the trained ``TrainModel``."""
     import time
     from .. import spec
     from ..checkpoint import read_state_dict
     if resident and not data_path:
         raise ValueError("resident=True trains from a dataset on the device: it needs data_path")
+    check_cond_drop(cond_drop)
     cfg = read_train_config(config_path)
     n_steps = steps if steps is not None else cfg["steps"]
     # the host side draws abar and assembles batches with small torch CPU ops: with one thread per VISIBLE core on a box whose
@@ -92,7 +95,8 @@ def fit(config_path, data_path=None, out_dir="runs/exp", steps=None, init=None, 
             if k not in data or tuple(data[k].shape[1:]) != shape:
                 raise ValueError(f"{data_path}: `{k}` must be [N, {', '.join(map(str, shape))}]")
     rd = ResidentData(data, dev) if resident else None
-    step_fn = GraphedTrainStep(model, opt, B, L, Lt, d_model=2 * cfg["c1"], warmup=cfg["warmup"], seed=seed, data=rd, alpha_set=alpha_set if resident else None)
+    step_fn = GraphedTrainStep(model, opt, B, L, Lt, d_model=2 * cfg["c1"], warmup=cfg["warmup"], seed=seed, data=rd, alpha_set=alpha_set if resident else None,
+                               cond_drop=cond_drop)
 
     def next_batch():
         if data is not None:                      # a random batch, as `next(iter(shuffled loader))` gives (train.py:99)

@@ -51,6 +51,13 @@ def train_step(model: TrainModel, optimizer: Adam, batch: dict, alpha_set: torch
     return out
 
 
+def check_cond_drop(cond_drop) -> float:
+    """The one rule for a conditioning-dropout probability (``GraphedTrainStep``, ``fit``): a real number in [0, 1]."""
+    if isinstance(cond_drop, bool) or not isinstance(cond_drop, (int, float)) or not 0.0 <= float(cond_drop) <= 1.0:
+        raise ValueError(f"cond_drop = {cond_drop!r} must be a number in [0, 1]")
+    return float(cond_drop)
+
+
 class GraphedTrainStep:
     """``train_step`` with its gradient computation captured once into a hipGraph and replayed: the ~1100 kernel launches of
     an update (draws, perturbation, forward, loss, backward) become one graph launch, which takes the host off the critical
@@ -63,11 +70,20 @@ class GraphedTrainStep:
     inside the graph; the host sends the draw index and the optimizer's scalars only, and the call is ``step(step=n)``."""
 
     def __init__(self, model: TrainModel, optimizer: Adam, B: int, L: int, Lt: int, S: int = 14, d_model: int = 256, warmup: int = 10000,
-                 lr_mul: float = 1.0, device_rng: bool = True, seed: int = 0, data: "ResidentData | None" = None, alpha_set=None):
+                 lr_mul: float = 1.0, device_rng: bool = True, seed: int = 0, data: "ResidentData | None" = None, alpha_set=None,
+                 cond_drop: float = 0.0):
         """``device_rng``: eps and the style Dropout mask are drawn inside the step by the library's Philox generator (as the
         reference draws them on its device, train.py:39, text_style.py:97); False: the caller passes them (tests).
         ``data`` with ``alpha_set`` (the schedule's cumulative products, uploaded here): train from the resident dataset; the step
-        keeps ``data`` alive, since the captured graph holds its addresses."""
+        keeps ``data`` alive, since the captured graph holds its addresses.
+        ``cond_drop`` in [0, 1]: conditioning dropout for classifier-free guidance (dhw_train_cond_drop) — with that probability a
+        sample trains under ``null_condition`` instead of its prompt and writer; one launch on the step's own input buffers, behind
+        the gather or the copy from the host and in front of the draws.  It needs ``device_rng=True``; 0 allocates and launches
+        nothing."""
+        check_cond_drop(cond_drop)
+        if cond_drop > 0 and not device_rng:
+            raise ValueError("cond_drop > 0 draws which samples lose their condition on the device: it needs device_rng=True")
+        self.cond_drop = float(cond_drop)
         if data is not None:
             if not device_rng:
                 raise ValueError("a step that draws its batch from resident data draws eps and the masks on the device too (device_rng=True)")
@@ -122,6 +138,7 @@ class GraphedTrainStep:
         d["rng"].copy_(model.rng)
         self.rng = model.rng = d["rng"]      # (the model's dropout sites read the same generator state: one pointer, inside the block)
         self.sqnorm, self.out = z(1), z(3)
+        self.dropped = torch.zeros(B, dtype=torch.int32, device=dev) if self.cond_drop > 0 else None
         model.prepare_tables(L, Lt)
         self.graph = None
         self.segments, self._reducer = None, None     # with a process group: N_BUCKETS graph segments + the bucketed all-reduce
@@ -142,6 +159,9 @@ class GraphedTrainStep:
             _tcheck(lib.dhw_train_batch_gather(dt.strokes.data_ptr(), dt.text.data_ptr(), dt.style.data_ptr(), self.idx.data_ptr(), self.style_src.data_ptr(),
                                                dt.N, B, L, dt.Lt, dt.S, self.x.data_ptr(), self.pen.data_ptr(), self.ids.data_ptr(), self.mask.data_ptr(),
                                                self.style.data_ptr(), st))
+        if self.cond_drop > 0:
+            _tcheck(lib.dhw_train_cond_drop(self.rng.data_ptr(), B, self.shape[2], self.shape[3], self.cond_drop, self.ids.data_ptr(), self.mask.data_ptr(),
+                                            self.style.data_ptr(), self.dropped.data_ptr(), st))
         if self.device_rng:
             _tcheck(lib.dhw_train_draw(self.rng.data_ptr(), B, L, self.eps.data_ptr(), self.keep.numel(), self.keep.numel() // B,
                                        TrainModel.STYLE_DROP, self.keep.data_ptr(), st))
@@ -207,6 +227,13 @@ class GraphedTrainStep:
         if self.data is None:
             raise ValueError("this step is fed from the host: it draws no batch")
         return self.idx, self.style_src, self.alphas
+
+    def last_dropped(self):
+        """The device tensor int32 [B] of the last update of a step with ``cond_drop`` > 0: 1 where the sample trained under the
+        null condition."""
+        if self.dropped is None:
+            raise ValueError("this step was built with cond_drop = 0: it drops no condition")
+        return self.dropped
 
     def __call__(self, batch: dict | None = None, alpha_set=None, step: int | None = None, *, eps=None, alphas=None, style_keep=None, graph: bool = True):
         """Host-fed: ``step(batch, alpha_set, n)``.  On resident data: ``step(step=n)`` — the batch, the noise levels, eps and the

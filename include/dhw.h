@@ -290,6 +290,68 @@ int dhw_ddim_invert(dhw_handle*, const float* strokes, const int64_t* text, cons
 int dhw_ddim_update(const float* base, const float* eps, const int32_t* lens, int B, int L,
                     float c0, float c1, float c2, float c3, float* out, void* hip_stream);
 
+/* Classifier-free guidance: sampling that extrapolates from the denoiser's answer under a GUIDANCE condition (by default the
+ * null condition: the prompt [1, 0, 0, ...] = the end token then padding, and an all-zero style; training hides both with
+ * dhw_train_cond_drop) towards its answer under the real one.  Scale 1 is the ordinary sample, larger scales trade diversity for
+ * legibility, scale 0 is the guidance condition's own sample.
+ *
+ * The guided noise estimate of stroke row (b, p), per coordinate, with e_c the denoiser's eps under the real condition, e_u under
+ * the guidance condition and w = scale[b]:
+ *    e = fadd(e_c, fmul(fsub(w, 1), fsub(e_c, e_u)))     for w != 0;        e = e_u     for w == 0.
+ * Every operation is rounded to nearest, nothing is contracted.  At w = 1 the product is a zero and e has e_c's value (a -0 may
+ * become +0).  The arithmetic alone gives e_c - fl(e_c - e_u) at w = 0, which is e_u only where that difference is exact; w = 0 is
+ * therefore a select, so that scale 0 IS the sample under the guidance condition.  The pen probability is the conditional row's.
+ *
+ * One forward per step.  text2 int64 [2B,Lt] and style2 f32 [2B,S,1280] (device): rows [0, B) hold the real condition, rows
+ * [B, 2B) the guidance condition of rows [0, B).  The state holds x twice; each step is one forward of the 2B rows (the launches
+ * and the precision of dhw_forward_ragged, dhw_forward when lens == NULL) and one step kernel that reads x[b], e[b] and e[b+B] and
+ * writes the new row to x[b] and x[b+B].  lens: HOST int32 [B] or NULL, the rules of dhw_forward_ragged; it applies to both halves.
+ * scale: HOST f32 [B], every entry finite and in [0, 64].  2B <= the handle's max_B.
+ *
+ * dhw_guided_ddim_sample
+ *    T, levels, S, latent, seed, first_sample, latent_out, out: as dhw_ddim_sample.  x(0) as there; steps j = 0..S-1:
+ *    x(j+1) = U(x(j), e; A_j, B_j, A_{j+1}, B_{j+1}) with dhw_ddim_sample's U, coefficient table and levels.  out[b,p] =
+ *    (x(S)[b,p], q_c of the last call) for p < lens[b]; rows at or past lens[b] of out and latent_out are 0.
+ *
+ * dhw_guided_sample
+ *    T, mode, noise, seed, first_sample, out: as dhw_sample.  x_T = noise[0], or the generator's draw for (seed, first_sample + b, p,
+ *    iter = -1).  Iteration k = 0..T-1 at schedule index i = T-1-k, sigma = sqrtf(abar_i) for every row, with the coefficients
+ *    dhw_sample computes on the host in fp32 and z = noise[1+k][b,p] (noise f32 [T+1,B,L,2], device) or the generator's draw for
+ *    (seed, first_sample + b, p, k) — the keys dhw_sample uses:
+ *       mode 0 ("new"):       x = fadd(fdiv(fsub(x, fmul(k0, e)), k1), fmul(z, k2))
+ *       mode 1 ("standard"):  x = fmul(k1, fsub(x, fdiv(fmul(k3, e), k0))), then for i != 0 x = fadd(x, fmul(k2, z))
+ *    one rounding per operation, dhw_sample's own order.  out[b,p] = (x, q_c of the last call), 0 at and past lens[b].
+ *
+ * dhw_guide_update
+ *    The one step kernel on given device arrays, so that it can be pinned bit for bit on its own.  kind 0: U(base, e; c0..c3); 1:
+ *    the "new" step with (k0, k1, k2) = (c0, c1, c2); 2: the "standard" step with (k0, k1, k2, k3) = (c0, c1, c2, c3).  base: device
+ *    f32, rows [0, B L) x 2 are read; eps2 f32 [2B,L,2]; pen f32, rows [0, B L) (read only with out3; NULL without it); lens DEVICE
+ *    int32 [B] or NULL, any 0 <= n (n >= L: every row); scale DEVICE f32 [B] (not range-checked: it is device memory); z f32 [B,L,2]
+ *    or NULL: the noise term is added iff z is given (kind 0 takes none).  out f32 [2B,L,2] or NULL: row r = b L + p and row r + B L
+ *    both receive the new value (out may be base); out3 f32 [B,L,3] or NULL = (new value, pen).  Rows at or past lens[b] are
+ *    written as 0 and not read.  No handle: errors are read through dhw_last_error(NULL).  B, L >= 1, 2 B L < 2^31.
+ *
+ * Rules for the entries.
+ *    Arguments.  Every check runs before the first HIP call and returns DHW_ERR_ARG naming the argument: required pointers
+ *       non-NULL; the forward entry's limits (B, L, Lt, lens); the level checks of dhw_ddim_sample, or 1 <= T <= 2^29 and mode 0 / 1;
+ *       every scale finite and within [0, 64]; 2B <= max_B (both numbers are in the message); 2 B L < 2^31; latent, latent_out,
+ *       noise, base, eps2, z and dhw_guide_update's out 8-byte aligned.
+ *    Determinism.  No atomics, no reductions: the result is bit-deterministic; row b equals sample b run alone at L = lens[b]
+ *       with first_sample + b and scale[b]; a row's result does not depend on the other rows' scales.
+ *    Side effects, as for dhw_ddim_sample.  Launches are eager on hip_stream.  The state lives in the ddim entries' scratch set
+ *       (x, eps, pen, sigma) used at 2B rows; the scales are copied to a [max_B] device array the handle allocates at its first guided
+ *       call and never moves.  Nothing of the sampler's is touched: not its graph cache, its generator state, its staging
+ *       buffers, its step plans or its text-plane tag.  The entries work on a handle created with DHW_PERSIST=1. */
+int dhw_guided_ddim_sample(dhw_handle*, const int64_t* text2, const float* style2, int B, int L, int Lt, const int32_t* lens,
+                           int T, const int32_t* levels, int S, const float* scale, const float* latent, uint64_t seed,
+                           int64_t first_sample, float* out, float* latent_out, void* hip_stream);
+int dhw_guided_sample(dhw_handle*, const int64_t* text2, const float* style2, int B, int L, int Lt, const int32_t* lens, int T,
+                      int mode, const float* scale, const float* noise, uint64_t seed, int64_t first_sample, float* out,
+                      void* hip_stream);
+int dhw_guide_update(int kind, const float* base, const float* eps2, const float* pen, const int32_t* lens, const float* scale,
+                     const float* z, int B, int L, float c0, float c1, float c2, float c3, float* out, float* out3,
+                     void* hip_stream);
+
 /* Stroke rasteriser: sampled strokes -> grey-level line images in the layout dhw_style_forward consumes (ink
  * left-aligned, white to the right).  No handle: errors are read through dhw_last_error(NULL).  The call allocates
  * nothing, synchronises nothing and can be captured into a graph.  All argument checks run before the first HIP call

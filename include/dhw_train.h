@@ -9,6 +9,8 @@
  *   dhw_train_convblock  <- ConvBlock.forward + its autograd backward (cnn.py:64-87): the first block of the denoiser's
  *                           backward pass as ONE entry point, issued on the generic operations below (weights uploaded per call,
  *                           in torch layout).
+ *   dhw_train_cond_drop  <- conditioning dropout for classifier-free guidance: a sample loses its prompt and its writer (no reference
+ *                           counterpart)
  *   dhw_op_*             <- the generic fp32 operations from which dhg_amd/train_model.py assembles the WHOLE
  *                           DiffusionModel forward (train mode) and backward — every parameter gradient of the
  *                           reference's loss.backward() (train.py:55-60).
@@ -78,6 +80,20 @@ int dhw_train_batch_draw(const uint64_t* rng, int N, int B, const float* abar, i
  * its mask is 1 everywhere.  Capturable. */
 int dhw_train_batch_gather(const float* strokes, const int64_t* text, const float* style, const int32_t* idx, const int32_t* style_src, int N, int B, int L,
                            int Lt, int S, float* x, float* pen, int64_t* ids, float* mask, float* style_out, void* hip_stream);
+
+/* Conditioning dropout (classifier-free guidance, dhw.h dhw_guided_*): with probability p a batch sample loses its prompt AND its
+ * writer, in place in a step's input buffers, so that the trained denoiser also answers the null condition.  One Philox block per
+ * batch sample b — key = the seed rng[0], counter = (stream rng[1] * B + b, 1, 0): word 2 = 1 with word 3 = 0, a counter no other
+ * consumer uses (word 2 = 0 with word 3 = 0 is dhw_train_batch_draw, word 3 = 1 eps, 2 the style mask, >= 3 the dropout sites) —
+ * whose first output word w0 gives
+ *   u = ((w0 >> 8) + 0.5) 2^-24 in fp32,   dropped[b] = (u < p)            (p = 0 drops none, p = 1 drops all)
+ * A dropped sample's ids row becomes [1, 0, 0, ...] (the end token, then padding: Tokenizer().encode(""); NOT an all-padding row),
+ * its mask row [0, 1, 1, ...] (1 where the id is 0) and its S style rows 0: exactly dhg_amd.null_condition, which guided sampling
+ * uses.  Samples that are kept are rewritten with what they held.  Strokes, pen, alphas and eps are untouched: a dropped sample
+ * trains the same loss.  ids int64 [B,Lt] (8-byte aligned), mask f32 [B,Lt], style f32 [B,S,1280] (16-byte aligned), dropped int32
+ * [B] (written for every b); 0 <= p <= 1.  Capturable. */
+int dhw_train_cond_drop(const uint64_t* rng, int B, int Lt, int S, float p, int64_t* ids, float* mask, float* style, int32_t* dropped,
+                        void* hip_stream);
 
 typedef struct {   /* HOST pointers, torch layouts */
   const float *conv1_w, *conv1_b;   /* [C/2, Cin, 3], [C/2] */

@@ -32,6 +32,10 @@ Deterministic sampling at N of the schedule's levels (DDIM, eta = 0: N denoiser 
 
     python infer.py "Follow the White Rabbit" style.npy --experiment-path data/best_exp --steps 20
 
+Classifier-free guidance (a checkpoint trained with `train.py --cond-drop`; works with or without --steps, --prompts-file, --page-file):
+
+    python infer.py "Follow the White Rabbit" style.npy --experiment-path data/best_exp --guidance 2.5
+
 A whole text as pages (word-wrapped, every line at the same scale, composed on the GPU into <output>_p<k>.png):
 
     python infer.py --page-file letter.txt style.npy --experiment-path data/best_exp --output letter"""
@@ -65,6 +69,8 @@ def main(argv=None):
                                                    "cross attention assigns to every character and write <output>_align.npz; writes no images")
     ap.add_argument("--steps", type=int, default=None, metavar="N", help="sample deterministically (DDIM, eta = 0) at N evenly spread levels of the "
                                                                          "schedule instead of the stochastic reverse process over all of them")
+    ap.add_argument("--guidance", type=float, default=None, metavar="W", help="classifier-free guidance scale (1 = unguided, larger = closer to the prompt "
+                                                                              "and the writer); needs a checkpoint trained with train.py --cond-drop")
     ap.add_argument("--page-file", metavar="TXT", help="a text to write as pages: wrapped to lines, every line sampled, all lines composed on the "
                                                        "GPU at one shared scale into <output>_p<k>.png (a blank line leaves a gap)")
     a = ap.parse_args(argv)
@@ -108,9 +114,16 @@ def main(argv=None):
         np.savez(f"{a.output}_align.npz", mean=np.asarray(al.mean), token=np.asarray(al.token), lengths=np.asarray(lens, np.int32))
         print(f"alignment of {len(lens)} lines -> ./{a.output}_align.npz")
 
+    if a.guidance is not None and not 0.0 <= a.guidance <= dhg_amd.inference.MAX_GUIDANCE:
+        ap.error(f"--guidance must lie in [0, {dhg_amd.inference.MAX_GUIDANCE:g}]")
+    if a.guidance is not None and (a.score or a.align or a.restyle or a.candidates > 1):
+        ap.error("--guidance belongs to plain sampling: it goes with neither --score, --align, --restyle nor --candidates")
+
     cand = dict(candidates=a.candidates) if a.candidates > 1 else {}   # (candidates = 1: today's calls, argument for argument)
     if a.steps is not None:
         cand["steps"] = a.steps
+    if a.guidance is not None:
+        cand["guidance"] = a.guidance
 
     def save(strokes_list):
         if a.save_strokes:

@@ -25,6 +25,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--eager", action="store_true", help="launch every kernel from the host instead of replaying the captured hipGraph")
+    ap.add_argument("--cond-drop", type=float, default=0.0, help="conditioning dropout probability (one more launch per update when > 0)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     sd = spec.synthetic_state_dict(2, 128, 192, 256, seed=0)
@@ -36,7 +37,7 @@ def main():
     batch = {"strokes": strokes3, "text": torch.from_numpy(inp["text"]), "style": torch.from_numpy(inp["style"])}
     beta = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "sched.npz"))
     alpha_set = torch.from_numpy(beta["alpha"])
-    graphed = tm.GraphedTrainStep(model, opt, a.batch, a.L, a.Lt)
+    graphed = tm.GraphedTrainStep(model, opt, a.batch, a.L, a.Lt, cond_drop=a.cond_drop)
     losses = []
     for step in range(1, a.warmup + a.steps + 1):
         if step == a.warmup + 1:
@@ -47,7 +48,7 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
     print(json.dumps({"metric": "training updates (forward + loss + backward + clip + Adam)", "ms_per_update": round(dt * 1e3, 2),
-                      "samples_per_s": round(a.batch / dt, 1), "batch": a.batch, "L": a.L, "Lt": a.Lt, "dtype": "f32", "launch": "eager" if a.eager else "hipGraph",
+                      "samples_per_s": round(a.batch / dt, 1), "batch": a.batch, "L": a.L, "Lt": a.Lt, "dtype": "f32", "launch": "eager" if a.eager else "hipGraph", "cond_drop": a.cond_drop,
                       "loss_first_last": [float(losses[0][0]), float(losses[-1][0])]}))
 
 

@@ -14,6 +14,8 @@ runs — the IAM corpus and its preprocessing are outside this package).  Writes
 both with the reference's 323 keys; cadence and numbering follow the reference ((count + 1) % freq, see fit()).
 `--resident` uploads the --data set once (with its optional "writer" key, int [N]) and draws and gathers every batch on the GPU inside
 the replayed graph; a sample's style then comes from a random other line of the same writer (dataset.py:110-115).
+`--cond-drop P` hides the prompt and the writer of a sample with probability P (conditioning dropout, drawn on the GPU inside the graph),
+which is what gives a checkpoint the unconditional branch that `infer.py --guidance` extrapolates from.
 --precision bf16 selects the mixed-precision GEMMs (fp32 master weights and optimizer state); batch_size is per rank."""
 import argparse
 
@@ -30,8 +32,13 @@ def main(argv=None):
     ap.add_argument("--init", help="state_dict to start from (.pth)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"], help="GEMM operand precision (fp32 = the reference's)")
+    ap.add_argument("--cond-drop", type=float, default=0.0, metavar="P",
+                    help="conditioning dropout: with probability P a sample trains without its prompt and writer (for infer.py --guidance; 0.1 is customary)")
     a = ap.parse_args(argv)
-    dhg_amd.train_model.fit(a.config, a.data, a.out, steps=a.steps, init=a.init, seed=a.seed, precision=a.precision, resident=a.resident)
+    if not 0.0 <= a.cond_drop <= 1.0:
+        ap.error("--cond-drop must lie in [0, 1]")
+    dhg_amd.train_model.fit(a.config, a.data, a.out, steps=a.steps, init=a.init, seed=a.seed, precision=a.precision, resident=a.resident,
+                            cond_drop=a.cond_drop)
 
 
 if __name__ == "__main__":
