@@ -192,7 +192,7 @@ struct dhw_handle {
   int* d_lens = nullptr;          // [max_B]
   int* h_lens_pin = nullptr;      // [max_B] pinned source of that copy
   hipEvent_t lens_ev = nullptr;   // recorded behind the last copy: the pinned buffer is rewritten only once that copy has read it
-  // guided calls (dhw_guided_ddim_sample / dhw_guided_sample, guide/dhw_guide_api.cpp): the per-sample scales, staged like the lengths.
+  // guided calls (dhw_guided_ddim_sample / dhw_guided_sample, step/dhw_step_api.cpp): the per-sample scales, staged like the lengths.
   // Allocated at the first guided call (the device array in the arena) and never moved.
   float* d_guide_scale = nullptr;       // [max_B]
   float* h_guide_scale_pin = nullptr;   // [max_B] pinned source of that copy

@@ -208,13 +208,7 @@ def _sample_guided(model, text, style_vector, L, T, diffusion_mode, noise, seed,
         raise ValueError("text must be an integer tensor [B, Lt]")
     B, Lt = text.shape
     lens = _check_ddim_common(text, style_vector, B, lengths, L)
-    if L is None:
-        L = max(lens) if lens is not None else stroke_length(Lt)
-    L = _check_int("L", L, 8)
-    if L % 8:
-        raise ValueError(f"L = {L} must be a multiple of 8")
-    T = _check_int("T", T, 1, 2 ** 29)
-    seed, first_sample = _check_int("seed", seed, 0, 2 ** 64 - 1), _check_int("first_sample", first_sample, -2 ** 63, 2 ** 63 - 1)
+    L, T, seed, first_sample = _check_eager_common(L, lens, Lt, seed, first_sample, lambda: _check_int("T", T, 1, 2 ** 29))
     if noise is not None:
         if not isinstance(noise, torch.Tensor) or not noise.dtype.is_floating_point:
             raise ValueError("noise must be a floating-point tensor [T+1,B,L,2]")
@@ -384,6 +378,18 @@ def _check_ddim_common(text, style_vector, B: int, lengths, L):
     return check_lengths(lengths, B, L) if lengths is not None else None
 
 
+def _check_eager_common(L, lens, Lt: int, seed, first_sample, levels_check):
+    """What ``sample_ddim`` and ``sample(guidance=...)`` check alike, in their order: L (default: the longest length, else
+    ``stroke_length(Lt)``; a multiple of 8), the call's own T / levels check, which stands between them, and the generator's
+    ranges.  Returns (L, what ``levels_check()`` returned, seed, first_sample)."""
+    if L is None:
+        L = max(lens) if lens is not None else stroke_length(Lt)
+    L = _check_int("L", L, 8)
+    if L % 8:
+        raise ValueError(f"L = {L} must be a multiple of 8")
+    return L, levels_check(), _check_int("seed", seed, 0, 2 ** 64 - 1), _check_int("first_sample", first_sample, -2 ** 63, 2 ** 63 - 1)
+
+
 def sample_ddim(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor, L: int | None = None, T: int = 60,
                 steps: int | None = None, levels=None, latent: torch.Tensor | None = None, seed: int = 0, first_sample: int = 0,
                 lengths=None, return_latent: bool = False, guidance=None, uncond_text: torch.Tensor | None = None,
@@ -411,28 +417,19 @@ def sample_ddim(model: DiffusionModel, text: torch.Tensor, style_vector: torch.T
             raise ValueError(f"latent must be [B,L,2] = {(B, L if L is not None else 'L', 2)}, got {tuple(latent.shape)}")
         L = int(latent.shape[1])
     lens = _check_ddim_common(text, style_vector, B, lengths, L)
-    if L is None:
-        L = max(lens) if lens is not None else stroke_length(Lt)
-    L = _check_int("L", L, 8)
-    if L % 8:
-        raise ValueError(f"L = {L} must be a multiple of 8")
-    lv = _check_ddim_levels(levels, steps, T)
-    seed, first_sample = _check_int("seed", seed, 0, 2 ** 64 - 1), _check_int("first_sample", first_sample, -2 ** 63, 2 ** 63 - 1)
-    if guidance is not None:
-        scale = _check_guidance(guidance, B)
-        text2, style2 = _guided_pair(text, style_vector, uncond_text, uncond_style)
-        with model._device_call("guide", text2, (text2, style2) if latent is None else (text2, style2, latent), 2 * B, L, style2.shape[1]) as c:
-            t, sv, lat = c.to(text2, torch.int64), c.to(style2), c.to(latent)
-            lat_out, out = c.empty((B, L, 2), wanted=return_latent), c.empty((B, L, 3))
-            c.run("dhw_guided_ddim_sample", t.data_ptr(), sv.data_ptr(), B, L, Lt, c.lens(lens), T, c.lens(lv), len(lv), _scale_array(scale), c.ptr(lat),
-                  seed, first_sample, out.data_ptr(), c.ptr(lat_out))
-        return (out.to(text.device), lat_out.to(text.device)) if return_latent else out.to(text.device)
-    tensors = (text, style_vector) if latent is None else (text, style_vector, latent)
-    with model._device_call("ddim", text, tensors, B, L, style_vector.shape[1]) as c:
-        t, sv, lat = c.to(text, torch.int64), c.to(style_vector), c.to(latent)
+    L, lv, seed, first_sample = _check_eager_common(L, lens, Lt, seed, first_sample, lambda: _check_ddim_levels(levels, steps, T))
+    # a guided call: the entry's name, the doubled condition (2B rows on the handle) and the scale array; text2 / style2 are the call's own otherwise
+    scale = _check_guidance(guidance, B) if guidance is not None else None
+    text2, style2 = _guided_pair(text, style_vector, uncond_text, uncond_style) if scale is not None else (text, style_vector)
+    tensors = (text2, style2) if latent is None else (text2, style2, latent)
+    with model._device_call("ddim" if scale is None else "guide", text2, tensors, B if scale is None else 2 * B, L, style2.shape[1]) as c:
+        t, sv, lat = c.to(text2, torch.int64), c.to(style2), c.to(latent)
         lat_out, out = c.empty((B, L, 2), wanted=return_latent), c.empty((B, L, 3))
-        c.run("dhw_ddim_sample", t.data_ptr(), sv.data_ptr(), B, L, Lt, c.lens(lens), T, c.lens(lv), len(lv), c.ptr(lat), seed, first_sample,
-              c.ptr(lat_out), out.data_ptr())
+        head = (t.data_ptr(), sv.data_ptr(), B, L, Lt, c.lens(lens), T, c.lens(lv), len(lv))
+        if scale is None:
+            c.run("dhw_ddim_sample", *head, c.ptr(lat), seed, first_sample, c.ptr(lat_out), out.data_ptr())
+        else:
+            c.run("dhw_guided_ddim_sample", *head, _scale_array(scale), c.ptr(lat), seed, first_sample, out.data_ptr(), c.ptr(lat_out))
     return (out.to(text.device), lat_out.to(text.device)) if return_latent else out.to(text.device)
 
 

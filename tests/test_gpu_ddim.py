@@ -146,6 +146,23 @@ def test_update_kernel_matches_numpy_bit_for_bit():
     assert np.array_equal(_bits(out.cpu().numpy()), _bits(np_update(b2.numpy(), e2.numpy(), *sets[1])))
 
 
+@pytest.mark.parametrize("lens", [None, [104, 40, 104, 8, 96]])
+def test_update_writes_its_own_rows_and_nothing_behind_them(lens):
+    """The unguided instantiation of the shared step kernel has no second half: base and eps hold exactly B * L rows, and the
+    B * L rows that follow `out` in the same allocation (where a guided step writes its second copy) keep their pattern."""
+    Bq, Lq = 5, 104   # 520 rows: two full blocks and 8 rows
+    g = torch.Generator().manual_seed(34)
+    base, eps = torch.randn((Bq, Lq, 2), generator=g) * 3, torch.randn((Bq, Lq, 2), generator=g)
+    pattern = torch.arange(Bq * Lq * 2, dtype=torch.float32).reshape(Bq, Lq, 2) + 0.5
+    buf = torch.cat((torch.full((Bq, Lq, 2), float("nan")), pattern)).cuda()
+    c = (np.float32(3.0), np.float32(0.1), np.float32(1.0 / 3), np.float32(0.7))
+    _raw_update(base.cuda(), eps.cuda(), None if lens is None else torch.tensor(lens, dtype=torch.int32).cuda(), c, buf[:Bq])
+    want = np_update(base.numpy(), eps.numpy(), *c)
+    got = buf.cpu().numpy()
+    assert np.array_equal(_bits(got[:Bq]), _bits(want if lens is None else _masked(want, lens)))
+    assert np.array_equal(_bits(got[Bq:]), _bits(pattern.numpy()))
+
+
 # ---------------------------------------------------------------- 2. S = 1 is one forward and one update
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
 def test_one_step_is_forward_then_update(prec):

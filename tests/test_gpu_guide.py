@@ -200,6 +200,35 @@ def test_step_kernel_matches_numpy_bit_for_bit(kind):
     assert np.array_equal(_bits(out.cpu().numpy()), _bits(np.concatenate((want, want))))
 
 
+@pytest.mark.parametrize("lens", [None, [104, 40, 104, 8, 96]])
+def test_guided_and_plain_ddim_updates_compute_one_u(lens):
+    """dhw_guide_update(kind = 0) with both eps halves the same array equals dhw_ddim_update on that array bit for bit, at every
+    scale: the difference is exactly +0, the product a zero, and e + (a zero) = e for e != 0; at scale 0 the select returns the
+    equal half.  So the guided and the unguided instantiation of the step kernel compute the same U.  520 rows: two full
+    blocks and 8 rows; the lengths cut inside blocks."""
+    Bq, Lq = 5, 104
+    g = torch.Generator().manual_seed(35)
+    base, e = torch.randn((Bq, Lq, 2), generator=g) * 3, torch.randn((Bq, Lq, 2), generator=g)
+    assert bool((e != 0).all())
+    lens_dev = None if lens is None else torch.tensor(lens, dtype=torch.int32).cuda()
+    scale = torch.tensor([0.0, 1.0, SCALE, 4.0, 0.25]).cuda()
+    abar, one = _lib.schedule(T)[1], np.float32(1)
+    for c in ((np.sqrt(abar[5]), np.sqrt(one - abar[5]), np.sqrt(abar[2]), np.sqrt(one - abar[2])),
+              (np.float32(3.0), np.float32(0.1), np.float32(1.0 / 3), np.float32(0.7))):
+        bd, ed, plain = base.cuda(), e.cuda(), torch.full((Bq, Lq, 2), float("nan")).cuda()
+        rc = _lib.lib().dhw_ddim_update(bd.data_ptr(), ed.data_ptr(), None if lens is None else lens_dev.data_ptr(), Bq, Lq, float(c[0]), float(c[1]), float(c[2]),
+                                        float(c[3]), plain.data_ptr(), _st())
+        assert rc == 0, _lib.lib().dhw_last_error(None).decode()
+        out = torch.full((2 * Bq, Lq, 2), float("nan")).cuda()
+        _raw(0, bd, torch.cat((ed, ed)), None, lens_dev, scale, None, c, out, None)
+        got, want = out.cpu().numpy(), plain.cpu().numpy()
+        assert np.isfinite(want).all()
+        assert np.array_equal(_bits(got[:Bq]), _bits(want)), c
+        assert np.array_equal(_bits(got[Bq:]), _bits(got[:Bq])), c
+        for b, n in enumerate(lens or []):
+            assert not _bits(got[b, n:]).any() and not _bits(got[Bq + b, n:]).any(), (c, b)
+
+
 # ---------------------------------------------------------------- 2. / 3. scale 1 and scale 0 are the plain calls
 @pytest.mark.parametrize("prec", ["bf16", "fp32"])
 def test_scale_one_and_zero_are_the_plain_calls(prec):
