@@ -409,7 +409,10 @@ int dhw_op_film_bwd(const float* dy, const float* x, const float* gamma, long lo
 int dhw_op_film_act(const float* x, const float* gamma, const float* beta, long long pstride, int B, int L, int C, int act, const float* addend, float* y,
                     void* st) {
   TRAIN_GUARD("dhw_op_film_act", int, {
-    OPCHECK(x && gamma && beta && y && B > 0 && L > 0 && C > 0 && C % 4 == 0 && pstride % 4 == 0, "dhw_op_film_act");
+    // (the forward has the 16-byte kernel only: whole f32x4 per lane and aligned bases, addend included where it is given)
+    OPCHECK(x && gamma && beta && y && B > 0 && L > 0 && C > 0 && C % 4 == 0 && pstride % 4 == 0 &&
+                ((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)addend | (uintptr_t)y) % 16 == 0,
+            "dhw_op_film_act");
     THIP(launch_film_act_fwd(x, gamma, beta, pstride, B, L, C, act, addend, y, (hipStream_t)st));
     return 0;
   });

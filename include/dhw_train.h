@@ -181,7 +181,10 @@ int dhw_op_film_bwd(const float* dy, const float* x, const float* gamma, long lo
  *   film_act : y = act ? SiLU(x gamma[b] + beta[b]) : x gamma[b] + beta[b]     (conditioning.py:23-26 [+ the SiLU that follows in cnn.py:70-80])
  *   ln_film  : y = LayerNorm(x) gamma[b] + beta[b]                             (model.py:25 + conditioning.py:23-26, as every EncoderLayer chains them)
  * Both take an optional addend (same shape as y): y += addend, the residual add that follows them in ConvBlock / EncoderLayer; its gradient is dy.
- * gamma / beta: per-sample rows [B][pstride]; the backward ADDS into dgamma / dbeta (same layout) and writes or adds dx. */
+ * gamma / beta: per-sample rows [B][pstride]; the backward ADDS into dgamma / dbeta (same layout) and writes or adds dx.
+ * Preconditions (DHW_ERR_ARG otherwise, nothing launched): dhw_op_film_act — the forward — needs C % 4 == 0, pstride % 4 == 0 and x, gamma,
+ * beta, addend (where given) and y 16-byte aligned: it has a 16-byte form only (its backward takes any C and alignment).
+ * dhw_op_ln_film_bwd needs C <= 512 (a lane keeps its channels' partial sums in registers); the forward takes any C. */
 int dhw_op_film_act(const float* x, const float* gamma, const float* beta, long long pstride, int B, int L, int C, int act, const float* addend /* or NULL */,
                     float* y, void* hip_stream);
 int dhw_op_film_act_bwd(const float* dy, const float* x, const float* gamma, const float* beta, long long pstride, int B, int L, int C, int act, float* dx,
@@ -193,7 +196,8 @@ int dhw_op_ln_film_bwd(const float* dy, const float* x, const float* mean, const
                        float* dx, int accumulate, float* dgamma, float* dbeta, void* hip_stream);
 int dhw_op_layernorm(const float* x, long long rows, int C, float* y, float* mean, float* rstd, void* hip_stream);
 int dhw_op_layernorm_bwd(const float* dy, const float* y, const float* rstd, long long rows, int C, float* dx, int accumulate, void* hip_stream);
-/* attention.py:16-22: P = softmax(S * scale + mask * -1e9) over `cols` keys; rows = B*H*Lq, mask [B][cols] or NULL */
+/* attention.py:16-22: P = softmax(S * scale + mask * -1e9) over `cols` keys; rows = B*H*Lq, mask [B][cols] or NULL.
+ * The backward dS = scale * P * (dP - sum_key dP P) may run in place (ds == dp): a row's dP is read before its dS is written. */
 int dhw_op_softmax(const float* s, long long rows, int cols, long long rows_per_sample, const float* mask, float scale, float* p, void* hip_stream);
 int dhw_op_softmax_bwd(const float* dp, const float* p, long long rows, int cols, float scale, float* ds, void* hip_stream);
 /* mode 0: AvgPool1d(2) forward (rows_out = rows_in / 2), 1: its backward (rows_out = 2 rows_in), 2: nearest x2 Upsample
@@ -208,7 +212,10 @@ int dhw_op_mask_mul(const float* x, const float* mask, float scale, long long n,
  * sigma[b][k] flat[woff[j] + k] for the `total` output channels j of all the Linears; woff / boff (device int64[total]) give
  * each channel's weight row and bias inside the flat parameter buffer, so the parameters stay in state_dict order.  Backward:
  * grad_flat[woff[j] + k] += sum_b dfilm[b][j] sigma[b][k], grad_flat[boff[j]] += sum_b dfilm[b][j], dsigma[b][k] += sum_j
- * dfilm[b][j] flat[woff[j] + k].  sigma / dsigma [B,32], film / dfilm [B,total]. */
+ * dfilm[b][j] flat[woff[j] + k].  sigma / dsigma [B,32], film / dfilm [B,total].
+ * The 32-float weight rows are read 16 bytes at a time: flat must be 16-byte aligned and every woff[j] a multiple of 4 (they are
+ * device arrays, so the entry cannot check them; train_model/net.py refuses a parameter layout that breaks this).  Distinct
+ * columns name distinct weight rows and biases: the weight gradient adds into them without atomics. */
 int dhw_op_film_table(const float* sigma, const float* flat, const int64_t* woff, const int64_t* boff, int B, int total, float* film, void* hip_stream);
 int dhw_op_film_table_bwd(const float* dfilm, const float* sigma, const float* flat, const int64_t* woff, const int64_t* boff, int B, int total,
                           float* grad_flat, float* dsigma, void* hip_stream);
