@@ -311,6 +311,8 @@ hipError_t launch_film_table(int dir, const float* sigma, const float* flat, con
 hipError_t launch_keep_mask(const uint64_t* rng, int site, long n, int per_sample, float p, float* keep, hipStream_t st);
 hipError_t launch_train_draw(const uint64_t* rng, int B, int L, float* eps, long n_keep, int keep_per_sample, float p, float* keep, hipStream_t st);
 hipError_t launch_adam_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, const float* sqnorm, hipStream_t st);
+hipError_t launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, const float* hyper, const float* ema_hyper,
+                           const float* sqnorm, hipStream_t st);
 hipError_t launch_unary(int kind, const float* x, long n, float* y, hipStream_t st);
 hipError_t launch_unary_bwd(int kind, const float* dy, const float* x, long n, float* dx, int accumulate, hipStream_t st);
 hipError_t launch_add2(const float* a, const float* b, long n, float* out, int accumulate, hipStream_t st);

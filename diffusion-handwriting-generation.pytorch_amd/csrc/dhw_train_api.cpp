@@ -222,6 +222,23 @@ int dhw_train_adam_dev(int nbuf, float* const* p, const float* const* g, float* 
   });
 }
 
+int dhw_train_adam_ema_dev(int nbuf, float* const* p, const float* const* g, float* const* m, float* const* v, float* const* ema,
+                           const int64_t* n, const float* hyper, const float* ema_hyper, float* sqnorm, void* hip_stream) {
+  TRAIN_GUARD("dhw_train_adam_ema_dev", int, {
+    if (nbuf < 1) return tfail(DHW_ERR_ARG, "dhw_train_adam_ema_dev: nbuf = %d must be at least 1", nbuf);
+    if (!ema) return tfail(DHW_ERR_ARG, "dhw_train_adam_ema_dev: ema is NULL");
+    if (!ema_hyper) return tfail(DHW_ERR_ARG, "dhw_train_adam_ema_dev: ema_hyper is NULL");
+    if (!p || !g || !m || !v || !n || !hyper || !sqnorm) return tfail(DHW_ERR_ARG, "dhw_train_adam_ema_dev: bad argument");
+    for (int i = 0; i < nbuf; ++i)
+      if (!p[i] || !g[i] || !m[i] || !v[i] || !ema[i] || n[i] < 0) return tfail(DHW_ERR_ARG, "dhw_train_adam_ema_dev: buffer %d has a NULL pointer or a negative size", i);
+    hipStream_t st = (hipStream_t)hip_stream;
+    THIP(hipMemsetAsync(sqnorm, 0, sizeof(float), st));
+    for (int i = 0; i < nbuf; ++i) THIP(launch_sqnorm(g[i], n[i], sqnorm, st));
+    for (int i = 0; i < nbuf; ++i) THIP(launch_adam_ema(p[i], g[i], m[i], v[i], ema[i], n[i], hyper, ema_hyper, sqnorm, st));
+    return 0;
+  });
+}
+
 int dhw_train_draw(const uint64_t* rng, int B, int L, float* eps, long long n_keep, int keep_per_sample, float p, float* keep, void* hip_stream) {
   TRAIN_GUARD("dhw_train_draw", int, {
     if (!rng || !eps || !keep || B < 1 || L < 1 || n_keep < 1 || keep_per_sample < 4 || keep_per_sample % 4 || n_keep % keep_per_sample || p < 0.f || p >= 1.f)

@@ -115,18 +115,88 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
 // The same update with its scalars read from device memory — hyper = {lr, beta1, beta2, eps, weight_decay, 1 - beta1^t,
 // 1 - beta2^t, max_norm} — so that a captured hipGraph of the whole training step can be replayed with the step's own
 // learning rate and bias corrections (the host rewrites the 8 floats before each replay).
+// The scalars of one update as the kernels below read them, and the update of ONE element: the single statement of the arithmetic
+// that adam_dev_kernel and adam_ema_kernel share, so that both contract the same expression into the same instructions.
+struct AdamScalars { float lr, b1, b2, eps, wd, bc1, bc2, clip; };
+__device__ __forceinline__ AdamScalars adam_scalars(const float* hyper, const float* sqnorm) {
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2 = hyper[6], max_norm = hyper[7], gs = hyper[8];
+  float clip = gs;   // (gs = 1 / world size behind a SUM all-reduce: the averaging costs no pass of its own; 1 otherwise)
+  if (max_norm > 0.f) clip = gs * fminf(1.0f, max_norm / __builtin_fmaf(sqrtf(*sqnorm), gs, 1e-6f));   // (the FMA it has always been)
+  return {lr, b1, b2, eps, wd, bc1, bc2, clip};
+}
+// Which products fuse into an FMA is written out rather than left to contraction: the compiler fused differently in the one-float and
+// the four-float loop (m' came out as fma(b1, m, .) in the latter only).  What stands here is what adam_dev_kernel has always
+// compiled to — the gradient term one FMA on the rounded wd * p, both moments as rounded products added — so its bits are unchanged.
+__device__ __forceinline__ void adam_element(const AdamScalars& h, float g, float& p, float& m, float& v) {
+#pragma clang fp contract(off)
+  const float gi = __builtin_fmaf(g, h.clip, h.wd * p);
+  const float mi = h.b1 * m + (1.0f - h.b1) * gi;
+  const float vi = h.b2 * v + (1.0f - h.b2) * gi * gi;
+  m = mi;
+  v = vi;
+  p -= h.lr / h.bc1 * mi / (sqrtf(vi) / sqrtf(h.bc2) + h.eps);
+}
+
 __global__ __launch_bounds__(256) void adam_dev_kernel(float* p, const float* g, float* m, float* v, long n, const float* hyper, const float* sqnorm) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2 = hyper[6], max_norm = hyper[7], gs = hyper[8];
-  float clip = gs;   // (gs = 1 / world size behind a SUM all-reduce: the averaging costs no pass of its own; 1 otherwise)
-  if (max_norm > 0.f) clip = gs * fminf(1.0f, max_norm / (sqrtf(*sqnorm) * gs + 1e-6f));
-  const float gi = g[i] * clip + wd * p[i];
-  const float mi = b1 * m[i] + (1.0f - b1) * gi;
-  const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+  const AdamScalars h = adam_scalars(hyper, sqnorm);
+  float pi = p[i], mi = m[i], vi = v[i];
+  adam_element(h, g[i], pi, mi, vi);
   m[i] = mi;
   v[i] = vi;
-  p[i] -= lr / bc1 * mi / (sqrtf(vi) / sqrtf(bc2) + eps);
+  p[i] = pi;
+}
+
+// adam_dev_kernel's update and, in the same pass, the exponential moving average of the weights just written:
+// ema' = fma(decay, ema, (1 - decay) p'), ema_hyper = {decay, 1 - decay} in DEVICE memory (both rounded by the host).  A streaming pass
+// over nine streams (p, g, m, v, ema read; p, m, v, ema written): 16 bytes per lane and stream, at most ADAM_EMA_GRID workgroups
+// striding over the buffer, the last n % 4 elements one per lane; `vec` = all five pointers are 16-byte aligned (the launcher
+// tests them), else one float per lane in the same grid-stride loop.
+constexpr unsigned ADAM_EMA_GRID = 2048;
+__device__ __forceinline__ float ema_element(float decay, float omd, float e, float p_new) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(decay, e, omd * p_new);
+}
+
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* p, const float* g, float* m, float* v, float* ema, long n, const float* hyper,
+                                                        const float* ema_hyper, const float* sqnorm, int vec) {
+  const AdamScalars h = adam_scalars(hyper, sqnorm);
+  const float decay = ema_hyper[0], omd = ema_hyper[1];
+  const long stride = (long)gridDim.x * 256, t = (long)blockIdx.x * 256 + threadIdx.x;
+  long tail = 0;      // first element of the one-float-per-lane part
+  if (vec) {
+    const long n4 = n / 4;
+    f32x4* p4 = reinterpret_cast<f32x4*>(p);
+    f32x4* m4 = reinterpret_cast<f32x4*>(m);
+    f32x4* v4 = reinterpret_cast<f32x4*>(v);
+    f32x4* e4 = reinterpret_cast<f32x4*>(ema);
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    for (long i = t; i < n4; i += stride) {
+      f32x4 pv = p4[i], mv = m4[i], vv = v4[i], ev = e4[i];
+      const f32x4 gv = g4[i];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float pk = pv[k], mk = mv[k], vk = vv[k];
+        adam_element(h, gv[k], pk, mk, vk);
+        pv[k] = pk; mv[k] = mk; vv[k] = vk;
+        ev[k] = ema_element(decay, omd, ev[k], pk);
+      }
+      m4[i] = mv;
+      v4[i] = vv;
+      p4[i] = pv;
+      e4[i] = ev;
+    }
+    tail = n4 * 4;
+  }
+  for (long i = tail + t; i < n; i += stride) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_element(h, g[i], pi, mi, vi);
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = pi;
+    ema[i] = ema_element(decay, omd, ema[i], pi);
+  }
 }
 
 // The step's random draws on the device (train.py:39 eps = randn_like(x); text_style.py:97 Dropout(0.3) on the style
@@ -234,6 +304,16 @@ hipError_t launch_keep_mask(const uint64_t* rng, int site, long n, int per_sampl
 }
 hipError_t launch_adam_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, const float* sqnorm, hipStream_t st) {
   hipLaunchKernelGGL(adam_dev_kernel, dim3(nb(n)), dim3(256), 0, st, p, g, m, v, n, hyper, sqnorm);
+  return hipGetLastError();
+}
+hipError_t launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, const float* hyper, const float* ema_hyper,
+                           const float* sqnorm, hipStream_t st) {
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+                         reinterpret_cast<uintptr_t>(ema);
+  const int vec = (bits & 15) == 0;
+  // one lane per f32x4 (or per float in the scalar form); at least the n % 4 tail's one workgroup
+  const unsigned grid = std::min<unsigned>(std::max(nb(vec ? n / 4 : n), 1u), ADAM_EMA_GRID);
+  hipLaunchKernelGGL(adam_ema_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, ema, n, hyper, ema_hyper, sqnorm, vec);
   return hipGetLastError();
 }
 hipError_t launch_colsum(const float* dy, long rows, int C, float* db, hipStream_t st) {   // db zeroed by the caller

@@ -9,6 +9,7 @@ are in the ``train_model`` package.
 from __future__ import annotations
 
 import ctypes as C
+import struct
 
 import torch
 
@@ -66,18 +67,41 @@ def loss_fn(eps, score_pred, pen_lifts, pen_lifts_pred, alphas, with_grad: bool 
     return (out, ds, dp) if with_grad else out
 
 
+def check_ema_decay(ema_decay):
+    """The one rule for an EMA decay (``Adam``, ``fit``, ``load_train_state``): None (no EMA) or a real number in (0, 1)."""
+    if ema_decay is None:
+        return None
+    if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 < float(ema_decay) < 1.0:   # (NaN fails both comparisons)
+        raise ValueError(f"ema_decay = {ema_decay!r} must be None or a number in (0, 1)")
+    return float(ema_decay)
+
+
+def ema_decay_at(t: int, decay: float) -> float:
+    """The decay of update number ``t`` >= 1 (the update counter after its increment): min(decay, (1 + t) / (10 + t)) — the customary
+    warm-up, so that the average forgets the initial weights at the rate the run has updates to average over."""
+    return min(decay, (1 + t) / (10 + t))
+
+
 class Adam:
     """torch.optim.Adam(lr, betas, eps, weight_decay) + clip_grad_norm_(max_norm) over a list of flat fp32 device
-    buffers (configs/best.yml:33-38, clip_grad 100, utils/clip_grad.py:42-43), one fused kernel per buffer."""
+    buffers (configs/best.yml:33-38, clip_grad 100, utils/clip_grad.py:42-43), one fused kernel per buffer.
 
-    def __init__(self, params, betas=(0.9, 0.98), eps: float = 1e-8, weight_decay: float = 1e-5, max_norm: float = 100.0):
+    ``ema_decay`` in (0, 1): also keep ``self.ema``, the exponential moving average of the parameters (clones of them at
+    construction), updated in the optimizer's own pass (dhw_train_adam_ema_dev) with the decay ``ema_decay_at(step_count, ema_decay)``;
+    that is the device-scalar path (``hyper`` / ``ema_hyper`` / ``step_dev``, which ``GraphedTrainStep`` drives) — ``step`` refuses."""
+
+    def __init__(self, params, betas=(0.9, 0.98), eps: float = 1e-8, weight_decay: float = 1e-5, max_norm: float = 100.0, ema_decay=None):
+        self.ema_decay = check_ema_decay(ema_decay)
         self.params = list(params)
         self.betas, self.eps, self.weight_decay, self.max_norm = betas, eps, weight_decay, max_norm
         self.m = [torch.zeros_like(p) for p in self.params]
         self.v = [torch.zeros_like(p) for p in self.params]
+        self.ema = [p.clone() for p in self.params] if self.ema_decay is not None else None
         self.step_count = 0
 
     def step(self, grads, lr: float):
+        if self.ema is not None:
+            raise ValueError("an optimizer with ema_decay updates through step_dev (device scalars: hyper / ema_hyper), not step")
         self.step_count += 1
         n = len(self.params)
         dev = self.params[0].device
@@ -96,13 +120,29 @@ class Adam:
         b1, b2 = self.betas
         return [lr, b1, b2, self.eps, self.weight_decay, 1.0 - b1 ** self.step_count, 1.0 - b2 ** self.step_count, self.max_norm, grad_scale]
 
-    def step_dev(self, grads, hyper_dev: torch.Tensor, sqnorm_dev: torch.Tensor):
+    def ema_hyper(self) -> list:
+        """The 2 scalars ``dhw_train_adam_ema_dev`` reads from device memory for the update ``hyper`` has just counted: {d, 1 - d}
+        with d = ema_decay_at(step_count, ema_decay); d and 1 - d are formed in double and rounded to fp32 each on its own."""
+        if self.ema is None:
+            raise ValueError("this optimizer keeps no EMA (ema_decay=None)")
+        d = ema_decay_at(self.step_count, self.ema_decay)
+        f32 = lambda x: struct.unpack("f", struct.pack("f", x))[0]   # noqa: E731
+        return [f32(d), f32(1.0 - d)]
+
+    def step_dev(self, grads, hyper_dev: torch.Tensor, sqnorm_dev: torch.Tensor, ema_hyper_dev: torch.Tensor | None = None):
         """The update with every scalar on the device (``hyper_dev`` = the 9 floats of ``hyper``): no allocation and no
-        host synchronisation, so it can sit inside a captured hipGraph.  ``sqnorm_dev`` receives ||g||^2."""
+        host synchronisation, so it can sit inside a captured hipGraph.  ``sqnorm_dev`` receives ||g||^2.  With EMA on,
+        ``ema_hyper_dev`` = the 2 floats of ``ema_hyper`` is required and the fused entry updates ``self.ema`` in the same pass."""
+        if (self.ema is None) != (ema_hyper_dev is None):
+            raise ValueError("ema_hyper_dev goes with an optimizer built with ema_decay, and only with one")
         n = len(self.params)
         dev = self.params[0].device
         arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
         sizes = (C.c_int64 * n)(*[p.numel() for p in self.params])
+        if self.ema is not None:
+            _tcheck(_lib.lib().dhw_train_adam_ema_dev(n, arr(self.params), arr(grads), arr(self.m), arr(self.v), arr(self.ema), sizes, hyper_dev.data_ptr(),
+                                                      ema_hyper_dev.data_ptr(), sqnorm_dev.data_ptr(), _stream(dev)))
+            return
         _tcheck(_lib.lib().dhw_train_adam_dev(n, arr(self.params), arr(grads), arr(self.m), arr(self.v), sizes, hyper_dev.data_ptr(),
                                               sqnorm_dev.data_ptr(), _stream(dev)))
 

@@ -12,11 +12,14 @@ Parameters keep the reference's ``state_dict`` names and torch layouts, so a ref
 trained one can be handed straight to ``dhg_amd.DiffusionModel`` for sampling.
 
 One module per concern, each importing only the ones before it: ``tape`` (Var, Tape; DHW_TRAIN_FUSE_DSILU), ``net`` (TrainModel;
-DHW_TRAIN_FILM_RIDER), ``data`` (ResidentData), ``step`` (train_step, GraphedTrainStep; DHW_TRAIN_BUCKETS), ``loop`` (fit).  Each
+DHW_TRAIN_FILM_RIDER), ``data`` (ResidentData), ``step`` (train_step, GraphedTrainStep; DHW_TRAIN_BUCKETS), ``state`` (save_train_state,
+load_train_state), ``evaluate`` (EvalStep), ``loop`` (fit).  Each
 environment switch is read once, at import, by the module named with it.
 """
 from .tape import FUSE_DSILU, Tape, Var, _ViewVar  # noqa: F401
 from .net import FILM_RIDER, N_BUCKETS, TrainModel, grad_bucket, positional_encoding  # noqa: F401
 from .data import ResidentData, group_tables  # noqa: F401
 from .step import GRAD_BUCKETS, GraphedTrainStep, train_step  # noqa: F401
+from .state import load_train_state, read_train_state, save_train_state  # noqa: F401
+from .evaluate import EvalStep  # noqa: F401
 from .loop import fit, read_train_config  # noqa: F401

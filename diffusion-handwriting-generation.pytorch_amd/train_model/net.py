@@ -95,15 +95,16 @@ class TrainModel:
             n_b = sum(host[k].numel() for k in self.layout if grad_bucket(k) == b)
             start = self.bucket_ranges[-1][1] if self.bucket_ranges else 0
             self.bucket_ranges.append((start, start + n_b))
+        self._shapes, self._conv_w = shapes, conv_w
+        self.sizes = {k: host[k].numel() for k in self.layout}     # elements per tensor; with self.layout, the whole layout of a flat buffer
         for k in self.layout:
-            n = host[k].numel()
+            n = self.sizes[k]
             if off % 4 and n % 4 == 0:
                 raise ValueError(f"parameter {k} would start unaligned in the flat buffer (an odd-sized tensor precedes it)")
-            view = (lambda buf: buf[off:off + n].view(3, *shapes[k][:2]).permute(1, 2, 0)) if k in conv_w else (lambda buf: buf[off:off + n].view(shapes[k]))
-            v = Var(view(self.flat))
-            v.g = view(self.flat_grad)
-            self.p[k] = v
             self.offset[k] = off
+            v = Var(self._view(self.flat, k))
+            v.g = self._view(self.flat_grad, k)
+            self.p[k] = v
             off += n
         # every AffineTransformLayer's gamma / beta Linear as columns of one [B, TOT] table (dhw_op_film_table): column ->
         # (weight row, bias) offsets inside the flat buffer; film_cols[name] = (first gamma column, first beta column)
@@ -140,8 +141,27 @@ class TrainModel:
     def zero_grad(self):
         self.flat_grad.zero_()   # one memset
 
+    def _view(self, buf, k):
+        """Tensor ``k`` inside a flat buffer laid out like ``self.flat``, in the reference's shape (a Conv1d weight: the permuted view
+        of its [tap][Cout][Cin] storage) — the one statement of the layout rule."""
+        piece = buf[self.offset[k]:self.offset[k] + self.sizes[k]]
+        return piece.view(3, *self._shapes[k][:2]).permute(1, 2, 0) if k in self._conv_w else piece.view(self._shapes[k])
+
+    def named_views(self, buf) -> dict:
+        """The named, reference-ordered views of any flat buffer laid out like ``self.flat`` (the gradients, Adam's moments, an EMA
+        of the weights): what ``state_dict`` gives for the parameters themselves."""
+        if buf.dim() != 1 or buf.numel() != self.flat.numel():
+            raise ValueError(f"a flat buffer of this model holds {self.flat.numel()} elements, got shape {tuple(buf.shape)}")
+        return {k: self._view(buf, k) for k in self.names}
+
     def state_dict(self):
-        return {k: self.p[k].d for k in self.names}
+        return self.named_views(self.flat)
+
+    def ema_state_dict(self, opt):
+        """The state_dict of the averaged weights ``opt`` keeps for this model (``Adam(model.parameters(), ema_decay=...)``)."""
+        if getattr(opt, "ema", None) is None:
+            raise ValueError("this optimizer keeps no EMA (ema_decay=None)")
+        return self.named_views(opt.ema[0])
 
     def pe(self, L, dim, factor):
         key = (L, dim, factor)

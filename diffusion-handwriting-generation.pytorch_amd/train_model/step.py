@@ -63,7 +63,9 @@ class GraphedTrainStep:
     an update (draws, perturbation, forward, loss, backward) become one graph launch, which takes the host off the critical
     path; the gradient all-reduce (multi-rank) and clip + Adam follow as three eager launches.  The batch
     lives in static device buffers that each call overwrites; the step's learning rate and Adam bias corrections are 8 floats
-    in device memory rewritten before every replay.  One instance serves one batch shape (B, L, Lt, S).
+    in device memory rewritten before every replay.  One instance serves one batch shape (B, L, Lt, S).  With an optimizer
+    that keeps an EMA (``Adam(ema_decay=...)``) the block carries its two scalars as well and the fused pass updates the average
+    wherever the optimizer runs: as the graph's last node, eagerly, or behind the collectives (every rank computes the same EMA).
 
     With ``data`` (a ``ResidentData``) the batch never crosses the bus: the step's first two launches draw B sample indices, the
     noise levels and the style sources (dhw_train_batch_draw) and gather the rows into the static buffers (dhw_train_batch_gather),
@@ -120,6 +122,8 @@ class GraphedTrainStep:
             self.abar = torch.as_tensor(alpha_set, dtype=torch.float32).contiguous().to(dev)
         if not device_rng:
             fields += [("eps", (B, L, 2), torch.float32), ("keep", (B, S, 1280), torch.float32)]
+        if getattr(optimizer, "ema", None) is not None:   # (appended, and only then: the block of a step without EMA is laid out as it always was)
+            fields += [("ema", (2,), torch.float32)]
         offs, off = {}, 0
         for name, shape, dt in fields:
             n = int(np.prod(shape)) * (8 if dt == torch.int64 else 4)
@@ -133,6 +137,7 @@ class GraphedTrainStep:
         self._dv, self._hv = carve(self._stage_dev), [carve(h) for h in self._stage_host]
         d = self._dv if data is None else {**self._dv, **resident}
         self.x, self.pen, self.alphas, self.sigma, self.ids, self.mask, self.style, self.hyper = (d[k] for k in ("x", "pen", "alphas", "sigma", "ids", "mask", "style", "hyper"))
+        self.ema_hyper = d.get("ema")           # the optimizer's {decay, 1 - decay} in the block, or None
         self.eps = d["eps"] if not device_rng else z(B, L, 2)
         self.keep = d["keep"] if not device_rng else z(B, S, 1280)
         d["rng"].copy_(model.rng)
@@ -184,7 +189,7 @@ class GraphedTrainStep:
             reducer.wait()
         elif dist_state()[0]:
             allreduce_grads(m.grads(), average=False)
-        self.opt.step_dev(m.grads(), self.hyper, self.sqnorm)
+        self.opt.step_dev(m.grads(), self.hyper, self.sqnorm, self.ema_hyper)
 
     def _capture_segments(self):
         """With a process group the update is captured as N_BUCKETS graph SEGMENTS cut at the tape's bucket markers (one shared
@@ -287,6 +292,8 @@ class GraphedTrainStep:
             hv["mask"].copy_(batch["text"] == 0)
             hv["style"].copy_(batch["style"])
         hv["hyper"].copy_(torch.tensor(self.opt.hyper(noam_lr(step, *self.sched), 1.0 / world), dtype=torch.float32))
+        if self.ema_hyper is not None:      # (behind hyper(): the decay of the update it has just counted)
+            hv["ema"].copy_(torch.tensor(self.opt.ema_hyper(), dtype=torch.float32))
         self._gscale = 1.0 / world
         self._stage_dev.copy_(self._stage_host[turn], non_blocking=True)
         ev = self._stage_ev[turn] = self._stage_ev[turn] or torch.cuda.Event()
@@ -323,7 +330,7 @@ class GraphedTrainStep:
                 with torch.cuda.graph(self.graph):
                     self._body()
                     if self._opt_in_graph:
-                        self.opt.step_dev(self.model.grads(), self.hyper, self.sqnorm)
+                        self.opt.step_dev(self.model.grads(), self.hyper, self.sqnorm, self.ema_hyper)
             elif self._opt_in_graph and dist_on:
                 raise RuntimeError("this step was captured without a process group; build a new GraphedTrainStep after init_process_group")
             self.graph.replay()

@@ -6,6 +6,8 @@
  *   dhw_train_perturb    <- x_perturbed = sqrt(abar) x + sqrt(1 - abar) eps                      (train.py:41-43)
  *   dhw_train_loss       <- loss_fn (loss.py:5-37) and d loss / d(score_pred, pen_lifts_pred)     (loss.backward())
  *   dhw_train_adam       <- clip_grad_norm_(max_norm) (utils/clip_grad.py:42-43) + torch.optim.Adam (configs/best.yml:33-38)
+ *   dhw_train_adam_ema_dev <- the same update with the exponential moving average of the weights kept in the same pass (no reference
+ *                           counterpart)
  *   dhw_train_convblock  <- ConvBlock.forward + its autograd backward (cnn.py:64-87): the first block of the denoiser's
  *                           backward pass as ONE entry point, issued on the generic operations below (weights uploaded per call,
  *                           in torch layout).
@@ -51,6 +53,19 @@ int dhw_train_adam(int nbuf, float* const* p, const float* const* g, float* cons
  * allocation, no synchronisation. */
 int dhw_train_adam_dev(int nbuf, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
                        const float* hyper, float* sqnorm, void* hip_stream);
+
+/* dhw_train_adam_dev with the exponential moving average (EMA) of the weights kept in the same pass — the weights a diffusion model is
+ * sampled from.  Same contract: capturable, no allocation, no synchronisation, sqnorm zeroed and filled with the squared norm of the
+ * gradient buffers, and p, m, v receive the BITS dhw_train_adam_dev gives them (one shared statement of the element update).  In
+ * addition every element of ema[i] (device, n[i] floats, laid out as p[i]) becomes
+ *   ema' = fmaf(decay, ema, omd * p')            p' = the parameter value just written, omd * p' rounded to fp32 first
+ * with ema_hyper = DEVICE float[2] = {decay, omd = 1 - decay}: the host rounds each of the two to fp32 on its own, so {0, 1} copies p'
+ * and {1, 0} leaves ema as it is, exactly.  The pass takes 16-byte loads and stores when p[i], g[i], m[i], v[i] and ema[i] are all
+ * 16-byte aligned and one float per lane otherwise; any n[i] >= 0.  ema or ema_hyper NULL, or nbuf < 1: DHW_ERR_ARG, before any HIP
+ * call (dhw_train_last_error names which). */
+int dhw_train_adam_ema_dev(int nbuf, float* const* p, const float* const* g, float* const* m, float* const* v, float* const* ema, const int64_t* n,
+                           const float* hyper /* [9], as dhw_train_adam_dev */, const float* ema_hyper /* DEVICE [2] = {decay, 1 - decay} */,
+                           float* sqnorm, void* hip_stream);
 
 /* The random draws of one update on the device, from the sampler's counter-based Philox generator (dhw.h: the same draw for
  * any batch sharding): eps ~ N(0,1) [B,L,2] (train.py:39) and the Dropout(p) keep-mask (1 = kept) over n_keep elements,

@@ -16,6 +16,9 @@ both with the reference's 323 keys; cadence and numbering follow the reference (
 the replayed graph; a sample's style then comes from a random other line of the same writer (dataset.py:110-115).
 `--cond-drop P` hides the prompt and the writer of a sample with probability P (conditioning dropout, drawn on the GPU inside the graph),
 which is what gives a checkpoint the unconditional branch that `infer.py --guidance` extrapolates from.
+`--ema D` keeps the exponential moving average of the weights inside the optimizer's pass and writes ema_<n>.pth / ema_final.pth;
+`--save-state` keeps train_state.pth (weights, Adam's moments and counter, the EMA) and `--resume PATH` continues from one;
+`--val batches.pt [--eval-freq N]` logs the held-out loss at fixed noise levels (and, with --ema, that of the averaged weights).
 --precision bf16 selects the mixed-precision GEMMs (fp32 master weights and optimizer state); batch_size is per rank."""
 import argparse
 
@@ -34,11 +37,22 @@ def main(argv=None):
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"], help="GEMM operand precision (fp32 = the reference's)")
     ap.add_argument("--cond-drop", type=float, default=0.0, metavar="P",
                     help="conditioning dropout: with probability P a sample trains without its prompt and writer (for infer.py --guidance; 0.1 is customary)")
+    ap.add_argument("--ema", type=float, metavar="D", help="keep an exponential moving average of the weights with decay D in (0, 1) (0.9999 is customary); "
+                    "writes ema_<n>.pth and ema_final.pth, the weights to sample from")
+    ap.add_argument("--save-state", action="store_true", help="keep train_state.pth in --out: weights, Adam's moments and counter, the EMA (for --resume)")
+    ap.add_argument("--resume", metavar="PATH", help="continue the run a train_state.pth was saved from (implies --save-state)")
+    ap.add_argument("--val", metavar="PATH", help="validation set (the form of --data): log its loss at fixed noise levels as `Eval <n> | ...` lines")
+    ap.add_argument("--eval-freq", type=int, metavar="N", help="evaluate --val every N updates (default: training_args.save_freq)")
     a = ap.parse_args(argv)
     if not 0.0 <= a.cond_drop <= 1.0:
         ap.error("--cond-drop must lie in [0, 1]")
+    if a.ema is not None and not 0.0 < a.ema < 1.0:
+        ap.error("--ema must lie in (0, 1)")
+    if a.eval_freq is not None and (a.eval_freq < 1 or not a.val):
+        ap.error("--eval-freq must be a positive number of updates and needs --val")
     dhg_amd.train_model.fit(a.config, a.data, a.out, steps=a.steps, init=a.init, seed=a.seed, precision=a.precision, resident=a.resident,
-                            cond_drop=a.cond_drop)
+                            cond_drop=a.cond_drop, ema=a.ema, save_state=a.save_state or a.resume is not None, resume=a.resume, val_path=a.val,
+                            eval_freq=a.eval_freq)
 
 
 if __name__ == "__main__":
