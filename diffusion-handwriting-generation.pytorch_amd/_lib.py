@@ -84,6 +84,8 @@ SIGNATURES = {
     "dhw_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, C.c_size_t, _P]),
     "dhw_prep_workspace_bytes": (C.c_size_t, [C.c_int]),
     "dhw_prep": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "dhw_moments_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dhw_moments_update": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "dhw_schedule": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "dhw_work": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dhw_last_error": (C.c_char_p, [_P]),

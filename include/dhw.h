@@ -526,6 +526,28 @@ int dhw_prep(const uint8_t* images,   /* device u8 [B,Hin,Win], image b in the t
              int32_t* status_out,     /* device [B] */
              void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Feature moments: the running sum and Gram matrix of pooled feature vectors in double precision, the statistics behind a
+ * Frechet distance between two sets of style features.  No handle: errors are read through
+ * dhw_last_error(NULL).  The call allocates nothing, synchronises nothing and can be captured into a graph.  All argument checks
+ * run before the first HIP call (DHW_ERR_ARG names the argument): 1 <= N <= 16384, 1 <= S <= 64, D a multiple of 16 in
+ * [16, 2048], N S D < 2^31, non-NULL and 16-byte aligned feat / sum / gram, ws_bytes >= dhw_moments_workspace_bytes(N, S, D)
+ * (8 N D bytes: the pooled matrix; 0 for dimensions the entry refuses), ws non-NULL and 16-byte aligned.
+ *    1. p[n][d] = (sum_s (double)feat[n][s][d]) / (double)S, s ascending from feat[n][0][d]: the mean over the S positions.
+ *       S = 1 takes vectors that are pooled already.  Rows of feat at or past N are never read.
+ *    2. sum[d] += sum_n p[n][d] and gram[i][j] += sum_n p[n][i] p[n][j], in double throughout; the Gram update runs on
+ *       v_mfma_f64_16x16x4_f64 with n ascending, from the tile's current value.  The caller zeroes sum and gram once and keeps
+ *       the sample count on the host.
+ *    3. No atomics: every element has one owning workgroup, so the same call on the same state gives the same bits.  Only the
+ *       upper triangle is computed; the owner writes the mirrored element too, so gram is bitwise symmetric on return (given a
+ *       symmetric gram on entry).
+ *    4. Non-finite inputs propagate as IEEE arithmetic has it. */
+size_t dhw_moments_workspace_bytes(int N, int S, int D);
+int dhw_moments_update(const float* feat,   /* device f32 [N,S,D]                     */
+                       int N, int S, int D,
+                       double* sum,         /* device f64 [D], in/out                 */
+                       double* gram,        /* device f64 [D,D], in/out, both triangles */
+                       void* ws, size_t ws_bytes, void* hip_stream);
+
 /* Reuse of the text side across calls.  The text side of the sampler (TextStyleEncoder and every layer's text K / V, for all T
  * steps) depends on text, style, T and the weights only.  A dhw_sample / dhw_sample_ragged / dhw_sample_cond call whose text and
  * style hold the same BITS as the previous such call's on this handle, at the same B, Lt, T and t_start, with unchanged weights
