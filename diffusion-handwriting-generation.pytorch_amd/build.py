@@ -16,7 +16,8 @@ SOURCES = ["train/sgemm_f32.hip", "train/sgemm_bf16.hip", "train/sgemm_group.hip
            "dhw_api.cpp", "dhw_style_api.cpp", "dhw_train_api.cpp",
            "render/dhw_render_api.cpp", "cond/dhw_cond_api.cpp", "score/dhw_score_api.cpp", "attnmap/dhw_attnmap_api.cpp", "sampler/weights.cpp", "sampler/workspace.cpp", "sampler/denoiser.cpp", "sampler/sample.cpp", "sampler/debug.cpp",
            "step/step.hip", "step/dhw_step_api.cpp", "page/page.hip", "page/dhw_page_api.cpp", "encode/encode.hip", "encode/dhw_encode_api.cpp",
-           "prep/prep.hip", "prep/dhw_prep_api.cpp", "train/cond_drop.hip", "moments/moments.hip", "moments/dhw_moments_api.cpp"]
+           "prep/prep.hip", "prep/dhw_prep_api.cpp", "train/cond_drop.hip", "moments/moments.hip", "moments/dhw_moments_api.cpp",
+           "pairs/pairs.hip", "pairs/dhw_pairs_api.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
 

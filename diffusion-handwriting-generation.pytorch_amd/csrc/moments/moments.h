@@ -48,5 +48,8 @@ inline int moments_check_args(const void* feat, int N, int S, int D, const void*
   return 0;
 }
 
+// rule 1 alone: pooled[n][d] = (sum_s (double)feat[n][s][d]) / S, s ascending (moments_pool_kernel; also behind dhw_pairs_pool)
+hipError_t launch_moments_pool(const float* feat, int N, int S, int D, double* pooled, hipStream_t st);
+
 // pooled = ws, f64 [N,D]: three launches on st (pool, column sums, gram), no allocation, no synchronisation
 hipError_t launch_moments(const float* feat, int N, int S, int D, double* sum, double* gram, double* pooled, hipStream_t st);

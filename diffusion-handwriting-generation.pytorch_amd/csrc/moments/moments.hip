@@ -152,10 +152,16 @@ __global__ __launch_bounds__(MOMENTS_THREADS) void moments_gram_kernel(const dou
     }
 }
 
-hipError_t launch_moments(const float* feat, int N, int S, int D, double* sum, double* gram, double* pooled, hipStream_t st) {
+hipError_t launch_moments_pool(const float* feat, int N, int S, int D, double* pooled, hipStream_t st) {
   const size_t cells = (size_t)N * D;
-  const int nb = (D + MOMENTS_BLOCK - 1) / MOMENTS_BLOCK;
   hipLaunchKernelGGL(moments_pool_kernel, dim3((unsigned)((cells + MOMENTS_THREADS - 1) / MOMENTS_THREADS)), dim3(MOMENTS_THREADS), 0, st, feat, N, S, D, pooled);
+  return hipGetLastError();
+}
+
+hipError_t launch_moments(const float* feat, int N, int S, int D, double* sum, double* gram, double* pooled, hipStream_t st) {
+  const int nb = (D + MOMENTS_BLOCK - 1) / MOMENTS_BLOCK;
+  const hipError_t e = launch_moments_pool(feat, N, S, D, pooled, st);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(moments_sum_kernel, dim3(D / 16), dim3(MOMENTS_THREADS), 0, st, pooled, N, D, sum);
   hipLaunchKernelGGL(moments_gram_kernel, dim3(nb * (nb + 1) / 2), dim3(MOMENTS_THREADS), 0, st, pooled, N, D, gram);
   return hipGetLastError();

@@ -548,6 +548,52 @@ int dhw_moments_update(const float* feat,   /* device f32 [N,S,D]               
                        double* gram,        /* device f64 [D,D], in/out, both triangles */
                        void* ws, size_t ws_bytes, void* hip_stream);
 
+/* Pairwise statistics of two sets of pooled feature vectors in double precision: what precision / recall (Kynkaanniemi et al.
+ * 2019), density / coverage (Naeem et al. 2020), the kernel distance (unbiased MMD^2, cubic polynomial kernel) and a
+ * nearest-neighbour search are made of.  No handle: errors are read through dhw_last_error(NULL).  The calls
+ * allocate nothing, synchronise nothing and can be captured into a graph.  All argument checks run before the first HIP call
+ * (DHW_ERR_ARG names the argument): 1 <= M, N <= 16384, D a multiple of 16 in [16, 2048], 1 <= k <= 8 and k < N, pointers
+ * non-NULL (except where marked) and 16-byte aligned, ws_bytes >= dhw_pairs_workspace_bytes(M, N, D) (dhw_pairs_knn: of
+ * (N, N, D); 0 for dimensions the entries refuse).
+ *    1. dhw_pairs_pool: out[n][d] = (sum_s (double)feat[n][s][d]) / (double)S, s ascending: rule 1 of dhw_moments_update, the
+ *       same kernel.  1 <= S <= 64, N S D < 2^31, rows of feat at or past N are never read.
+ *    2. d2(i, j) = fmax(0, sq_i + sq_j - 2 dot_ij): sq the row's own squared norm in double, dot the inner product on
+ *       v_mfma_f64_16x16x4_f64 with d ascending.  The M x N matrix is never written: it is reduced where it is computed.
+ *    3. dhw_pairs_knn: radius2[i] = the k-th smallest of { d2(x_i, x_j) : j != i }.  j is excluded by index: a duplicate of
+ *       row i counts, and gives radius 0.
+ *    4. dhw_pairs_cover: count[m] = #{ j : d2(q_m, ref_j) <= radius2[j] }, nearest2[m] = min_j d2(q_m, ref_j), nearest_idx[m] =
+ *       the smallest j attaining it.  radius2 and count are both given or both NULL; nearest_idx may be NULL.
+ *    5. dhw_pairs_polysum: out[0] = sum_{i,j} (x_i . y_j + D)^3, without the pairs i == j when skip_diag != 0 (which needs
+ *       M == N).  Dividing by D^3 and normalising is the caller's.
+ *    6. No atomics: every output element has one writer and every sum a fixed order, so the same call on the same inputs gives
+ *       the same bits.  The column range is split over workgroups and the partial results are merged in a fixed order; env
+ *       DHW_PAIRS_SPLIT=<n> (read at each call; 0 or unset: automatic) forces the number of splits.  Rows at or past M / N are
+ *       never read.  Inputs are assumed finite. */
+int dhw_pairs_pool(const float* feat,   /* device f32 [N,S,D] */
+                   int N, int S, int D,
+                   double* out,         /* device f64 [N,D]   */
+                   void* hip_stream);
+size_t dhw_pairs_workspace_bytes(int M, int N, int D);
+int dhw_pairs_knn(const double* x,      /* device f64 [N,D] */
+                  int N, int D, int k,
+                  double* radius2,      /* device f64 [N]   */
+                  void* ws, size_t ws_bytes, void* hip_stream);
+int dhw_pairs_cover(const double* q,          /* device f64 [M,D]        */
+                    int M,
+                    const double* ref,        /* device f64 [N,D]        */
+                    int N, int D,
+                    const double* radius2,    /* device f64 [N] or NULL  */
+                    int32_t* count,           /* device i32 [M] or NULL  */
+                    double* nearest2,         /* device f64 [M]          */
+                    int32_t* nearest_idx,     /* device i32 [M] or NULL  */
+                    void* ws, size_t ws_bytes, void* hip_stream);
+int dhw_pairs_polysum(const double* x,   /* device f64 [M,D] */
+                      int M,
+                      const double* y,   /* device f64 [N,D] */
+                      int N, int D, int skip_diag,
+                      double* out,       /* device f64 [1]   */
+                      void* ws, size_t ws_bytes, void* hip_stream);
+
 /* Reuse of the text side across calls.  The text side of the sampler (TextStyleEncoder and every layer's text K / V, for all T
  * steps) depends on text, style, T and the weights only.  A dhw_sample / dhw_sample_ragged / dhw_sample_cond call whose text and
  * style hold the same BITS as the previous such call's on this handle, at the same B, Lt, T and t_start, with unchanged weights

@@ -3,12 +3,16 @@
 rows, in the StyleExtractor's feature space (dhg_amd.sample_quality).
 
     python tools/eval_samples.py --data val.pt --experiment-path runs/exp1 --weights mobilenet_v2.pth \\
-        [--n 1024] [--guidance 2.5] [--steps 20] [--mode new] [--real-stats real.npz] [--save-real-stats real.npz]
+        [--n 1024] [--guidance 2.5] [--steps 20] [--mode new] [--real-stats real.npz] [--save-real-stats real.npz] [--metrics [--k 3]]
 
 --data is the file train.py --val reads: {"strokes" [N,L,3], "text" [N,Lt], "style" [N,14,1280]}.  Several values of --guidance
 or --steps give one line per combination; the real statistics are computed once (or read from --real-stats).  One line per run:
 
     FD <value> | n <count> | sampler <sample|ddim> | T .. | steps .. | guidance .. | mode .. | seconds: sample .. features .. moments .. eig ..
+
+--metrics: a second line per run, from dhg_amd.sample_metrics (at most 16384 lines, not with --real-stats):
+
+    PR precision .. | recall .. | density .. | coverage .. | KID .. | k ..
 
 --synthetic: the model holds spec.synthetic_state_dict(2) instead of a checkpoint (with --synthetic-rows R, --data is first
 written with R synthetic rows); without --weights the extractor is random-initialised.  Such distances only exercise the path.
@@ -42,7 +46,7 @@ def synthetic_rows(rows, L, Lt, seed=0):
     return {"strokes": torch.from_numpy(strokes), "text": torch.from_numpy(inp["text"]), "style": torch.from_numpy(inp["style"])}
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", required=True)
     ap.add_argument("--experiment-path")
@@ -64,11 +68,22 @@ def main(argv=None):
     ap.add_argument("--synthetic-L", type=int, default=256)
     ap.add_argument("--synthetic-Lt", type=int, default=32)
     ap.add_argument("--json", help="also write the runs to this file")
+    ap.add_argument("--metrics", action="store_true", help="also print precision / recall / density / coverage and KID (a PR line per setting)")
+    ap.add_argument("--k", type=int, default=3, help="neighbours of the k-NN balls of --metrics (1 to 8)")
+    return ap
+
+
+def main(argv=None):
+    ap = parser()
     a = ap.parse_args(argv)
     if a.mode is not None and any(s is not None for s in a.steps):
         ap.error("--mode belongs to the ancestral sampler: it cannot be combined with --steps")
     if a.synthetic_rows is not None and not a.synthetic:
         ap.error("--synthetic-rows needs --synthetic")
+    if a.metrics and a.real_stats:
+        ap.error("--metrics needs the real lines themselves: it cannot be combined with --real-stats")
+    if not 1 <= a.k <= 8:
+        ap.error("--k must be in [1, 8]")
     sys.path.insert(0, ROOT)
     import torch
 
@@ -92,6 +107,7 @@ def main(argv=None):
             warnings.simplefilter("ignore")   # the random initialisation is what --synthetic asks for
         extractor = dhg_amd.StyleExtractor(a.weights)
     real = dhg_amd.FeatureStats.load(a.real_stats) if a.real_stats else None
+    real_pair = None   # --metrics: (statistics, rows) of the real lines, computed by the first run
     runs = []
     for steps in a.steps:
         for guidance in a.guidance:
@@ -103,12 +119,20 @@ def main(argv=None):
             if guidance is not None:
                 kw["guidance"] = guidance
             sec = {}
-            fd, real, gen = dhg_amd.sample_quality(model, data, extractor, n=a.n, batch=a.batch, seed=a.seed, real=real, timings=sec, **kw)
+            if a.metrics:
+                m = dhg_amd.sample_metrics(model, data, extractor, n=a.n, batch=a.batch, seed=a.seed, k=a.k, real=real_pair, timings=sec, **kw)
+                fd, real, gen, real_pair = m["fd"], m["real_stats"], m["gen_stats"], (m["real_stats"], m["real_set"])
+            else:
+                fd, real, gen = dhg_amd.sample_quality(model, data, extractor, n=a.n, batch=a.batch, seed=a.seed, real=real, timings=sec, **kw)
             run = {"fd": fd, "n": gen.count, "n_real": real.count, "sampler": "ddim" if steps is not None else "sample", "T": a.T, "steps": steps,
                    "guidance": guidance, "mode": None if steps is not None else (a.mode or "new"), "seconds": {k: round(v, 4) for k, v in sec.items()}}
             runs.append(run)
             print(f"FD {fd:.6g} | n {gen.count} | sampler {run['sampler']} | T {a.T} | steps {steps} | guidance {guidance} | mode {run['mode']} | "
                   "seconds: " + " ".join(f"{k} {v:.3f}" for k, v in sec.items()), flush=True)
+            if a.metrics:
+                run.update({name: m[name] for name in ("precision", "recall", "density", "coverage", "kid", "k")})
+                print(f"PR precision {m['precision']:.4f} | recall {m['recall']:.4f} | density {m['density']:.4f} | coverage {m['coverage']:.4f} | "
+                      f"KID {m['kid']:.6g} | k {m['k']}", flush=True)
     if a.save_real_stats:
         real.save(a.save_real_stats)
     if a.json:
