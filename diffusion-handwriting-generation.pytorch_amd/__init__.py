@@ -7,6 +7,7 @@ from .vis import render_page, render_strokes, save_line_png, save_page_png, show
 from .encode import encode_strokes, make_batches, padded_lengths, read_strokes_xml  # noqa: F401
 from .imgprep import load_styles, prepare_images  # noqa: F401
 from .quality import FeatureSet, FeatureStats, frechet_distance, kernel_distance, knn_radius, line_features, nearest, precision_recall, sample_metrics, sample_quality  # noqa: F401
+from .dtw import dtw_distance, nearest_strokes, stroke_features  # noqa: F401
 from .model import DiffusionModel, DiffusionWriter  # noqa: F401
 from .style_extractor import StyleExtractor  # noqa: F401
 from .tokenizer import Tokenizer, stroke_length  # noqa: F401

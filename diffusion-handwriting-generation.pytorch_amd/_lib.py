@@ -91,6 +91,8 @@ SIGNATURES = {
     "dhw_pairs_knn": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "dhw_pairs_cover": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "dhw_pairs_polysum": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "dhw_dtw_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dhw_dtw": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "dhw_schedule": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "dhw_work": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dhw_last_error": (C.c_char_p, [_P]),

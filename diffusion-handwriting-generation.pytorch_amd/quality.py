@@ -433,11 +433,12 @@ def _sampler_of(sampler: dict, who: str = "sample_quality"):
     return ddim
 
 
-def _evaluate(who, model, data, extractor, n, batch, seed, real, real_set, with_sets, timings, sampler):
+def _evaluate(who, model, data, extractor, n, batch, seed, real, real_set, with_sets, timings, sampler, keep=None):
     """The one loop behind ``sample_quality`` and ``sample_metrics``: the first ``n`` rows of ``data``, ``batch`` at a time, real
     lines rendered and generated lines drawn with ``first_sample`` = the row index; every batch of features feeds a
     ``FeatureStats`` and, ``with_sets``, a ``FeatureSet``.  ``real`` / ``real_set``: given statistics / rows of the real lines
-    (None: computed).  Returns (fd, real, gen, real_set, gen_set)."""
+    (None: computed).  ``keep`` (a list): the generated strokes of every batch are appended to it.  Returns (fd, real, gen,
+    real_set, gen_set)."""
     ddim = _sampler_of(sampler, who)
     for k in ("strokes", "text", "style"):
         if k not in data:
@@ -495,6 +496,8 @@ def _evaluate(who, model, data, extractor, n, batch, seed, real, real_set, with_
         lines = draw(model, torch.as_tensor(data["text"][lo:hi]).to(dev), torch.as_tensor(data["style"][lo:hi]).to(dev), L=L, seed=seed,
                      first_sample=lo, **sampler)
         t1 = tick()
+        if keep is not None:
+            keep.append(lines)
         f = line_features(lines, extractor, batch=batch)
         t2 = tick()
         gen.update(f)
@@ -523,17 +526,46 @@ def sample_quality(model, data, extractor, n=None, batch: int = 32, seed: int = 
     return _evaluate("sample_quality", model, data, extractor, n, batch, seed, real, None, False, timings, sampler)[:3]
 
 
-def sample_metrics(model, data, extractor, n=None, batch: int = 32, seed: int = 0, k: int = 3, real=None, timings=None, **sampler):
+def sample_metrics(model, data, extractor, n=None, batch: int = 32, seed: int = 0, k: int = 3, real=None, timings=None, dtw: bool = False, **sampler):
     """``sample_quality`` with every metric: the same rows, sampler keywords and ``first_sample`` (one loop serves both), the
     features of each batch kept as statistics and as rows.  ``real``: a ``FeatureSet`` of the real lines (its statistics are
     computed from its rows) or a (``FeatureStats``, ``FeatureSet``) pair, used as given; None: both come from ``data["strokes"]``.
     At most 16384 lines.  Returns {"fd", "precision", "recall", "density", "coverage", "kid", "k", "n", "real_stats", "gen_stats",
-    "real_set", "gen_set"}; "fd" is ``sample_quality``'s value, bit for bit."""
+    "real_set", "gen_set"}; "fd" is ``sample_quality``'s value, bit for bit.
+
+    ``dtw=True`` also keeps the real and the generated strokes and adds the stroke-space distances of DESIGN.md §39 (normalised
+    ``dtw_distance`` with its default features): "dtw_paired", the mean distance between generated row r and real row r;
+    "dtw_nearest", the mean over generated rows of the distance to the nearest real line, with the index vector
+    "dtw_nearest_idx" (a value near 0: the model copies that line); "dtw_self", the mean over generated rows of the distance to
+    the nearest other generated line (a value near 0: the samples collapse onto one another).  Every other key is unchanged."""
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= PAIRS_MAX_K:
         raise ValueError(f"k = {k!r} must be an integer in [1, {PAIRS_MAX_K}]")
     stats, rows = real if isinstance(real, tuple) and len(real) == 2 else (None, real)
+    if dtw and "strokes" in data:
+        from .dtw import DTW_MAX_L
+        if int(data["strokes"].shape[1]) > DTW_MAX_L:
+            raise ValueError(f"dtw=True: lines of L = {int(data['strokes'].shape[1])} rows: at most {DTW_MAX_L}")
+    kept = [] if dtw else None
     fd, real_stats, gen_stats, real_set, gen_set = _evaluate("sample_metrics", model, data, extractor, n, batch, seed, stats, rows, True, timings,
-                                                             sampler)
+                                                             sampler, kept)
     out = {"fd": fd, **precision_recall(real_set, gen_set, k), "kid": kernel_distance(real_set, gen_set), "k": int(k), "n": gen_set.count,
            "real_stats": real_stats, "gen_stats": gen_stats, "real_set": real_set, "gen_set": gen_set}
+    if dtw:
+        out.update(_dtw_metrics(kept, data["strokes"], gen_set.count, batch))
     return out
+
+
+def _dtw_metrics(kept, real_strokes, n: int, batch: int) -> dict:
+    """The stroke-space keys of ``sample_metrics``: generated strokes `kept` (one tensor per batch) against the first n real lines.
+    The paired distances are the diagonal of the generated x real matrix, computed in diagonal blocks of `batch` lines (a pair's
+    bits do not depend on the block it is computed in)."""
+    import torch
+
+    from .dtw import dtw_distance, nearest_strokes
+    gen = torch.cat(kept) if len(kept) != 1 else kept[0]
+    real = torch.as_tensor(real_strokes[:n]).to(gen.device)
+    paired = torch.cat([dtw_distance(gen[lo:lo + batch], real[lo:lo + batch])[0].diagonal() for lo in range(0, n, batch)])
+    near, idx = nearest_strokes(gen, real)
+    self_near, _ = nearest_strokes(gen)
+    mean = lambda t: float(t.cpu().numpy().astype(np.float64).mean())   # noqa: E731
+    return {"dtw_paired": mean(paired), "dtw_nearest": mean(near), "dtw_nearest_idx": idx, "dtw_self": mean(self_near)}

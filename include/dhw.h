@@ -594,6 +594,41 @@ int dhw_pairs_polysum(const double* x,   /* device f64 [M,D] */
                       double* out,       /* device f64 [1]   */
                       void* ws, size_t ws_bytes, void* hip_stream);
 
+/* Dynamic time warping (DTW) between every line of a set a and every line of a set b, in stroke space: a distance that sees
+ * pen order, speed and lifts and needs no trained network.  No handle: errors are read through
+ * dhw_last_error(NULL).  The call allocates nothing, synchronises nothing and can be captured into a graph.  All argument
+ * checks run before the first HIP call (DHW_ERR_ARG names the argument): 1 <= M, N <= 16384 and M N <= 2^26; 1 <= La, Lb <=
+ * 1024; 1 <= F <= 4; skip_diag only with M == N; at least one of dist_out / steps_out / nearest_out; nearest_idx only together
+ * with nearest_out; a, b and ws non-NULL; every non-NULL pointer 16-byte aligned; ws_bytes >= dhw_dtw_workspace_bytes(M, N,
+ * La, Lb, F) = M N sizeof(float) rounded up to a multiple of 16 (the matrix the nearest pass reads when dist_out is NULL), and 0
+ * for dimensions the entry refuses.
+ *
+ * Pair (p, q), with n = lens_a[p] (La when lens_a is NULL) and m = lens_b[q] (Lb when lens_b is NULL):
+ *    1. Rows of a[p] at or past n and rows of b[q] at or past m are never read, whatever they hold.
+ *    2. c(i,j) = sum_{f<F} (a[p][i][f] - b[q][j][f])^2: the difference, the product and the sum over f ascending are fp32
+ *       operations of their own; there is no fused multiply-add.
+ *    3. D(0,0) = c(0,0) and K(0,0) = 1.
+ *    4. Otherwise D(i,j) = c(i,j) + min(D(i-1,j-1), D(i-1,j), D(i,j-1)) in fp32, over the predecessors that exist.
+ *    5. The predecessor is the first of (i-1,j-1), (i-1,j), (i,j-1), in that order, that attains the minimum;
+ *       K(i,j) = K(predecessor) + 1: the number of cells on the warping path.
+ *    6. dist = D(n-1,m-1) and steps = K(n-1,m-1).  With normalize != 0, dist is divided by (float)steps in one correctly
+ *       rounded fp32 division.
+ *    7. A length outside [1, La] (or [1, Lb]) gives dist = +inf and steps = 0 for every pair of that line.
+ *    8. nearest_out[p] = the smallest dist over q (q != p with skip_diag != 0), nearest_idx[p] = the smallest q attaining it;
+ *       +inf and -1 when no pair of p is finite.
+ *    9. No atomics and one writer per output element: the same call gives the same bits, and pair (p, q) gives the same bits
+ *       alone (M = N = 1) as inside any batch.
+ *   10. Non-finite features are the caller's business: no access leaves the buffers, nothing else is promised for them. */
+size_t dhw_dtw_workspace_bytes(int M, int N, int La, int Lb, int F);
+int dhw_dtw(const float* a, const int32_t* lens_a, int M, int La,     /* device f32 [M,La,F]; DEVICE int32 [M] or NULL */
+            const float* b, const int32_t* lens_b, int N, int Lb,     /* device f32 [N,Lb,F]; DEVICE int32 [N] or NULL */
+            int F, int normalize, int skip_diag,
+            float* dist_out,        /* device f32 [M,N] or NULL */
+            int32_t* steps_out,     /* device int32 [M,N] or NULL */
+            float* nearest_out,     /* device f32 [M] or NULL */
+            int32_t* nearest_idx,   /* device int32 [M] or NULL; only together with nearest_out */
+            void* ws, size_t ws_bytes, void* hip_stream);
+
 /* Reuse of the text side across calls.  The text side of the sampler (TextStyleEncoder and every layer's text K / V, for all T
  * steps) depends on text, style, T and the weights only.  A dhw_sample / dhw_sample_ragged / dhw_sample_cond call whose text and
  * style hold the same BITS as the previous such call's on this handle, at the same B, Lt, T and t_start, with unchanged weights

@@ -3,7 +3,7 @@
 rows, in the StyleExtractor's feature space (dhg_amd.sample_quality).
 
     python tools/eval_samples.py --data val.pt --experiment-path runs/exp1 --weights mobilenet_v2.pth \\
-        [--n 1024] [--guidance 2.5] [--steps 20] [--mode new] [--real-stats real.npz] [--save-real-stats real.npz] [--metrics [--k 3]]
+        [--n 1024] [--guidance 2.5] [--steps 20] [--mode new] [--real-stats real.npz] [--save-real-stats real.npz] [--metrics [--k 3]] [--dtw]
 
 --data is the file train.py --val reads: {"strokes" [N,L,3], "text" [N,Lt], "style" [N,14,1280]}.  Several values of --guidance
 or --steps give one line per combination; the real statistics are computed once (or read from --real-stats).  One line per run:
@@ -13,6 +13,10 @@ or --steps give one line per combination; the real statistics are computed once 
 --metrics: a second line per run, from dhg_amd.sample_metrics (at most 16384 lines, not with --real-stats):
 
     PR precision .. | recall .. | density .. | coverage .. | KID .. | k ..
+
+--dtw: one more line per run, the stroke-space distances of dhg_amd.sample_metrics(dtw=True) (not with --real-stats):
+
+    DTW paired .. | nearest .. | self ..
 
 --synthetic: the model holds spec.synthetic_state_dict(2) instead of a checkpoint (with --synthetic-rows R, --data is first
 written with R synthetic rows); without --weights the extractor is random-initialised.  Such distances only exercise the path.
@@ -70,6 +74,7 @@ def parser():
     ap.add_argument("--json", help="also write the runs to this file")
     ap.add_argument("--metrics", action="store_true", help="also print precision / recall / density / coverage and KID (a PR line per setting)")
     ap.add_argument("--k", type=int, default=3, help="neighbours of the k-NN balls of --metrics (1 to 8)")
+    ap.add_argument("--dtw", action="store_true", help="also print the stroke-space DTW distances (a DTW line per setting)")
     return ap
 
 
@@ -80,8 +85,8 @@ def main(argv=None):
         ap.error("--mode belongs to the ancestral sampler: it cannot be combined with --steps")
     if a.synthetic_rows is not None and not a.synthetic:
         ap.error("--synthetic-rows needs --synthetic")
-    if a.metrics and a.real_stats:
-        ap.error("--metrics needs the real lines themselves: it cannot be combined with --real-stats")
+    if (a.metrics or a.dtw) and a.real_stats:
+        ap.error("--metrics and --dtw need the real lines themselves: they cannot be combined with --real-stats")
     if not 1 <= a.k <= 8:
         ap.error("--k must be in [1, 8]")
     sys.path.insert(0, ROOT)
@@ -119,7 +124,9 @@ def main(argv=None):
             if guidance is not None:
                 kw["guidance"] = guidance
             sec = {}
-            if a.metrics:
+            if a.metrics or a.dtw:
+                if a.dtw:
+                    kw["dtw"] = True
                 m = dhg_amd.sample_metrics(model, data, extractor, n=a.n, batch=a.batch, seed=a.seed, k=a.k, real=real_pair, timings=sec, **kw)
                 fd, real, gen, real_pair = m["fd"], m["real_stats"], m["gen_stats"], (m["real_stats"], m["real_set"])
             else:
@@ -133,6 +140,9 @@ def main(argv=None):
                 run.update({name: m[name] for name in ("precision", "recall", "density", "coverage", "kid", "k")})
                 print(f"PR precision {m['precision']:.4f} | recall {m['recall']:.4f} | density {m['density']:.4f} | coverage {m['coverage']:.4f} | "
                       f"KID {m['kid']:.6g} | k {m['k']}", flush=True)
+            if a.dtw:
+                run.update({name: m[name] for name in ("dtw_paired", "dtw_nearest", "dtw_self")})
+                print(f"DTW paired {m['dtw_paired']:.6g} | nearest {m['dtw_nearest']:.6g} | self {m['dtw_self']:.6g}", flush=True)
     if a.save_real_stats:
         real.save(a.save_real_stats)
     if a.json:
