@@ -170,8 +170,10 @@ struct dhw_handle {
   // x_t in x and its draw z in w; the ddim entries keep the state in x and the inversion's iterate in w; eps, pen and sigma are
   // the denoiser's outputs and input for both.  The entries share the set as they share ws[0]: all of them launch eagerly on
   // the caller's stream, and within a call every row p < lens[b] is written before a launch of that call reads it, while rows
-  // at or past lens[b] are never read.  No graph reads the set: these calls leave the cached graphs alone.
-  struct DenoiseScratch { float *x = nullptr, *w = nullptr, *eps = nullptr, *pen = nullptr, *sigma = nullptr; } scratch;
+  // at or past lens[b] are never read.  No graph reads the set: these calls leave the cached graphs alone.  hist [max_B*max_L, 2]
+  // is the set's fifth buffer: the previous step's x0 estimate of dhw_dpm_sample / dhw_guided_dpm_sample, allocated at the first
+  // such call (step/dhw_step_api.cpp) and never moved; step 0 of a call writes it before any step reads it.
+  struct DenoiseScratch { float *x = nullptr, *w = nullptr, *eps = nullptr, *pen = nullptr, *sigma = nullptr, *hist = nullptr; } scratch;
   uint64_t* d_seed = nullptr;   // [seed, first_sample] read by the noise kernels
   // Reuse of the all-steps text plane across dhw_sample* calls.  plane_tag: what the plane in the ".T" buffers was
   // computed for; cleared by everything that may change it (plane_invalidate) and while a call is being enqueued.

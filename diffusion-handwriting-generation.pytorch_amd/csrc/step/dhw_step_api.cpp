@@ -1,6 +1,7 @@
 // dhw_step_api.cpp — C-ABI of the eager samplers (include/dhw.h): deterministic sampling and inversion (dhw_ddim_sample,
-// dhw_ddim_invert, dhw_ddim_update) and classifier-free guided sampling (dhw_guided_ddim_sample,
-// dhw_guided_sample, dhw_guide_update; §33).  A sampling call is step_start, then per step the launches of dhw_forward /
+// dhw_ddim_invert, dhw_ddim_update), classifier-free guided sampling (dhw_guided_ddim_sample,
+// dhw_guided_sample, dhw_guide_update; §33) and the second-order multistep solver over the same levels (dhw_dpm_coefs,
+// dhw_dpm_update, dhw_dpm_sample, dhw_guided_dpm_sample; §40).  A sampling call is step_start, then per step the launches of dhw_forward /
 // dhw_forward_ragged (sampler/sample.cpp: forward_enqueue) and one step_update (step_loop) — eagerly on the caller's stream.  A
 // guided call runs ONE forward over 2B rows per step: rows [0, B) under the real condition, rows [B, 2B) under the guidance
 // condition, the same x in both.  Nothing here touches h->d_seed, the sampler's staging buffers, its graph cache, its step
@@ -9,9 +10,12 @@
 #include <vector>
 
 #include "../sampler/denoiser.h"
+#include "solver_host.h"
 #include "step.h"
 
 namespace {
+
+constexpr int STEP_DPM = 3;   // step_loop's kind behind the three GuideKinds: dpm_update (step.h DpmParams) instead of step_update
 
 // ---------------------------------------------------------------- the start and the loop of every sampling entry
 // what one step of a sampling call hands to step_update, computed on the host in fp32 before the first launch
@@ -21,12 +25,21 @@ struct Step {
   float sigma_next;
   const float* z;   // the step's external noise, or null
   int iter;
+  int second;       // STEP_DPM: a second-order step, with (k0, k1, c4, c5) of solver_host.h
+  float k0, k1, c4, c5;
 };
 
 // the steps of a deterministic call: level j to level j + 1 of the coefficient table, no noise
 std::vector<Step> ddim_steps(const std::vector<DdimCoef>& t, int S) {
   std::vector<Step> steps((size_t)S);
   for (size_t j = 0; j < (size_t)S; ++j) steps[j] = Step{t[j].A, t[j].B, t[j + 1].A, t[j + 1].B, 0, t[j + 1].A, nullptr, 0};
+  return steps;
+}
+
+// the steps of a multistep call: the rows of the solver's table
+std::vector<Step> dpm_steps(const std::vector<DpmCoef>& t) {
+  std::vector<Step> steps(t.size());
+  for (size_t j = 0; j < t.size(); ++j) steps[j] = Step{t[j].c0, t[j].c1, t[j].c2, t[j].c3, 0, t[j].c2, nullptr, 0, t[j].kind == DPM_SECOND, t[j].k0, t[j].k1, t[j].c4, t[j].c5};
   return steps;
 }
 
@@ -73,12 +86,41 @@ StepParams step_params(dhw_handle* h, const int* dl, int halves, int kind, int B
   return p;
 }
 
+// the multistep update's own block (step.h: StepParams keeps its size) from a step's filled StepParams and the step's second-order part
+DpmParams dpm_params(const StepParams& p, const Step& g, float* hist) {
+  DpmParams d{};
+  d.base = p.base;
+  d.eps = p.eps;
+  d.pen = p.pen;
+  d.lens = p.lens;
+  d.scale = p.scale;
+  d.hist = hist;
+  d.rows = p.rows;
+  d.B = p.B;
+  d.L = p.L;
+  d.halves = p.halves;
+  d.second = g.second;
+  d.c0 = p.c0;
+  d.c1 = p.c1;
+  d.c2 = p.c2;
+  d.c3 = p.c3;
+  d.k0 = g.k0;
+  d.k1 = g.k1;
+  d.c4 = g.c4;
+  d.c5 = g.c5;
+  d.out = p.out;
+  d.out3 = p.out3;
+  d.sigma = p.sigma;
+  d.sigma_next = p.sigma_next;
+  return d;
+}
+
 // per step: the forward over halves * B rows, then the update in place; the last step writes the caller's [B, L, 3] instead
 int step_loop(dhw_handle* h, EagerCall& ec, int halves, int kind, const int64_t* text, const float* style, int B, int L, int Lt, uint64_t seed,
               int64_t first_sample, const std::vector<Step>& steps, float* out) {
   auto& [st, dl, c] = ec;
   const dhw_handle::DenoiseScratch& s = h->scratch;
-  const char* label = halves == 2 ? "guide_update" : "ddim_update";
+  const char* label = kind == STEP_DPM ? "dpm_update" : halves == 2 ? "guide_update" : "ddim_update";
   StepParams p = step_params(h, dl, halves, kind, B, L);
   p.seed = seed;
   p.first_sample = first_sample;
@@ -97,7 +139,8 @@ int step_loop(dhw_handle* h, EagerCall& ec, int halves, int kind, const int64_t*
     p.out3 = last ? out : nullptr;
     p.sigma = last ? nullptr : s.sigma;
     p.sigma_next = g.sigma_next;
-    RUN_SMALL(c, label, launch_step_update(p, st));
+    if (kind == STEP_DPM) RUN_SMALL(c, label, launch_dpm_update(dpm_params(p, g, s.hist), st));
+    else RUN_SMALL(c, label, launch_step_update(p, st));
     if (c.err) return c.err;
   }
   return 0;
@@ -114,18 +157,40 @@ int ddim_check_common(dhw_handle* h, const char* fn, const int64_t* text, const 
   return 0;
 }
 
+// the multistep entries' own checks (behind the level checks, before the first HIP call) and their table
+int dpm_check_table(dhw_handle* h, const char* fn, int T, const int32_t* levels, int S, int order, std::vector<DpmCoef>& table) {
+  char msg[160];
+  if (solver_check_order(order, msg, sizeof msg) || dpm_coef_table(schedule_abar(T).data(), levels, S, order, table, msg, sizeof msg))
+    return fail(h, DHW_ERR_ARG, "%s: %s", fn, msg);
+  return 0;
+}
+
+// the set's fifth buffer, behind ensure_scratch: allocated once, at the handle's capacity, never moved
+int ensure_hist(dhw_handle* h) {
+  if (h->scratch.hist) return 0;
+  return dev_alloc(h, (void**)&h->scratch.hist, (size_t)h->dims.max_B * h->dims.max_L * 2 * 4);
+}
+
+// order null: dhw_ddim_sample; else dhw_dpm_sample with that order
 int sample_impl_ddim(dhw_handle* h, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens, int T, const int32_t* levels,
-                     int S, const float* latent, uint64_t seed, int64_t first_sample, float* latent_out, float* out, void* hip_stream) {
-  const char* fn = "dhw_ddim_sample";
+                     int S, const float* latent, uint64_t seed, int64_t first_sample, float* latent_out, float* out, void* hip_stream, const int* order = nullptr) {
+  const bool dpm = order != nullptr;
+  const char* fn = dpm ? "dhw_dpm_sample" : "dhw_ddim_sample";
   if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
   if (!out) return fail(h, DHW_ERR_ARG, "%s: null pointer (out)", fn);
   int rc = ddim_check_common(h, fn, text, style, B, L, Lt, lens, T, levels, S);
   if (rc) return rc;
+  std::vector<DpmCoef> table;
+  if (dpm && (rc = dpm_check_table(h, fn, T, levels, S, *order, table))) return rc;
   if (((uintptr_t)latent | (uintptr_t)latent_out) & 7)
     return fail(h, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)latent & 7) ? "latent" : "latent_out");
 
   EagerCall ec;
   if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec)) || (rc = ensure_scratch(h))) return rc;   // (leaves dhw_sample's text plane alone: forward_enqueue)
+  if (dpm) {
+    if ((rc = ensure_hist(h)) || (rc = step_start(h, ec, 1, latent, 2, B, L, seed, first_sample, table[0].c0, latent_out))) return rc;
+    return step_loop(h, ec, 1, STEP_DPM, text, style, B, L, Lt, 0, 0, dpm_steps(table), out);
+  }
   const std::vector<DdimCoef> t = ddim_coef_table(schedule_abar(T).data(), levels, S);
   if ((rc = step_start(h, ec, 1, latent, 2, B, L, seed, first_sample, t[0].A, latent_out))) return rc;
   return step_loop(h, ec, 1, GUIDE_DDIM, text, style, B, L, Lt, 0, 0, ddim_steps(t, S), out);
@@ -240,19 +305,27 @@ int guide_begin(dhw_handle* h, int B, int L, int Lt, const int32_t* lens, const 
 }
 
 int sample_impl_guided_ddim(dhw_handle* h, const int64_t* text2, const float* style2, int B, int L, int Lt, const int32_t* lens, int T, const int32_t* levels,
-                            int S, const float* scale, const float* latent, uint64_t seed, int64_t first_sample, float* out, float* latent_out, void* hip_stream) {
-  const char* fn = "dhw_guided_ddim_sample";
+                            int S, const float* scale, const float* latent, uint64_t seed, int64_t first_sample, float* out, float* latent_out, void* hip_stream,
+                            const int* order = nullptr) {   // order null: dhw_guided_ddim_sample; else dhw_guided_dpm_sample with that order
+  const bool dpm = order != nullptr;
+  const char* fn = dpm ? "dhw_guided_dpm_sample" : "dhw_guided_ddim_sample";
   if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
   int rc = guide_check_front(h, fn, text2, style2, out, B, L, Lt, lens);
   if (rc) return rc;
   char msg[160];
   if (ddim_check_levels(T, levels, S, msg, sizeof msg)) return fail(h, DHW_ERR_ARG, "%s: %s", fn, msg);
+  std::vector<DpmCoef> table;
+  if (dpm && (rc = dpm_check_table(h, fn, T, levels, S, *order, table))) return rc;
   if ((rc = guide_check_back(h, fn, scale, B, L))) return rc;
   if (((uintptr_t)latent | (uintptr_t)latent_out) & 7)
     return fail(h, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)latent & 7) ? "latent" : "latent_out");
 
   EagerCall ec;
   if ((rc = guide_begin(h, B, L, Lt, lens, scale, hip_stream, &ec))) return rc;
+  if (dpm) {
+    if ((rc = ensure_hist(h)) || (rc = step_start(h, ec, 2, latent, 2, B, L, seed, first_sample, table[0].c0, latent_out))) return rc;
+    return step_loop(h, ec, 2, STEP_DPM, text2, style2, B, L, Lt, 0, 0, dpm_steps(table), out);
+  }
   const std::vector<DdimCoef> t = ddim_coef_table(schedule_abar(T).data(), levels, S);
   if ((rc = step_start(h, ec, 2, latent, 2, B, L, seed, first_sample, t[0].A, latent_out))) return rc;
   return step_loop(h, ec, 2, GUIDE_DDIM, text2, style2, B, L, Lt, 0, 0, ddim_steps(t, S), out);
@@ -320,6 +393,62 @@ int update_impl_guide(int kind, const float* base, const float* eps2, const floa
   return 0;
 }
 
+// ---------------------------------------------------------------- the multistep solver's handle-less entries
+int coefs_impl_dpm(int T, const int32_t* levels, int S, int order, float* out) {
+  const char* fn = "dhw_dpm_coefs";
+  char msg[160];
+  if (ddim_check_levels(T, levels, S, msg, sizeof msg) || solver_check_order(order, msg, sizeof msg)) return fail(nullptr, DHW_ERR_ARG, "%s: %s", fn, msg);
+  if (!out) return fail(nullptr, DHW_ERR_ARG, "%s: null pointer (out)", fn);
+  std::vector<DpmCoef> table;
+  if (dpm_coef_table(schedule_abar(T).data(), levels, S, order, table, msg, sizeof msg)) return fail(nullptr, DHW_ERR_ARG, "%s: %s", fn, msg);
+  for (int j = 0; j < S; ++j) dpm_row_pack(table[(size_t)j], out + (size_t)j * DPM_ROW);
+  return 0;
+}
+
+int update_impl_dpm(const float* base, const float* eps, const float* pen, const int32_t* lens, const float* scale, float* hist, int B, int L, const float* coef,
+                    float* out, float* out3, void* hip_stream) {
+  const char* fn = "dhw_dpm_update";
+  const int halves = scale ? 2 : 1;
+  if (B < 1 || L < 1 || (long long)halves * B * L > 0x7fffffffLL)
+    return fail(nullptr, DHW_ERR_ARG, "%s: shape out of range: B=%d L=%d (both >= 1, B * L below 2^31, 2 * B * L with a scale)", fn, B, L);
+  if (!base || !eps || !hist || !coef)
+    return fail(nullptr, DHW_ERR_ARG, "%s: null pointer (%s)", fn, !base ? "base" : !eps ? "eps" : !hist ? "hist" : "coef");
+  if (!out && !out3) return fail(nullptr, DHW_ERR_ARG, "%s: null pointer (out and out3: one of them is needed)", fn);
+  if (out3 && !pen) return fail(nullptr, DHW_ERR_ARG, "%s: null pointer (pen: out3 takes its third column from it)", fn);
+  DpmCoef c{};
+  char msg[96];
+  if (dpm_row_unpack(coef, c, msg, sizeof msg)) return fail(nullptr, DHW_ERR_ARG, "%s: %s", fn, msg);
+  if (((uintptr_t)base | (uintptr_t)eps | (uintptr_t)hist | (uintptr_t)out) & 7)
+    return fail(nullptr, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)base & 7) ? "base" : ((uintptr_t)eps & 7) ? "eps" : ((uintptr_t)hist & 7) ? "hist" : "out");
+  if (((uintptr_t)lens | (uintptr_t)scale | (uintptr_t)pen | (uintptr_t)out3) & 3)
+    return fail(nullptr, DHW_ERR_ARG, "%s: lens, scale, pen and out3 must be 4-byte aligned", fn);
+  DpmParams p{};
+  p.base = base;
+  p.eps = eps;
+  p.pen = pen;
+  p.lens = lens;
+  p.scale = scale;
+  p.hist = hist;
+  p.rows = (long)B * L;
+  p.B = B;
+  p.L = L;
+  p.halves = halves;
+  p.second = c.kind == DPM_SECOND;
+  p.c0 = c.c0;
+  p.c1 = c.c1;
+  p.c2 = c.c2;
+  p.c3 = c.c3;
+  p.k0 = c.k0;
+  p.k1 = c.k1;
+  p.c4 = c.c4;
+  p.c5 = c.c5;
+  p.out = out;
+  p.out3 = out3;
+  const hipError_t e = launch_dpm_update(p, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return fail(nullptr, DHW_ERR_HIP, "%s: launch: %s", fn, hipGetErrorString(e));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -354,6 +483,30 @@ int dhw_guided_sample(dhw_handle* h, const int64_t* text2, const float* style2, 
 int dhw_guide_update(int kind, const float* base, const float* eps2, const float* pen, const int32_t* lens, const float* scale, const float* z, int B, int L, float c0,
                      float c1, float c2, float c3, float* out, float* out3, void* hip_stream) {
   DHW_GUARD((dhw_handle*)nullptr, "dhw_guide_update", int, { return update_impl_guide(kind, base, eps2, pen, lens, scale, z, B, L, c0, c1, c2, c3, out, out3, hip_stream); });
+}
+
+int dhw_dpm_coefs(int T, const int32_t* levels, int S, int order, float* out) {
+  DHW_GUARD((dhw_handle*)nullptr, "dhw_dpm_coefs", int, { return coefs_impl_dpm(T, levels, S, order, out); });
+}
+
+int dhw_dpm_update(const float* base, const float* eps, const float* pen, const int32_t* lens, const float* scale, float* hist, int B, int L, const float* coef,
+                   float* out, float* out3, void* hip_stream) {
+  DHW_GUARD((dhw_handle*)nullptr, "dhw_dpm_update", int, { return update_impl_dpm(base, eps, pen, lens, scale, hist, B, L, coef, out, out3, hip_stream); });
+}
+
+int dhw_dpm_sample(dhw_handle* h, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens, int T, const int32_t* levels,
+                   int S, int order, const float* latent, uint64_t seed, int64_t first_sample, float* latent_out, float* out, void* hip_stream) {
+  DHW_GUARD(h, "dhw_dpm_sample", int, {
+    return sample_impl_ddim(h, text, style, B, L, Lt, lens, T, levels, S, latent, seed, first_sample, latent_out, out, hip_stream, &order);
+  });
+}
+
+int dhw_guided_dpm_sample(dhw_handle* h, const int64_t* text2, const float* style2, int B, int L, int Lt, const int32_t* lens, int T, const int32_t* levels,
+                          int S, int order, const float* scale, const float* latent, uint64_t seed, int64_t first_sample, float* out, float* latent_out,
+                          void* hip_stream) {
+  DHW_GUARD(h, "dhw_guided_dpm_sample", int, {
+    return sample_impl_guided_ddim(h, text2, style2, B, L, Lt, lens, T, levels, S, scale, latent, seed, first_sample, out, latent_out, hip_stream, &order);
+  });
 }
 
 }  // extern "C"

@@ -269,12 +269,14 @@ def restyle(strokes: torch.Tensor, text: torch.Tensor, style_vector: torch.Tenso
 
 
 def infer(prompt: str, style_vector: torch.Tensor, model: DiffusionModel, diffusion_mode: str = "new", T: int = 60,
-          seed: int = 0, steps: int | None = None, guidance=None) -> np.ndarray:
+          seed: int = 0, steps: int | None = None, guidance=None, order: int | None = None) -> np.ndarray:
     """Single-prompt convenience wrapper with the reference's front end: tokenise, L = 16 per token rounded up
     to a multiple of 8, sample, return the [L,3] stroke array that the reference hands to ``show_strokes``.
     ``steps``: sample deterministically at that many levels instead (``sample_ddim``; ``diffusion_mode`` then plays no part).
-    ``guidance``: a classifier-free guidance scale against ``null_condition`` (``sample`` / ``sample_ddim``); None: unguided."""
+    ``guidance``: a classifier-free guidance scale against ``null_condition`` (``sample`` / ``sample_ddim``); None: unguided.
+    ``order`` (with ``steps``): ``sample_ddim``'s solver order, 1 or 2."""
     guided = _guided_kw(guidance, 1, 1)
+    guided.update(_order_kw(order, steps))
     ids = Tokenizer().encode(prompt)
     text = torch.tensor([ids], dtype=torch.int64)
     if steps is not None:
@@ -370,6 +372,23 @@ def _check_ddim_levels(levels, steps, T) -> list:
     return lv
 
 
+def _check_order(order) -> int:
+    """``order`` of ``sample_ddim``: 1 (DDIM) or 2 (second-order multistep)."""
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or int(order) not in (1, 2):
+        raise ValueError(f"order = {order!r} must be 1 (DDIM) or 2 (second-order multistep)")
+    return int(order)
+
+
+def _order_kw(order, steps) -> dict:
+    """What a front end passes on for its ``order`` argument: nothing for None (the calls stay as they are, argument for
+    argument), else {"order": order}, which needs ``steps``."""
+    if order is None:
+        return {}
+    if steps is None:
+        raise ValueError("order belongs to deterministic sampling: pass steps as well")
+    return {"order": _check_order(order)}
+
+
 def _check_ddim_common(text, style_vector, B: int, lengths, L):
     if not isinstance(text, torch.Tensor) or text.dim() != 2 or text.shape[0] != B or text.dtype.is_floating_point:
         raise ValueError(f"text must be an integer tensor [B = {B}, Lt], got {tuple(text.shape) if isinstance(text, torch.Tensor) else type(text).__name__}")
@@ -393,7 +412,7 @@ def _check_eager_common(L, lens, Lt: int, seed, first_sample, levels_check):
 def sample_ddim(model: DiffusionModel, text: torch.Tensor, style_vector: torch.Tensor, L: int | None = None, T: int = 60,
                 steps: int | None = None, levels=None, latent: torch.Tensor | None = None, seed: int = 0, first_sample: int = 0,
                 lengths=None, return_latent: bool = False, guidance=None, uncond_text: torch.Tensor | None = None,
-                uncond_style: torch.Tensor | None = None):
+                uncond_style: torch.Tensor | None = None, order: int = 1):
     """Deterministic (DDIM, eta = 0) sampling over a sub-sequence of the schedule (include/dhw.h dhw_ddim_sample): one
     denoiser call per level and no noise after the start, so the line is a function of its start latent alone.
 
@@ -404,7 +423,13 @@ def sample_ddim(model: DiffusionModel, text: torch.Tensor, style_vector: torch.T
     with ``return_latent=True``.  The calls launch eagerly; they leave ``sample``'s cached graphs and generator state alone.
 
     ``guidance`` (a scale, or B of them; ``uncond_text`` / ``uncond_style`` as in ``sample``): classifier-free guidance
-    (include/dhw.h dhw_guided_ddim_sample) over the same levels, from the same latent; ``None`` is today's call."""
+    (include/dhw.h dhw_guided_ddim_sample) over the same levels, from the same latent; ``None`` is today's call.
+
+    ``order``: 1 (today's call) or 2: the second-order multistep solver (DPM-Solver++ 2M; include/dhw.h dhw_dpm_sample /
+    dhw_guided_dpm_sample) over the same levels with the same number of denoiser calls; every step between the
+    first and the last also uses the previous step's x0 estimate.  It works with ``guidance``, ``lengths``, ``latent`` and
+    ``return_latent``; with one or two levels it returns order 1's bits."""
+    order = _check_order(order)
     if not isinstance(text, torch.Tensor) or text.dim() != 2:
         raise ValueError("text must be an integer tensor [B, Lt]")
     if guidance is None and (uncond_text is not None or uncond_style is not None):
@@ -426,10 +451,14 @@ def sample_ddim(model: DiffusionModel, text: torch.Tensor, style_vector: torch.T
         t, sv, lat = c.to(text2, torch.int64), c.to(style2), c.to(latent)
         lat_out, out = c.empty((B, L, 2), wanted=return_latent), c.empty((B, L, 3))
         head = (t.data_ptr(), sv.data_ptr(), B, L, Lt, c.lens(lens), T, c.lens(lv), len(lv))
-        if scale is None:
-            c.run("dhw_ddim_sample", *head, c.ptr(lat), seed, first_sample, c.ptr(lat_out), out.data_ptr())
+        if order != 1:
+            head, ddim, guided = head + (order,), "dhw_dpm_sample", "dhw_guided_dpm_sample"
         else:
-            c.run("dhw_guided_ddim_sample", *head, _scale_array(scale), c.ptr(lat), seed, first_sample, out.data_ptr(), c.ptr(lat_out))
+            ddim, guided = "dhw_ddim_sample", "dhw_guided_ddim_sample"
+        if scale is None:
+            c.run(ddim, *head, c.ptr(lat), seed, first_sample, c.ptr(lat_out), out.data_ptr())
+        else:
+            c.run(guided, *head, _scale_array(scale), c.ptr(lat), seed, first_sample, out.data_ptr(), c.ptr(lat_out))
     return (out.to(text.device), lat_out.to(text.device)) if return_latent else out.to(text.device)
 
 
@@ -440,7 +469,8 @@ def invert(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, sty
     ``sample_ddim(latent=invert(x))`` under the same text, style and levels reproduces ``x`` to an error the tests measure;
     under another style or text it rewrites the line reproducibly (``transfer``).  ``iters`` in [1, 8]: fixed-point
     iterations per step (1 = the usual DDIM inversion); the call makes ``len(levels) * iters`` denoiser calls.
-    Returns the latent [B,L,2], 0 past ``lengths[b]``."""
+    Returns the latent [B,L,2], 0 past ``lengths[b]``.  There is no ``order``: a multistep step uses the step before it, so it
+    has no one-step inverse; the inversion is of the first-order process (``sample_ddim(order=1)``)."""
     B, L = _check_strokes(strokes)
     if L < 8 or L % 8:
         raise ValueError(f"strokes: L = {L} must be a multiple of 8, at least 8")
@@ -459,7 +489,8 @@ def transfer(strokes: torch.Tensor, text: torch.Tensor, style_from: torch.Tensor
              lengths=None, text_to: torch.Tensor | None = None, **kw) -> torch.Tensor:
     """Rewrite an existing line reproducibly: invert ``strokes`` under ``(text, style_from)``, then ``sample_ddim`` that latent
     under ``(text_to or text, style_to)``.  Keywords: T, steps, levels (both halves), iters (the inversion).  Returns [B,L,3],
-    the pen from the last denoiser call.  Unlike ``restyle`` nothing is random and no strength is chosen."""
+    the pen from the last denoiser call.  Unlike ``restyle`` nothing is random and no strength is chosen.  There is no ``order``:
+    both halves are the first-order process, because a multistep step has no one-step inverse (``invert``)."""
     iters = kw.pop("iters", 1)
     extra = set(kw) - {"T", "steps", "levels"}
     if extra:
@@ -647,7 +678,8 @@ def _encode_batch(who: str, prompts, style_vector):
 
 
 def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diffusion_mode: str = "new", T: int = 60,
-                seed: int = 0, first_sample: int = 0, candidates: int = 1, levels=None, steps: int | None = None, guidance=None) -> list:
+                seed: int = 0, first_sample: int = 0, candidates: int = 1, levels=None, steps: int | None = None, guidance=None,
+                order: int | None = None) -> list:
     """Many prompts in ONE ragged sampler call: prompt i is tokenised, gets its own ``L_i = stroke_length(n_i)`` and is padded
     with token 0 to the longest prompt.  ``style_vector`` is [1,S,1280] (one writer for every prompt) or [B,S,1280].  Returns a
     list of [L_i, 3] arrays; entry i equals ``sample(model, text_i, style_i, L=L_i, seed=seed, first_sample=first_sample + i)``.
@@ -658,12 +690,13 @@ def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diff
     (ties: the lower j).
 
     ``steps``: every line is sampled deterministically at that many levels (``sample_ddim`` with ``ddim_levels(T, steps)``)
-    instead; ``diffusion_mode`` then plays no part.
+    instead; ``diffusion_mode`` then plays no part.  ``order`` (with ``steps``): ``sample_ddim``'s solver order, 1 or 2.
 
     ``guidance``: a classifier-free guidance scale, or one per prompt, against ``null_condition`` (each call is then one forward
     of 2B rows per step); refused together with ``candidates > 1``."""
     candidates = _check_candidates(candidates)
     guided = _guided_kw(guidance, candidates)
+    solver = _order_kw(order, steps)
     if steps is None:
         def draw(tx, st, ln, first):
             return sample(model, tx, st, L=max(lens), T=T, diffusion_mode=diffusion_mode, seed=seed, first_sample=first, lengths=ln, **guided)
@@ -671,7 +704,7 @@ def infer_batch(prompts, style_vector: torch.Tensor, model: DiffusionModel, diff
         ddim = ddim_levels(T, steps)
 
         def draw(tx, st, ln, first):
-            return sample_ddim(model, tx, st, L=max(lens), T=T, levels=ddim, seed=seed, first_sample=first, lengths=ln, **guided)
+            return sample_ddim(model, tx, st, L=max(lens), T=T, levels=ddim, seed=seed, first_sample=first, lengths=ln, **guided, **solver)
     text, lens, sv = _encode_batch("infer_batch", prompts, style_vector)
     B = len(lens)
     if candidates == 1:
@@ -787,17 +820,19 @@ def _check_renderer(renderer: str) -> None:
 def infer_file(prompt: str, source, config_path: str | None = None, checkpoint_path: str | None = None,
                experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *, precision: str = "bf16",
                seed: int = 0, render: bool = True, style_weights: str | None = None, renderer: str = "matplotlib",
-               candidates: int = 1, steps: int | None = None, guidance=None) -> np.ndarray:
+               candidates: int = 1, steps: int | None = None, guidance=None, order: int | None = None) -> np.ndarray:
     """The reference's command-line entry (inference.py:19-27) around this build's sampler: resolve config / checkpoint
     (directly or inside ``experiment_path``), load the model, sample one prompt, write ``./<output>.png`` (``renderer``:
     "matplotlib" = the reference's figure, "gpu" = the 96-row grey line image of ``render_strokes``).
     ``candidates = N > 1``: the best of N samples by ``score`` (``infer_batch``).  ``steps``: deterministic sampling at that
-    many levels (``sample_ddim``).  ``guidance``: a classifier-free guidance scale (``sample``).  Returns the [L,3] strokes."""
+    many levels (``sample_ddim``), ``order`` its solver order.  ``guidance``: a classifier-free guidance scale (``sample``).
+    Returns the [L,3] strokes."""
     from .checkpoint import load_model
 
     _check_renderer(renderer)
     candidates = _check_candidates(candidates)
     ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}   # (no steps: today's calls, argument for argument)
+    ddim.update(_order_kw(order, steps))
     ddim.update(_guided_kw(guidance, candidates, 1))
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
@@ -856,16 +891,18 @@ def _open_lines(who: str, prompts, strokes_path, source, config_path, checkpoint
 def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint_path: str | None = None,
                      experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
                      precision: str = "bf16", seed: int = 0, render: bool = True, style_weights: str | None = None,
-                     renderer: str = "matplotlib", candidates: int = 1, steps: int | None = None, guidance=None) -> list:
+                     renderer: str = "matplotlib", candidates: int = 1, steps: int | None = None, guidance=None,
+                     order: int | None = None) -> list:
     """``infer_file`` for many prompts of one writer: one ragged sampler call (``infer_batch``), ``./<output>_<i>.png`` per
     prompt (``renderer="gpu"``: every line rasterised in one ``render_strokes`` call).  ``candidates = N > 1``: every line is
-    the best of N samples by ``score``.  ``steps``: deterministic sampling at that many levels (``sample_ddim``).  ``guidance``: a
+    the best of N samples by ``score``.  ``steps`` / ``order``: deterministic sampling at that many levels (``sample_ddim``).  ``guidance``: a
     classifier-free guidance scale, or one per prompt (``infer_batch``).  Returns the list of [L_i, 3] strokes."""
     from .checkpoint import load_model
 
     _check_renderer(renderer)
     candidates = _check_candidates(candidates)
     ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}
+    ddim.update(_order_kw(order, steps))
     prompts = list(prompts)
     ddim.update(_guided_kw(guidance, candidates, max(1, len(prompts))))
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
@@ -916,7 +953,7 @@ def wrap_text(text: str, max_chars: int = 40):
 
 def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, max_chars: int = 40, diffusion_mode: str = "new",
                T: int = 60, seed: int = 0, first_sample: int = 0, candidates: int = 1, levels=None, steps: int | None = None,
-               guidance=None, pages=None, height: int = 1980, width: int = 1400, lines_per_page: int = 20, margin_left: float = 70.0,
+               guidance=None, order: int | None = None, pages=None, height: int = 1980, width: int = 1400, lines_per_page: int = 20, margin_left: float = 70.0,
                margin_top: float = 70.0, pitch: float = 92.0, line_width: float = 2.0, scale=None):
     """Write a text: ``wrap_text`` to lines, ``infer_batch`` for their strokes, ``render_page`` onto pages at one shared scale.
 
@@ -924,7 +961,7 @@ def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, 
     (``max_B``): the round that starts at line i0 is ``infer_batch(..., first_sample=first_sample + i0 * candidates)``, so with
     ``candidates = 1`` line i uses generator index ``first_sample + i`` however the rounds fall, and the rounds of a best-of-N
     run never share an index.  ``guidance`` (one scale for every line): a guided round is one forward of twice its lines, so the
-    rounds are half as long.  The sampler arguments are ``infer_batch``'s, the page arguments ``render_page``'s; all are
+    rounds are half as long.  ``order`` (with ``steps``): ``sample_ddim``'s solver order.  The sampler arguments are ``infer_batch``'s, the page arguments ``render_page``'s; all are
     checked, with ValueError, before a device is touched.
 
     Returns (pages f32 [P,1,height,width] on the GPU, the list of [L_i,3] stroke arrays, one per wrapped line)."""
@@ -938,6 +975,7 @@ def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, 
     first_sample = _check_int("first_sample", first_sample, 0)
     if steps is not None:
         ddim_levels(T, steps)
+    solver = _order_kw(order, steps)
     if candidates > 1:
         _check_levels(levels, T)
     guided = _guided_kw(guidance, candidates, 1)
@@ -955,7 +993,7 @@ def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, 
     strokes = []
     for i0 in range(0, len(lines), cap):
         strokes += infer_batch(lines[i0:i0 + cap], sv, model, diffusion_mode=diffusion_mode, T=T, seed=seed,
-                               first_sample=first_sample + i0 * candidates, candidates=candidates, levels=levels, steps=steps, **guided)
+                               first_sample=first_sample + i0 * candidates, candidates=candidates, levels=levels, steps=steps, **guided, **solver)
     out, _, _ = render_page(pad_strokes(strokes), [len(s) for s in strokes], slots, pages=pages, height=height, width=width,
                             lines_per_page=lines_per_page, margin_left=margin_left, margin_top=margin_top, pitch=pitch,
                             line_width=line_width, scale=scale)
@@ -965,7 +1003,7 @@ def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, 
 def write_page_file(text: str, source, config_path: str | None = None, checkpoint_path: str | None = None,
                     experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
                     precision: str = "bf16", seed: int = 0, style_weights: str | None = None, candidates: int = 1,
-                    steps: int | None = None, guidance=None, **page_kwargs) -> list:
+                    steps: int | None = None, guidance=None, order: int | None = None, **page_kwargs) -> list:
     """``infer.py --page-file``: resolve config / checkpoint as ``infer_file`` does, ``write_page`` the text in the hand of
     ``source`` and save ``./<output>_p<k>.png`` per page (``vis.save_page_png``).  Returns the list of [L_i,3] strokes."""
     from .checkpoint import load_model
@@ -976,6 +1014,7 @@ def write_page_file(text: str, source, config_path: str | None = None, checkpoin
         raise ValueError("write_page_file: the text holds no word")
     candidates = _check_candidates(candidates)
     ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}
+    ddim.update(_order_kw(order, steps))
     ddim.update(_guided_kw(guidance, candidates, 1))
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)

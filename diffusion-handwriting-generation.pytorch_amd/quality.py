@@ -419,7 +419,7 @@ def line_features(strokes, extractor, lengths=None, batch: int = 32):
 
 
 _SAMPLE_KW = {"T", "diffusion_mode", "guidance"}
-_DDIM_KW = {"T", "steps", "levels", "guidance"}
+_DDIM_KW = {"T", "steps", "levels", "guidance", "order"}
 
 
 def _sampler_of(sampler: dict, who: str = "sample_quality"):
@@ -519,7 +519,7 @@ def sample_quality(model, data, extractor, n=None, batch: int = 32, seed: int = 
     ``data``: the dict ``train.py --val`` reads, {"strokes" [N,L,3], "text" [N,Lt], "style" [N,S,1280]}.  The first ``n`` rows
     (default all) are used.  Real statistics come from ``data["strokes"]``, or from ``real`` (a ``FeatureStats``, e.g. loaded from
     a file) when given.  Generated lines come from ``sample`` (keywords T, diffusion_mode, guidance), or from ``sample_ddim`` when
-    ``steps=`` or ``levels=`` is among the keywords, with the rows' text and style at L = data["strokes"].shape[1], ``batch`` rows
+    ``steps=`` or ``levels=`` is among the keywords (then also ``order=``, its solver order), with the rows' text and style at L = data["strokes"].shape[1], ``batch`` rows
     per call and ``first_sample`` = the row index, so the result does not depend on ``batch``.  ``timings`` (a dict): filled with
     the seconds spent in sampling, rendering + features, moments and the host eigen-decompositions (synchronises per stage).
     Returns (fd, real_stats, generated_stats)."""

@@ -352,6 +352,60 @@ int dhw_guide_update(int kind, const float* base, const float* eps2, const float
                      const float* z, int B, int L, float c0, float c1, float c2, float c3, float* out, float* out3,
                      void* hip_stream);
 
+/* Second-order multistep sampling (DPM-Solver++ 2M) over the levels of dhw_ddim_sample: the same number of denoiser calls, each
+ * step between the first and the last also using the x0 estimate the previous step left behind.
+ *
+ * Setup.  levels, a_j, A_j = sqrtf(a_j), B_j = sqrtf(1 - a_j) and (A_S, B_S) = (1, 0) are exactly dhw_ddim_sample's.  order is 1 or
+ * 2.  Step j (0 <= j < S) moves the state from level j to level j + 1 using (e_j, q_j), the forward of x_j at sigma = A_j (guided:
+ * e_j is dhw_guided_ddim_sample's combination of the two halves).  Every step first computes, with the first three operations of U,
+ *    x0_j = fdiv(fsub(x_j, fmul(B_j, e_j)), A_j).
+ *
+ * First-order steps: j = 0, j = S - 1 (it goes to B = 0, where log-SNR is infinite), and every step when order = 1.
+ *    x_{j+1} = U(x_j, e_j; A_j, B_j, A_{j+1}, B_{j+1}): the bits of dhw_ddim_update.  Then hist <- x0_j.
+ *
+ * Second-order steps: 0 < j < S - 1 when order = 2.  On the HOST, in double from the fp32 A, B of the table, each result rounded
+ * once to fp32:
+ *    lambda_j = log(A_j / B_j),  h = lambda_{j+1} - lambda_j,  r = (lambda_j - lambda_{j-1}) / h,
+ *    k1 = 1 / (2 r),  k0 = 1 + k1,  c4 = B_{j+1} / B_j,  c5 = -A_{j+1} expm1(-h).
+ * On the device, nine fp32 operations per coordinate, each rounded to nearest, nothing contracted:
+ *    m = B_j e;  d = x - m;  x0 = d / A_j;  p = k0 x0;  q = k1 hist;  D = p - q;  s = c4 x;  n = c5 D;  x' = s + n.
+ * Then hist <- x0.  (In exact arithmetic: x' = (B_{j+1}/B_j) x + A_{j+1} (1 - e^{-h}) ((1 + 1/(2r)) x0_j - (1/(2r)) x0_{j-1}).)
+ *
+ * Edge cases.  A table whose h or r is not finite and positive (levels whose fp32 a_j coincide or reach 1) is refused with
+ * DHW_ERR_ARG before any HIP call.  Step 0 never reads hist.  Rows at or past lens[b] are never read, in base, eps or hist; they are
+ * written as 0 in out and hist.  With S <= 2 every step is first order: order = 2 then returns dhw_ddim_sample's bits.
+ *
+ * dhw_dpm_coefs
+ *    The table the library uses, on the host, no handle: out is a HOST f32 [S][9] = (kind, c0, c1, c2, c3, k0, k1, c4, c5) per step:
+ *    kind 1 (first order) or 2 (second order); (c0, c1, c2, c3) = (A_j, B_j, A_{j+1}, B_{j+1}) in every row; (k0, k1, c4, c5) as
+ *    above in a second-order row and 0 in a first-order one.  T, levels, S as dhw_ddim_sample; errors through dhw_last_error(NULL).
+ *
+ * dhw_dpm_update
+ *    The one step kernel on given device arrays, so that it can be pinned bit for bit on its own.  coef: HOST f32 [9], a row of
+ *    dhw_dpm_coefs' layout (coef[0] must be 1 or 2).  base, eps, out device f32 [B,L,2] (out may be base); hist device f32 [B,L,2],
+ *    read (kind 2 only) and written in place; lens DEVICE int32 [B] or NULL, any 0 <= n.  scale DEVICE f32 [B] or NULL: with it the
+ *    step is the guided one: eps is [2B,L,2], e = the combination of eps[r] and eps[r + B L] at scale[b], out is [2B,L,2] and rows r
+ *    and r + B L both receive x'; hist stays [B,L,2].  out3 f32 [B,L,3] or NULL = (x', pen[r]); pen f32 [B,L] is read with out3 only.
+ *    One of out / out3 is needed.  base, eps, hist, out 8-byte aligned.  No handle: errors through dhw_last_error(NULL).  B, L >= 1,
+ *    B L (2 B L with a scale) < 2^31.
+ *
+ * dhw_dpm_sample, dhw_guided_dpm_sample
+ *    The argument lists, the start, the output, the checks, the determinism and the side effects of dhw_ddim_sample and
+ *    dhw_guided_ddim_sample, plus order (1 or 2, checked behind the levels; then the table's h and r).  Every check answers before
+ *    dhw_finalize.  hist is a fifth buffer [max_B max_L, 2] of the eager entries' scratch set, allocated at the first such call and
+ *    never moved; every call writes it at step 0 before any step reads it, so nothing carries over from call to call.  The
+ *    coefficients travel to the kernel by value; no graph is used.  Nothing of the sampler's is touched.  The entries work on a
+ *    handle created with DHW_PERSIST=1. */
+int dhw_dpm_coefs(int T, const int32_t* levels, int S, int order, float* out);
+int dhw_dpm_update(const float* base, const float* eps, const float* pen, const int32_t* lens, const float* scale, float* hist,
+                   int B, int L, const float* coef, float* out, float* out3, void* hip_stream);
+int dhw_dpm_sample(dhw_handle*, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens,
+                   int T, const int32_t* levels, int S, int order, const float* latent, uint64_t seed, int64_t first_sample,
+                   float* latent_out, float* out, void* hip_stream);
+int dhw_guided_dpm_sample(dhw_handle*, const int64_t* text2, const float* style2, int B, int L, int Lt, const int32_t* lens,
+                          int T, const int32_t* levels, int S, int order, const float* scale, const float* latent, uint64_t seed,
+                          int64_t first_sample, float* out, float* latent_out, void* hip_stream);
+
 /* Stroke rasteriser: sampled strokes -> grey-level line images in the layout dhw_style_forward consumes (ink
  * left-aligned, white to the right).  No handle: errors are read through dhw_last_error(NULL).  The call allocates
  * nothing, synchronises nothing and can be captured into a graph.  All argument checks run before the first HIP call

@@ -31,6 +31,7 @@ Where each character of saved lines sits, from the model's cross attention ("lin
 Deterministic sampling at N of the schedule's levels (DDIM, eta = 0: N denoiser calls instead of 60, no noise after the start):
 
     python infer.py "Follow the White Rabbit" style.npy --experiment-path data/best_exp --steps 20
+    python infer.py "Follow the White Rabbit" style.npy --experiment-path data/best_exp --steps 10 --order 2
 
 Classifier-free guidance (a checkpoint trained with `train.py --cond-drop`; works with or without --steps, --prompts-file, --page-file):
 
@@ -69,6 +70,8 @@ def main(argv=None):
                                                    "cross attention assigns to every character and write <output>_align.npz; writes no images")
     ap.add_argument("--steps", type=int, default=None, metavar="N", help="sample deterministically (DDIM, eta = 0) at N evenly spread levels of the "
                                                                          "schedule instead of the stochastic reverse process over all of them")
+    ap.add_argument("--order", type=int, default=None, choices=(1, 2), help="with --steps: 1 = DDIM, 2 = the second-order multistep solver (DPM-Solver++ 2M) "
+                                                                          "over the same levels, the same number of denoiser calls")
     ap.add_argument("--guidance", type=float, default=None, metavar="W", help="classifier-free guidance scale (1 = unguided, larger = closer to the prompt "
                                                                               "and the writer); needs a checkpoint trained with train.py --cond-drop")
     ap.add_argument("--page-file", metavar="TXT", help="a text to write as pages: wrapped to lines, every line sampled, all lines composed on the "
@@ -92,6 +95,8 @@ def main(argv=None):
         ap.error("--candidates belongs to sampling, not to --restyle")
     if a.steps is not None and a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.order is not None and a.steps is None:
+        ap.error("--order chooses the solver of deterministic sampling: it needs --steps")
     if a.steps is not None and (a.score or a.align or a.restyle):
         ap.error("--steps belongs to sampling: it goes with neither --score, --align nor --restyle")
 
@@ -122,6 +127,8 @@ def main(argv=None):
     cand = dict(candidates=a.candidates) if a.candidates > 1 else {}   # (candidates = 1: today's calls, argument for argument)
     if a.steps is not None:
         cand["steps"] = a.steps
+    if a.order is not None:
+        cand["order"] = a.order
     if a.guidance is not None:
         cand["guidance"] = a.guidance
 

@@ -3,10 +3,10 @@
 rows, in the StyleExtractor's feature space (dhg_amd.sample_quality).
 
     python tools/eval_samples.py --data val.pt --experiment-path runs/exp1 --weights mobilenet_v2.pth \\
-        [--n 1024] [--guidance 2.5] [--steps 20] [--mode new] [--real-stats real.npz] [--save-real-stats real.npz] [--metrics [--k 3]] [--dtw]
+        [--n 1024] [--guidance 2.5] [--steps 20 [--order 1 2]] [--mode new] [--real-stats real.npz] [--save-real-stats real.npz] [--metrics [--k 3]] [--dtw]
 
---data is the file train.py --val reads: {"strokes" [N,L,3], "text" [N,Lt], "style" [N,14,1280]}.  Several values of --guidance
-or --steps give one line per combination; the real statistics are computed once (or read from --real-stats).  One line per run:
+--data is the file train.py --val reads: {"strokes" [N,L,3], "text" [N,Lt], "style" [N,14,1280]}.  Several values of --guidance,
+--steps or --order (sample_ddim's solver order) give one line per combination; the real statistics are computed once (or read from --real-stats).  One line per run:
 
     FD <value> | n <count> | sampler <sample|ddim> | T .. | steps .. | guidance .. | mode .. | seconds: sample .. features .. moments .. eig ..
 
@@ -64,6 +64,7 @@ def parser():
     ap.add_argument("--T", type=int, default=60)
     ap.add_argument("--guidance", type=float, nargs="*", default=[None])
     ap.add_argument("--steps", type=int, nargs="*", default=[None])
+    ap.add_argument("--order", type=int, nargs="*", default=[None], choices=(1, 2), help="solver order of sample_ddim (needs --steps): one setting per value")
     ap.add_argument("--mode", default=None, choices=("new", "standard"))
     ap.add_argument("--real-stats")
     ap.add_argument("--save-real-stats")
@@ -83,6 +84,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.mode is not None and any(s is not None for s in a.steps):
         ap.error("--mode belongs to the ancestral sampler: it cannot be combined with --steps")
+    if any(o is not None for o in a.order) and any(s is None for s in a.steps):
+        ap.error("--order belongs to deterministic sampling: it needs --steps")
     if a.synthetic_rows is not None and not a.synthetic:
         ap.error("--synthetic-rows needs --synthetic")
     if (a.metrics or a.dtw) and a.real_stats:
@@ -114,35 +117,38 @@ def main(argv=None):
     real = dhg_amd.FeatureStats.load(a.real_stats) if a.real_stats else None
     real_pair = None   # --metrics: (statistics, rows) of the real lines, computed by the first run
     runs = []
-    for steps in a.steps:
-        for guidance in a.guidance:
-            kw = {"T": a.T}
-            if steps is not None:
-                kw["steps"] = steps
-            elif a.mode is not None:
-                kw["diffusion_mode"] = a.mode
-            if guidance is not None:
-                kw["guidance"] = guidance
-            sec = {}
-            if a.metrics or a.dtw:
-                if a.dtw:
-                    kw["dtw"] = True
-                m = dhg_amd.sample_metrics(model, data, extractor, n=a.n, batch=a.batch, seed=a.seed, k=a.k, real=real_pair, timings=sec, **kw)
-                fd, real, gen, real_pair = m["fd"], m["real_stats"], m["gen_stats"], (m["real_stats"], m["real_set"])
-            else:
-                fd, real, gen = dhg_amd.sample_quality(model, data, extractor, n=a.n, batch=a.batch, seed=a.seed, real=real, timings=sec, **kw)
-            run = {"fd": fd, "n": gen.count, "n_real": real.count, "sampler": "ddim" if steps is not None else "sample", "T": a.T, "steps": steps,
-                   "guidance": guidance, "mode": None if steps is not None else (a.mode or "new"), "seconds": {k: round(v, 4) for k, v in sec.items()}}
-            runs.append(run)
-            print(f"FD {fd:.6g} | n {gen.count} | sampler {run['sampler']} | T {a.T} | steps {steps} | guidance {guidance} | mode {run['mode']} | "
-                  "seconds: " + " ".join(f"{k} {v:.3f}" for k, v in sec.items()), flush=True)
-            if a.metrics:
-                run.update({name: m[name] for name in ("precision", "recall", "density", "coverage", "kid", "k")})
-                print(f"PR precision {m['precision']:.4f} | recall {m['recall']:.4f} | density {m['density']:.4f} | coverage {m['coverage']:.4f} | "
-                      f"KID {m['kid']:.6g} | k {m['k']}", flush=True)
+    for steps, order, guidance in ((s, o, g) for s in a.steps for o in a.order for g in a.guidance):
+        kw = {"T": a.T}
+        if steps is not None:
+            kw["steps"] = steps
+        elif a.mode is not None:
+            kw["diffusion_mode"] = a.mode
+        if order is not None:
+            kw["order"] = order
+        if guidance is not None:
+            kw["guidance"] = guidance
+        sec = {}
+        if a.metrics or a.dtw:
             if a.dtw:
-                run.update({name: m[name] for name in ("dtw_paired", "dtw_nearest", "dtw_self")})
-                print(f"DTW paired {m['dtw_paired']:.6g} | nearest {m['dtw_nearest']:.6g} | self {m['dtw_self']:.6g}", flush=True)
+                kw["dtw"] = True
+            m = dhg_amd.sample_metrics(model, data, extractor, n=a.n, batch=a.batch, seed=a.seed, k=a.k, real=real_pair, timings=sec, **kw)
+            fd, real, gen, real_pair = m["fd"], m["real_stats"], m["gen_stats"], (m["real_stats"], m["real_set"])
+        else:
+            fd, real, gen = dhg_amd.sample_quality(model, data, extractor, n=a.n, batch=a.batch, seed=a.seed, real=real, timings=sec, **kw)
+        run = {"fd": fd, "n": gen.count, "n_real": real.count, "sampler": "ddim" if steps is not None else "sample", "T": a.T, "steps": steps,
+               "guidance": guidance, "mode": None if steps is not None else (a.mode or "new"), "seconds": {k: round(v, 4) for k, v in sec.items()}}
+        if order is not None:
+            run["order"] = order
+        runs.append(run)
+        print(f"FD {fd:.6g} | n {gen.count} | sampler {run['sampler']} | T {a.T} | steps {steps}{'' if order is None else f' | order {order}'} | guidance {guidance} | mode {run['mode']} | "
+              "seconds: " + " ".join(f"{k} {v:.3f}" for k, v in sec.items()), flush=True)
+        if a.metrics:
+            run.update({name: m[name] for name in ("precision", "recall", "density", "coverage", "kid", "k")})
+            print(f"PR precision {m['precision']:.4f} | recall {m['recall']:.4f} | density {m['density']:.4f} | coverage {m['coverage']:.4f} | "
+                  f"KID {m['kid']:.6g} | k {m['k']}", flush=True)
+        if a.dtw:
+            run.update({name: m[name] for name in ("dtw_paired", "dtw_nearest", "dtw_self")})
+            print(f"DTW paired {m['dtw_paired']:.6g} | nearest {m['dtw_nearest']:.6g} | self {m['dtw_self']:.6g}", flush=True)
     if a.save_real_stats:
         real.save(a.save_real_stats)
     if a.json:
