@@ -1,7 +1,8 @@
 // dhw_step_api.cpp — C-ABI of the eager samplers (include/dhw.h): deterministic sampling and inversion (dhw_ddim_sample,
 // dhw_ddim_invert, dhw_ddim_update), classifier-free guided sampling (dhw_guided_ddim_sample,
 // dhw_guided_sample, dhw_guide_update; §33) and the second-order multistep solver over the same levels (dhw_dpm_coefs,
-// dhw_dpm_update, dhw_dpm_sample, dhw_guided_dpm_sample; §40).  A sampling call is step_start, then per step the launches of dhw_forward /
+// dhw_dpm_update, dhw_dpm_sample, dhw_guided_dpm_sample; §40) — one argument block, one kernel and one loop for all of them
+// (§34, §41).  A sampling call is step_start, then per step the launches of dhw_forward /
 // dhw_forward_ragged (sampler/sample.cpp: forward_enqueue) and one step_update (step_loop) — eagerly on the caller's stream.  A
 // guided call runs ONE forward over 2B rows per step: rows [0, B) under the real condition, rows [B, 2B) under the guidance
 // condition, the same x in both.  Nothing here touches h->d_seed, the sampler's staging buffers, its graph cache, its step
@@ -15,34 +16,80 @@
 
 namespace {
 
-constexpr int STEP_DPM = 3;   // step_loop's kind behind the three GuideKinds: dpm_update (step.h DpmParams) instead of step_update
-
-// ---------------------------------------------------------------- the start and the loop of every sampling entry
-// what one step of a sampling call hands to step_update, computed on the host in fp32 before the first launch
+// ---------------------------------------------------------------- what every update hands to the one kernel
+// what one step hands to step_update, computed on the host in fp32 before the first launch
 struct Step {
+  int kind;                                // StepKind
   float c0, c1, c2, c3;
-  int add_noise;
-  float sigma_next;
-  const float* z;   // the step's external noise, or null
-  int iter;
-  int second;       // STEP_DPM: a second-order step, with (k0, k1, c4, c5) of solver_host.h
-  float k0, k1, c4, c5;
+  float sigma_next;                        // the next forward's sigma (a sampling loop; an update entry writes none)
+  int add_noise = 0;                       // the ancestral kinds
+  const float* z = nullptr;                // the step's external noise, or null
+  int iter = 0;
+  float k0 = 0, k1 = 0, c4 = 0, c5 = 0;    // STEP_DPM_SECOND (solver_host.h)
 };
+
+// a row of the solver's table as a step; the one place that turns solver_host.h's DpmKind (1 / 2: the row format of
+// dhw_dpm_coefs) into a StepKind
+Step dpm_step(const DpmCoef& c) { return Step{c.kind == DPM_SECOND ? STEP_DPM_SECOND : STEP_DPM_FIRST, c.c0, c.c1, c.c2, c.c3, c.c2, 0, nullptr, 0, c.k0, c.k1, c.c4, c.c5}; }
 
 // the steps of a deterministic call: level j to level j + 1 of the coefficient table, no noise
 std::vector<Step> ddim_steps(const std::vector<DdimCoef>& t, int S) {
   std::vector<Step> steps((size_t)S);
-  for (size_t j = 0; j < (size_t)S; ++j) steps[j] = Step{t[j].A, t[j].B, t[j + 1].A, t[j + 1].B, 0, t[j + 1].A, nullptr, 0};
+  for (size_t j = 0; j < (size_t)S; ++j) steps[j] = Step{STEP_DDIM, t[j].A, t[j].B, t[j + 1].A, t[j + 1].B, t[j + 1].A};
   return steps;
 }
 
 // the steps of a multistep call: the rows of the solver's table
 std::vector<Step> dpm_steps(const std::vector<DpmCoef>& t) {
   std::vector<Step> steps(t.size());
-  for (size_t j = 0; j < t.size(); ++j) steps[j] = Step{t[j].c0, t[j].c1, t[j].c2, t[j].c3, 0, t[j].c2, nullptr, 0, t[j].kind == DPM_SECOND, t[j].k0, t[j].k1, t[j].c4, t[j].c5};
+  for (size_t j = 0; j < t.size(); ++j) steps[j] = dpm_step(t[j]);
   return steps;
 }
 
+// the block's per-call fields: the arrays, the shape, the halves; a multistep call passes its hist
+StepParams step_params(const float* base, const float* eps, const float* pen, const int* lens, const float* scale, float* hist, int halves, int B, int L) {
+  StepParams p{};
+  p.base = base;
+  p.eps = eps;
+  p.pen = pen;
+  p.lens = lens;
+  p.scale = scale;
+  p.hist = hist;
+  p.rows = (long)B * L;
+  p.B = B;
+  p.L = L;
+  p.halves = halves;
+  return p;
+}
+
+// the block's per-step fields
+void step_set(StepParams& p, const Step& g) {
+  p.kind = g.kind;
+  p.c0 = g.c0;
+  p.c1 = g.c1;
+  p.c2 = g.c2;
+  p.c3 = g.c3;
+  p.k0 = g.k0;
+  p.k1 = g.k1;
+  p.c4 = g.c4;
+  p.c5 = g.c5;
+  p.add_noise = g.add_noise;
+  p.z = g.z;
+  p.iter = g.iter;
+  p.sigma_next = g.sigma_next;
+}
+
+// a handle-less update entry behind its checks: one launch on the caller's arrays
+int update_launch(const char* fn, StepParams p, const Step& g, float* out, float* out3, void* hip_stream) {
+  step_set(p, g);
+  p.out = out;
+  p.out3 = out3;
+  const hipError_t e = launch_step_update(p, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return fail(nullptr, DHW_ERR_HIP, "%s: launch: %s", fn, hipGetErrorString(e));
+  return 0;
+}
+
+// ---------------------------------------------------------------- the start and the loop of every sampling entry
 // x(0) in every half of the state (one launch per half), sigma0 for all halves * B rows; `copy` receives it once more
 // (latent_out) or is null
 int step_start(dhw_handle* h, EagerCall& ec, int halves, const float* src, int src_cols, int B, int L, uint64_t seed, int64_t first_sample, float sigma0,
@@ -69,78 +116,25 @@ int step_start(dhw_handle* h, EagerCall& ec, int halves, const float* src, int s
   return 0;
 }
 
-// the params of an update on the handle's scratch set; the caller adds the step's own
-StepParams step_params(dhw_handle* h, const int* dl, int halves, int kind, int B, int L) {
-  const dhw_handle::DenoiseScratch& s = h->scratch;
-  StepParams p{};
-  p.base = s.x;
-  p.eps = s.eps;
-  p.pen = s.pen;
-  p.lens = dl;
-  p.scale = halves == 2 ? h->d_guide_scale : nullptr;
-  p.rows = (long)B * L;
-  p.B = B;
-  p.L = L;
-  p.halves = halves;
-  p.kind = kind;
-  return p;
-}
-
-// the multistep update's own block (step.h: StepParams keeps its size) from a step's filled StepParams and the step's second-order part
-DpmParams dpm_params(const StepParams& p, const Step& g, float* hist) {
-  DpmParams d{};
-  d.base = p.base;
-  d.eps = p.eps;
-  d.pen = p.pen;
-  d.lens = p.lens;
-  d.scale = p.scale;
-  d.hist = hist;
-  d.rows = p.rows;
-  d.B = p.B;
-  d.L = p.L;
-  d.halves = p.halves;
-  d.second = g.second;
-  d.c0 = p.c0;
-  d.c1 = p.c1;
-  d.c2 = p.c2;
-  d.c3 = p.c3;
-  d.k0 = g.k0;
-  d.k1 = g.k1;
-  d.c4 = g.c4;
-  d.c5 = g.c5;
-  d.out = p.out;
-  d.out3 = p.out3;
-  d.sigma = p.sigma;
-  d.sigma_next = p.sigma_next;
-  return d;
-}
-
-// per step: the forward over halves * B rows, then the update in place; the last step writes the caller's [B, L, 3] instead
-int step_loop(dhw_handle* h, EagerCall& ec, int halves, int kind, const int64_t* text, const float* style, int B, int L, int Lt, uint64_t seed,
-              int64_t first_sample, const std::vector<Step>& steps, float* out) {
+// per step: the forward over halves * B rows, then the update in place; the last step writes the caller's [B, L, 3] instead.
+// A call's steps are all multistep or none is: the first one decides the label and whether the block carries hist.
+int step_loop(dhw_handle* h, EagerCall& ec, int halves, const int64_t* text, const float* style, int B, int L, int Lt, uint64_t seed, int64_t first_sample,
+              const std::vector<Step>& steps, float* out) {
   auto& [st, dl, c] = ec;
   const dhw_handle::DenoiseScratch& s = h->scratch;
-  const char* label = kind == STEP_DPM ? "dpm_update" : halves == 2 ? "guide_update" : "ddim_update";
-  StepParams p = step_params(h, dl, halves, kind, B, L);
+  const bool multistep = !steps.empty() && step_multistep(steps[0].kind);
+  const char* label = multistep ? "dpm_update" : halves == 2 ? "guide_update" : "ddim_update";
+  StepParams p = step_params(s.x, s.eps, s.pen, dl, halves == 2 ? h->d_guide_scale : nullptr, multistep ? s.hist : nullptr, halves, B, L);
   p.seed = seed;
   p.first_sample = first_sample;
   for (size_t j = 0; j < steps.size(); ++j) {
     if (int rc = forward_enqueue(h, s.x, text, s.sigma, style, halves * B, L, Lt, s.eps, s.pen, st, dl)) return rc;
-    const Step& g = steps[j];
     const bool last = j + 1 == steps.size();
-    p.c0 = g.c0;
-    p.c1 = g.c1;
-    p.c2 = g.c2;
-    p.c3 = g.c3;
-    p.add_noise = g.add_noise;
-    p.z = g.z;
-    p.iter = g.iter;
+    step_set(p, steps[j]);
     p.out = last ? nullptr : s.x;
     p.out3 = last ? out : nullptr;
     p.sigma = last ? nullptr : s.sigma;
-    p.sigma_next = g.sigma_next;
-    if (kind == STEP_DPM) RUN_SMALL(c, label, launch_dpm_update(dpm_params(p, g, s.hist), st));
-    else RUN_SMALL(c, label, launch_step_update(p, st));
+    RUN_SMALL(c, label, launch_step_update(p, st));
     if (c.err) return c.err;
   }
   return 0;
@@ -171,31 +165,6 @@ int ensure_hist(dhw_handle* h) {
   return dev_alloc(h, (void**)&h->scratch.hist, (size_t)h->dims.max_B * h->dims.max_L * 2 * 4);
 }
 
-// order null: dhw_ddim_sample; else dhw_dpm_sample with that order
-int sample_impl_ddim(dhw_handle* h, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens, int T, const int32_t* levels,
-                     int S, const float* latent, uint64_t seed, int64_t first_sample, float* latent_out, float* out, void* hip_stream, const int* order = nullptr) {
-  const bool dpm = order != nullptr;
-  const char* fn = dpm ? "dhw_dpm_sample" : "dhw_ddim_sample";
-  if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
-  if (!out) return fail(h, DHW_ERR_ARG, "%s: null pointer (out)", fn);
-  int rc = ddim_check_common(h, fn, text, style, B, L, Lt, lens, T, levels, S);
-  if (rc) return rc;
-  std::vector<DpmCoef> table;
-  if (dpm && (rc = dpm_check_table(h, fn, T, levels, S, *order, table))) return rc;
-  if (((uintptr_t)latent | (uintptr_t)latent_out) & 7)
-    return fail(h, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)latent & 7) ? "latent" : "latent_out");
-
-  EagerCall ec;
-  if ((rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec)) || (rc = ensure_scratch(h))) return rc;   // (leaves dhw_sample's text plane alone: forward_enqueue)
-  if (dpm) {
-    if ((rc = ensure_hist(h)) || (rc = step_start(h, ec, 1, latent, 2, B, L, seed, first_sample, table[0].c0, latent_out))) return rc;
-    return step_loop(h, ec, 1, STEP_DPM, text, style, B, L, Lt, 0, 0, dpm_steps(table), out);
-  }
-  const std::vector<DdimCoef> t = ddim_coef_table(schedule_abar(T).data(), levels, S);
-  if ((rc = step_start(h, ec, 1, latent, 2, B, L, seed, first_sample, t[0].A, latent_out))) return rc;
-  return step_loop(h, ec, 1, GUIDE_DDIM, text, style, B, L, Lt, 0, 0, ddim_steps(t, S), out);
-}
-
 int invert_impl_ddim(dhw_handle* h, const float* strokes, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens, int T,
                      const int32_t* levels, int S, int iters, float* latent_out, void* hip_stream) {
   const char* fn = "dhw_ddim_invert";
@@ -216,7 +185,8 @@ int invert_impl_ddim(dhw_handle* h, const float* strokes, const int64_t* text, c
 
   // the loop runs backwards: y(j+1) stays in scratch.x while the iterate w lives in scratch.w; the last iteration of a step
   // writes y(j) over it, the last one of the call writes the caller's latent_out
-  StepParams p = step_params(h, dl, 1, GUIDE_DDIM, B, L);
+  StepParams p = step_params(s.x, s.eps, s.pen, dl, nullptr, nullptr, 1, B, L);
+  p.kind = STEP_DDIM;
   for (int j = S - 1; j >= 0; --j) {
     p.c0 = t[(size_t)j + 1].A;
     p.c1 = t[(size_t)j + 1].B;
@@ -245,23 +215,7 @@ int update_impl_ddim(const float* base, const float* eps, const int32_t* lens, i
   if (((uintptr_t)base | (uintptr_t)eps | (uintptr_t)out) & 7)
     return fail(nullptr, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)base & 7) ? "base" : ((uintptr_t)eps & 7) ? "eps" : "out");
   if ((uintptr_t)lens & 3) return fail(nullptr, DHW_ERR_ARG, "%s: lens must be 4-byte aligned", fn);
-  StepParams p{};
-  p.base = base;
-  p.eps = eps;
-  p.lens = lens;
-  p.rows = (long)B * L;
-  p.B = B;
-  p.L = L;
-  p.halves = 1;
-  p.kind = GUIDE_DDIM;
-  p.c0 = c0;
-  p.c1 = c1;
-  p.c2 = c2;
-  p.c3 = c3;
-  p.out = out;
-  const hipError_t e = launch_step_update(p, (hipStream_t)hip_stream);
-  if (e != hipSuccess) return fail(nullptr, DHW_ERR_HIP, "%s: launch: %s", fn, hipGetErrorString(e));
-  return 0;
+  return update_launch(fn, step_params(base, eps, nullptr, lens, nullptr, nullptr, 1, B, L), Step{STEP_DDIM, c0, c1, c2, c3, 0.f}, out, nullptr, hip_stream);
 }
 
 // ---------------------------------------------------------------- guided sampling
@@ -304,31 +258,37 @@ int guide_begin(dhw_handle* h, int B, int L, int Lt, const int32_t* lens, const 
   return stage_scale(h, scale, B, ec->st);
 }
 
-int sample_impl_guided_ddim(dhw_handle* h, const int64_t* text2, const float* style2, int B, int L, int Lt, const int32_t* lens, int T, const int32_t* levels,
-                            int S, const float* scale, const float* latent, uint64_t seed, int64_t first_sample, float* out, float* latent_out, void* hip_stream,
-                            const int* order = nullptr) {   // order null: dhw_guided_ddim_sample; else dhw_guided_dpm_sample with that order
-  const bool dpm = order != nullptr;
-  const char* fn = dpm ? "dhw_guided_dpm_sample" : "dhw_guided_ddim_sample";
+// The four deterministic sampling entries.  halves = 1: dhw_ddim_sample / dhw_dpm_sample (text, style of B rows; scale is not
+// read); halves = 2: dhw_guided_ddim_sample / dhw_guided_dpm_sample (text2, style2 of 2B rows).  order null: the ddim entries; else
+// the dpm entries with that order.  Each entry keeps its own check order, messages and prologue.
+int sample_impl_levels(dhw_handle* h, int halves, const int* order, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens, int T,
+                       const int32_t* levels, int S, const float* scale, const float* latent, uint64_t seed, int64_t first_sample, float* latent_out, float* out,
+                       void* hip_stream) {
+  const bool guided = halves == 2, dpm = order != nullptr;
+  const char* fn = guided ? (dpm ? "dhw_guided_dpm_sample" : "dhw_guided_ddim_sample") : (dpm ? "dhw_dpm_sample" : "dhw_ddim_sample");
   if (!h) return fail(nullptr, DHW_ERR_ARG, "null handle");
-  int rc = guide_check_front(h, fn, text2, style2, out, B, L, Lt, lens);
-  if (rc) return rc;
-  char msg[160];
-  if (ddim_check_levels(T, levels, S, msg, sizeof msg)) return fail(h, DHW_ERR_ARG, "%s: %s", fn, msg);
+  int rc;
+  if (guided) {
+    if ((rc = guide_check_front(h, fn, text, style, out, B, L, Lt, lens))) return rc;
+    char msg[160];
+    if (ddim_check_levels(T, levels, S, msg, sizeof msg)) return fail(h, DHW_ERR_ARG, "%s: %s", fn, msg);
+  } else {
+    if (!out) return fail(h, DHW_ERR_ARG, "%s: null pointer (out)", fn);
+    if ((rc = ddim_check_common(h, fn, text, style, B, L, Lt, lens, T, levels, S))) return rc;
+  }
   std::vector<DpmCoef> table;
   if (dpm && (rc = dpm_check_table(h, fn, T, levels, S, *order, table))) return rc;
-  if ((rc = guide_check_back(h, fn, scale, B, L))) return rc;
+  if (guided && (rc = guide_check_back(h, fn, scale, B, L))) return rc;
   if (((uintptr_t)latent | (uintptr_t)latent_out) & 7)
     return fail(h, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)latent & 7) ? "latent" : "latent_out");
 
   EagerCall ec;
-  if ((rc = guide_begin(h, B, L, Lt, lens, scale, hip_stream, &ec))) return rc;
-  if (dpm) {
-    if ((rc = ensure_hist(h)) || (rc = step_start(h, ec, 2, latent, 2, B, L, seed, first_sample, table[0].c0, latent_out))) return rc;
-    return step_loop(h, ec, 2, STEP_DPM, text2, style2, B, L, Lt, 0, 0, dpm_steps(table), out);
-  }
-  const std::vector<DdimCoef> t = ddim_coef_table(schedule_abar(T).data(), levels, S);
-  if ((rc = step_start(h, ec, 2, latent, 2, B, L, seed, first_sample, t[0].A, latent_out))) return rc;
-  return step_loop(h, ec, 2, GUIDE_DDIM, text2, style2, B, L, Lt, 0, 0, ddim_steps(t, S), out);
+  if (guided) rc = guide_begin(h, B, L, Lt, lens, scale, hip_stream, &ec);
+  else if (!(rc = eager_begin(h, B, L, Lt, lens, hip_stream, &ec))) rc = ensure_scratch(h);   // (leaves dhw_sample's text plane alone: forward_enqueue)
+  if (rc || (dpm && (rc = ensure_hist(h)))) return rc;
+  const std::vector<Step> steps = dpm ? dpm_steps(table) : ddim_steps(ddim_coef_table(schedule_abar(T).data(), levels, S), S);
+  if ((rc = step_start(h, ec, halves, latent, 2, B, L, seed, first_sample, steps[0].c0, latent_out))) return rc;   // (c0 of step 0 is A_0)
+  return step_loop(h, ec, halves, text, style, B, L, Lt, 0, 0, steps, out);
 }
 
 int sample_impl_guided(dhw_handle* h, const int64_t* text2, const float* style2, int B, int L, int Lt, const int32_t* lens, int T, int mode, const float* scale,
@@ -350,10 +310,10 @@ int sample_impl_guided(dhw_handle* h, const int64_t* text2, const float* style2,
   std::vector<Step> steps((size_t)T);
   for (int k = 0, i = T - 1; i >= 0; --i, ++k) {
     const GuideStep g = guide_step(mode, beta.data(), abar.data(), i);
-    steps[(size_t)k] = Step{g.c0, g.c1, g.c2, g.c3, g.add_noise, g.sigma_next, noise ? noise + (size_t)(1 + k) * step_stride : nullptr, k};
+    steps[(size_t)k] = Step{mode == 0 ? STEP_NEW : STEP_STANDARD, g.c0, g.c1, g.c2, g.c3, g.sigma_next, g.add_noise, noise ? noise + (size_t)(1 + k) * step_stride : nullptr, k};
   }
   if ((rc = step_start(h, ec, 2, noise, 2, B, L, seed, first_sample, sqrtf(abar[(size_t)T - 1]), nullptr))) return rc;
-  return step_loop(h, ec, 2, mode == 0 ? GUIDE_NEW : GUIDE_STANDARD, text2, style2, B, L, Lt, seed, first_sample, steps, out);
+  return step_loop(h, ec, 2, text2, style2, B, L, Lt, seed, first_sample, steps, out);
 }
 
 int update_impl_guide(int kind, const float* base, const float* eps2, const float* pen, const int32_t* lens, const float* scale, const float* z, int B, int L, float c0,
@@ -369,28 +329,7 @@ int update_impl_guide(int kind, const float* base, const float* eps2, const floa
     return fail(nullptr, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)base & 7) ? "base" : ((uintptr_t)eps2 & 7) ? "eps2" : ((uintptr_t)z & 7) ? "z" : "out");
   if (((uintptr_t)lens | (uintptr_t)scale | (uintptr_t)pen | (uintptr_t)out3) & 3)
     return fail(nullptr, DHW_ERR_ARG, "%s: lens, scale, pen and out3 must be 4-byte aligned", fn);
-  StepParams p{};
-  p.base = base;
-  p.eps = eps2;
-  p.pen = pen;
-  p.lens = lens;
-  p.scale = scale;
-  p.z = z;
-  p.rows = (long)B * L;
-  p.B = B;
-  p.L = L;
-  p.halves = 2;
-  p.kind = kind;
-  p.c0 = c0;
-  p.c1 = c1;
-  p.c2 = c2;
-  p.c3 = c3;
-  p.add_noise = z != nullptr;
-  p.out = out;
-  p.out3 = out3;
-  const hipError_t e = launch_step_update(p, (hipStream_t)hip_stream);
-  if (e != hipSuccess) return fail(nullptr, DHW_ERR_HIP, "%s: launch: %s", fn, hipGetErrorString(e));
-  return 0;
+  return update_launch(fn, step_params(base, eps2, pen, lens, scale, nullptr, 2, B, L), Step{kind, c0, c1, c2, c3, 0.f, z != nullptr, z}, out, out3, hip_stream);
 }
 
 // ---------------------------------------------------------------- the multistep solver's handle-less entries
@@ -422,31 +361,7 @@ int update_impl_dpm(const float* base, const float* eps, const float* pen, const
     return fail(nullptr, DHW_ERR_ARG, "%s: %s must be 8-byte aligned", fn, ((uintptr_t)base & 7) ? "base" : ((uintptr_t)eps & 7) ? "eps" : ((uintptr_t)hist & 7) ? "hist" : "out");
   if (((uintptr_t)lens | (uintptr_t)scale | (uintptr_t)pen | (uintptr_t)out3) & 3)
     return fail(nullptr, DHW_ERR_ARG, "%s: lens, scale, pen and out3 must be 4-byte aligned", fn);
-  DpmParams p{};
-  p.base = base;
-  p.eps = eps;
-  p.pen = pen;
-  p.lens = lens;
-  p.scale = scale;
-  p.hist = hist;
-  p.rows = (long)B * L;
-  p.B = B;
-  p.L = L;
-  p.halves = halves;
-  p.second = c.kind == DPM_SECOND;
-  p.c0 = c.c0;
-  p.c1 = c.c1;
-  p.c2 = c.c2;
-  p.c3 = c.c3;
-  p.k0 = c.k0;
-  p.k1 = c.k1;
-  p.c4 = c.c4;
-  p.c5 = c.c5;
-  p.out = out;
-  p.out3 = out3;
-  const hipError_t e = launch_dpm_update(p, (hipStream_t)hip_stream);
-  if (e != hipSuccess) return fail(nullptr, DHW_ERR_HIP, "%s: launch: %s", fn, hipGetErrorString(e));
-  return 0;
+  return update_launch(fn, step_params(base, eps, pen, lens, scale, hist, halves, B, L), dpm_step(c), out, out3, hip_stream);
 }
 
 }  // namespace
@@ -455,7 +370,7 @@ extern "C" {
 
 int dhw_ddim_sample(dhw_handle* h, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens, int T, const int32_t* levels,
                     int S, const float* latent, uint64_t seed, int64_t first_sample, float* latent_out, float* out, void* hip_stream) {
-  DHW_GUARD(h, "dhw_ddim_sample", int, { return sample_impl_ddim(h, text, style, B, L, Lt, lens, T, levels, S, latent, seed, first_sample, latent_out, out, hip_stream); });
+  DHW_GUARD(h, "dhw_ddim_sample", int, { return sample_impl_levels(h, 1, nullptr, text, style, B, L, Lt, lens, T, levels, S, nullptr, latent, seed, first_sample, latent_out, out, hip_stream); });
 }
 
 int dhw_ddim_invert(dhw_handle* h, const float* strokes, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens, int T,
@@ -471,7 +386,7 @@ int dhw_ddim_update(const float* base, const float* eps, const int32_t* lens, in
 int dhw_guided_ddim_sample(dhw_handle* h, const int64_t* text2, const float* style2, int B, int L, int Lt, const int32_t* lens, int T, const int32_t* levels,
                            int S, const float* scale, const float* latent, uint64_t seed, int64_t first_sample, float* out, float* latent_out, void* hip_stream) {
   DHW_GUARD(h, "dhw_guided_ddim_sample", int, {
-    return sample_impl_guided_ddim(h, text2, style2, B, L, Lt, lens, T, levels, S, scale, latent, seed, first_sample, out, latent_out, hip_stream);
+    return sample_impl_levels(h, 2, nullptr, text2, style2, B, L, Lt, lens, T, levels, S, scale, latent, seed, first_sample, latent_out, out, hip_stream);
   });
 }
 
@@ -497,7 +412,7 @@ int dhw_dpm_update(const float* base, const float* eps, const float* pen, const 
 int dhw_dpm_sample(dhw_handle* h, const int64_t* text, const float* style, int B, int L, int Lt, const int32_t* lens, int T, const int32_t* levels,
                    int S, int order, const float* latent, uint64_t seed, int64_t first_sample, float* latent_out, float* out, void* hip_stream) {
   DHW_GUARD(h, "dhw_dpm_sample", int, {
-    return sample_impl_ddim(h, text, style, B, L, Lt, lens, T, levels, S, latent, seed, first_sample, latent_out, out, hip_stream, &order);
+    return sample_impl_levels(h, 1, &order, text, style, B, L, Lt, lens, T, levels, S, nullptr, latent, seed, first_sample, latent_out, out, hip_stream);
   });
 }
 
@@ -505,7 +420,7 @@ int dhw_guided_dpm_sample(dhw_handle* h, const int64_t* text2, const float* styl
                           int S, int order, const float* scale, const float* latent, uint64_t seed, int64_t first_sample, float* out, float* latent_out,
                           void* hip_stream) {
   DHW_GUARD(h, "dhw_guided_dpm_sample", int, {
-    return sample_impl_guided_ddim(h, text2, style2, B, L, Lt, lens, T, levels, S, scale, latent, seed, first_sample, out, latent_out, hip_stream, &order);
+    return sample_impl_levels(h, 2, &order, text2, style2, B, L, Lt, lens, T, levels, S, scale, latent, seed, first_sample, latent_out, out, hip_stream);
   });
 }
 

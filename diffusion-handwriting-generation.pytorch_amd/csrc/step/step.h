@@ -1,6 +1,6 @@
 // step.h — launchers of the eager samplers' small kernels (include/dhw.h: dhw_ddim_sample, dhw_ddim_invert, dhw_ddim_update,
 // dhw_guided_ddim_sample, dhw_guided_sample, dhw_guide_update, dhw_dpm_update, dhw_dpm_sample, dhw_guided_dpm_sample; DESIGN.md
-// §23, §33, §34, §40); shared by step.hip and dhw_step_api.cpp (the loops that launch them around the denoiser).
+// §23, §33, §34, §40, §41); shared by step.hip and dhw_step_api.cpp (the loops that launch them around the denoiser).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,9 +23,20 @@ struct DdimStartParams {
   float sigma0;
 };
 
-// One step per stroke row r = b*L + p of the B samples.  halves = 1: the update `kind` (GUIDE_DDIM only) of (base[r], eps[r]).
+// The update a step makes.  0 / 1 / 2 are GuideKind's numbers (dhw_guide_update's `kind`); the two behind them are the multistep
+// solver's first- and second-order step (include/dhw.h dhw_dpm_update), internal: dhw_step_api.cpp translates
+// solver_host.h's DpmKind, the row format of dhw_dpm_coefs, into them.
+enum StepKind { STEP_DDIM = GUIDE_DDIM, STEP_NEW = GUIDE_NEW, STEP_STANDARD = GUIDE_STANDARD, STEP_DPM_FIRST = 3, STEP_DPM_SECOND = 4 };
+static_assert(STEP_DDIM == 0 && STEP_NEW == 1 && STEP_STANDARD == 2 && STEP_DPM_FIRST == GUIDE_STANDARD + 1,
+              "the public kinds keep GuideKind's numbers; the internal ones follow them");
+constexpr bool step_multistep(int kind) { return kind == STEP_DPM_FIRST || kind == STEP_DPM_SECOND; }
+
+// One step per stroke row r = b*L + p of the B samples.  halves = 1: the update `kind` (not an ancestral one) of (base[r], eps[r]).
 // halves = 2, a guided step behind a forward of 2B rows: e = combine(eps[r], eps[r + rows], scale[b]), then the update `kind` of
-// (base[r], e), written to BOTH halves of the doubled state.
+// (base[r], e), written to BOTH halves of the doubled state.  A multistep kind also writes hist[r] = x0 = (base - c1 e) / c0;
+// STEP_DPM_FIRST is otherwise STEP_DDIM (U's bits), STEP_DPM_SECOND the nine operations on (base, e, hist[r]).
+// ONE block for every kind: the multistep fields are APPENDED, so no field of §34's block moved and the kernels
+// that do not read them load what they loaded before (§34 and §40 feared a wider block; that holds for an inserted field only).
 struct StepParams {
   const float* base;      // the state; rows [0, rows) are read
   const float* eps;       // [halves*rows, 2]: the conditional half, then (halves = 2) the guidance half
@@ -36,8 +47,8 @@ struct StepParams {
   long rows;              // B * L
   int B, L;
   int halves;             // 1 or 2
-  int kind;               // GuideKind
-  float c0, c1, c2, c3;   // computed on the host in fp32 (ddim_host.h / guide_host.h), passed by value
+  int kind;               // StepKind
+  float c0, c1, c2, c3;   // computed on the host in fp32 (ddim_host.h / guide_host.h / solver_host.h), passed by value
   int add_noise;          // ancestral kinds: the noise term is added
   uint64_t seed;          // the generator's key and counters, as normal2 takes them
   int64_t first_sample;
@@ -47,31 +58,11 @@ struct StepParams {
   float* out3;            // [rows, 3] = (x, pen): the last step of a sampling call, or null
   float* sigma;           // [halves*B]: b (and b + B) receive sigma_next for the next forward, or null
   float sigma_next;
-};
-
-// One step of the second-order multistep solver (include/dhw.h dhw_dpm_update) per stroke row r = b*L + p of the B
-// samples; its own block: StepParams keeps its size (§34: a wider argument block changes the existing kernels' scalar loads).
-// second = 0: x' = U(base, e; c0, c1, c2, c3), step_update's bits.  second = 1: the nine operations on (base, e, hist[r]).  Both
-// write hist[r] = x0 = (base - c1 e) / c0.  halves = 2: e = combine(eps[r], eps[r + rows], scale[b]), x' goes to both halves.
-struct DpmParams {
-  const float* base;      // the state; rows [0, rows) are read
-  const float* eps;       // [halves*rows, 2]
-  const float* pen;       // [rows] (read with out3 only)
-  const int* lens;        // per-sample lengths (device, B entries), or null
-  const float* scale;     // [B] (device); halves = 2 only
-  float* hist;            // [rows, 2], one half only: read by a second-order step (its own row, before it is written), written by every step
-  long rows;              // B * L
-  int B, L;
-  int halves;             // 1 or 2
-  int second;             // 0: first order, 1: second order
-  float c0, c1, c2, c3;   // A_j, B_j, A_{j+1}, B_{j+1}
-  float k0, k1, c4, c5;   // second order only (solver_host.h)
-  float* out;             // [halves*rows, 2] (may be `base`), or null with out3
-  float* out3;            // [rows, 3] = (x', pen): the last step of a sampling call, or null
-  float* sigma;           // [halves*B], or null
-  float sigma_next;
+  // the multistep kinds only, behind everything else
+  float* hist;            // [rows, 2], one half only: read by a second-order step (its own row, before it is written), written by
+                          // every multistep step; null for the other kinds
+  float k0, k1, c4, c5;   // STEP_DPM_SECOND only (solver_host.h)
 };
 
 hipError_t launch_ddim_start(const DdimStartParams& p, hipStream_t st);
 hipError_t launch_step_update(const StepParams& p, hipStream_t st);
-hipError_t launch_dpm_update(const DpmParams& p, hipStream_t st);

@@ -1,7 +1,7 @@
 // step.hip — the small kernels of the eager samplers around the denoiser launches (include/dhw.h: dhw_ddim_sample,
 // dhw_ddim_invert, dhw_ddim_update, dhw_guided_ddim_sample, dhw_guided_sample, dhw_guide_update, dhw_dpm_*; DESIGN.md §23, §33,
-// §34, §40).  ddim_start writes the first state; step_update moves a state from one noise level to the next along the denoiser's
-// answer; dpm_update does so with the previous step's x0 estimate as well (second-order multistep) and keeps the new estimate.
+// §34, §40, §41).  ddim_start writes the first state; step_update moves a state from one noise level to the next along the denoiser's
+// answer; its multistep kinds do so with the previous step's x0 estimate as well (second order) and keep the new estimate.
 // Behind a guided call's forward over 2B rows that answer lies under the real condition in rows [0, B) of eps and under the
 // guidance condition in rows [B, 2B): the guided instantiations combine the two per stroke row and write the new row to BOTH
 // halves of the doubled state, so the next forward sees one x under two conditions.  Both kernels BRANCH on the lengths read at
@@ -75,58 +75,6 @@ DHW_DEV float step_standard(float x, float e, float z, float c0, float c1, float
   return add ? y + n : y;
 }
 
-// One thread per stroke row of the B samples.  KIND and GUIDED are template arguments: the launcher switches, no lane does.
-// !GUIDED takes eps[row] as it is (no combine: e + 0 * (e - e) would turn a -0 into +0 and an infinity into NaN) and touches
-// nothing of a second half.  out3 (the last step of a sampling call) also gets the row with the denoiser's pen value.
-template <int KIND, bool GUIDED>
-__global__ __launch_bounds__(256) void step_update_kernel(const StepParams p) {
-  static_assert(GUIDED || KIND == GUIDE_DDIM, "the unguided ancestral steps are heads_finish's (heads_core.h)");
-  const unsigned row = blockIdx.x * 256u + threadIdx.x;   // (halves * rows < 2^31, checked by the launcher: 32-bit index arithmetic)
-  const unsigned rows = (unsigned)p.rows;
-  if (row >= rows) return;
-  const int b = (int)(row / (unsigned)p.L), pos = (int)(row - (unsigned)b * (unsigned)p.L);
-  if (p.sigma && pos == 0) {
-    p.sigma[b] = p.sigma_next;
-    if (GUIDED) p.sigma[b + p.B] = p.sigma_next;
-  }
-  float2 x = make_float2(0.f, 0.f);
-  float q = 0.f;
-  if (pos < (p.lens ? p.lens[b] : p.L)) {
-    const float2 base = reinterpret_cast<const float2*>(p.base)[row];
-    float2 e = reinterpret_cast<const float2*>(p.eps)[row];
-    if (GUIDED) e = guide_combine(e, reinterpret_cast<const float2*>(p.eps)[row + rows], p.scale[b]);
-    if (KIND == GUIDE_DDIM) {
-      x.x = step_u(base.x, e.x, p.c0, p.c1, p.c2, p.c3);
-      x.y = step_u(base.y, e.y, p.c0, p.c1, p.c2, p.c3);
-    } else {
-      const bool add = p.add_noise != 0;   // (a kernel argument: uniform)
-      float2 z = make_float2(0.f, 0.f);
-      if (add) {
-        if (p.z) z = reinterpret_cast<const float2*>(p.z)[row];
-        else normal2(p.seed, p.first_sample + b, pos, p.iter, z.x, z.y);
-      }
-      if (KIND == GUIDE_NEW) {
-        x.x = step_new(base.x, e.x, z.x, p.c0, p.c1, p.c2, add);
-        x.y = step_new(base.y, e.y, z.y, p.c0, p.c1, p.c2, add);
-      } else {
-        x.x = step_standard(base.x, e.x, z.x, p.c0, p.c1, p.c2, p.c3, add);
-        x.y = step_standard(base.y, e.y, z.y, p.c0, p.c1, p.c2, p.c3, add);
-      }
-    }
-    if (p.out3) q = p.pen[row];
-  }
-  if (p.out) {
-    reinterpret_cast<float2*>(p.out)[row] = x;
-    if (GUIDED) reinterpret_cast<float2*>(p.out)[row + rows] = x;
-  }
-  if (p.out3) {
-    float* o = p.out3 + (size_t)row * 3;
-    o[0] = x.x;
-    o[1] = x.y;
-    o[2] = q;
-  }
-}
-
 // the x0 estimate from (base, e) at level (c0, c1): the first three operations of step_u, the same roundings
 DHW_DEV float step_x0(float base, float e, float c0, float c1) {
 #pragma clang fp contract(off)
@@ -146,11 +94,16 @@ DHW_DEV float dpm_second(float x, float x0, float hist, float k0, float k1, floa
   return s + n;
 }
 
-// One thread per stroke row, indexed like step_update_kernel.  SECOND and GUIDED are template arguments.  A first-order step is
-// step_u itself (the bits of dhw_ddim_update) and never reads hist; every step leaves its x0 in hist, one half only.  A row reads
-// its own base / hist entry before it writes it, so out may be base and hist is updated in place.
-template <bool SECOND, bool GUIDED>
-__global__ __launch_bounds__(256) void dpm_update_kernel(const DpmParams p) {
+// One thread per stroke row of the B samples.  KIND and GUIDED are template arguments: the launcher switches, no lane does.
+// !GUIDED takes eps[row] as it is (no combine: e + 0 * (e - e) would turn a -0 into +0 and an infinity into NaN) and touches
+// nothing of a second half.  out3 (the last step of a sampling call) also gets the row with the denoiser's pen value.  A multistep
+// kind leaves its x0 in hist, one half only, 0 at and past a length; its first-order step is step_u itself (the bits of
+// dhw_ddim_update) and never reads hist.  A row reads its own base / hist entry before it writes it, so out may be base and hist is
+// updated in place.
+template <int KIND, bool GUIDED>
+__global__ __launch_bounds__(256) void step_update_kernel(const StepParams p) {
+  constexpr bool MULTISTEP = step_multistep(KIND);
+  static_assert(GUIDED || KIND == STEP_DDIM || MULTISTEP, "the unguided ancestral steps are heads_finish's (heads_core.h)");
   const unsigned row = blockIdx.x * 256u + threadIdx.x;   // (halves * rows < 2^31, checked by the launcher: 32-bit index arithmetic)
   const unsigned rows = (unsigned)p.rows;
   if (row >= rows) return;
@@ -165,19 +118,35 @@ __global__ __launch_bounds__(256) void dpm_update_kernel(const DpmParams p) {
     const float2 base = reinterpret_cast<const float2*>(p.base)[row];
     float2 e = reinterpret_cast<const float2*>(p.eps)[row];
     if (GUIDED) e = guide_combine(e, reinterpret_cast<const float2*>(p.eps)[row + rows], p.scale[b]);
-    x0.x = step_x0(base.x, e.x, p.c0, p.c1);
-    x0.y = step_x0(base.y, e.y, p.c0, p.c1);
-    if (SECOND) {
+    if (MULTISTEP) {
+      x0.x = step_x0(base.x, e.x, p.c0, p.c1);
+      x0.y = step_x0(base.y, e.y, p.c0, p.c1);
+    }
+    if (KIND == STEP_DPM_SECOND) {
       const float2 h = reinterpret_cast<const float2*>(p.hist)[row];
       x.x = dpm_second(base.x, x0.x, h.x, p.k0, p.k1, p.c4, p.c5);
       x.y = dpm_second(base.y, x0.y, h.y, p.k0, p.k1, p.c4, p.c5);
-    } else {
+    } else if (KIND == STEP_DDIM || KIND == STEP_DPM_FIRST) {
       x.x = step_u(base.x, e.x, p.c0, p.c1, p.c2, p.c3);
       x.y = step_u(base.y, e.y, p.c0, p.c1, p.c2, p.c3);
+    } else {
+      const bool add = p.add_noise != 0;   // (a kernel argument: uniform)
+      float2 z = make_float2(0.f, 0.f);
+      if (add) {
+        if (p.z) z = reinterpret_cast<const float2*>(p.z)[row];
+        else normal2(p.seed, p.first_sample + b, pos, p.iter, z.x, z.y);
+      }
+      if (KIND == STEP_NEW) {
+        x.x = step_new(base.x, e.x, z.x, p.c0, p.c1, p.c2, add);
+        x.y = step_new(base.y, e.y, z.y, p.c0, p.c1, p.c2, add);
+      } else {
+        x.x = step_standard(base.x, e.x, z.x, p.c0, p.c1, p.c2, p.c3, add);
+        x.y = step_standard(base.y, e.y, z.y, p.c0, p.c1, p.c2, p.c3, add);
+      }
     }
     if (p.out3) q = p.pen[row];
   }
-  reinterpret_cast<float2*>(p.hist)[row] = x0;
+  if (MULTISTEP) reinterpret_cast<float2*>(p.hist)[row] = x0;
   if (p.out) {
     reinterpret_cast<float2*>(p.out)[row] = x;
     if (GUIDED) reinterpret_cast<float2*>(p.out)[row + rows] = x;
@@ -204,33 +173,22 @@ hipError_t launch_ddim_start(const DdimStartParams& p, hipStream_t st) {
 
 hipError_t launch_step_update(const StepParams& p, hipStream_t st) {
   const bool guided = p.halves == 2;
-  if (step_bad_shape(p.rows, p.B, p.L, p.halves) || !p.base || !p.eps || (guided && !p.scale) || (!p.out && !p.out3) || (p.out3 && !p.pen))
+  if (step_bad_shape(p.rows, p.B, p.L, p.halves) || !p.base || !p.eps || (guided && !p.scale) || (!p.out && !p.out3) || (p.out3 && !p.pen) ||
+      step_multistep(p.kind) != (p.hist != nullptr))
     return hipErrorInvalidValue;
   const dim3 grid((unsigned)((p.rows + 255) / 256)), block(256);
-  if (!guided && p.kind != GUIDE_DDIM) return hipErrorInvalidValue;
-  switch (p.kind) {
-    case GUIDE_DDIM:
-      if (guided) hipLaunchKernelGGL((step_update_kernel<GUIDE_DDIM, true>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((step_update_kernel<GUIDE_DDIM, false>), grid, block, 0, st, p);
-      break;
-    case GUIDE_NEW: hipLaunchKernelGGL((step_update_kernel<GUIDE_NEW, true>), grid, block, 0, st, p); break;
-    case GUIDE_STANDARD: hipLaunchKernelGGL((step_update_kernel<GUIDE_STANDARD, true>), grid, block, 0, st, p); break;
-    default: return hipErrorInvalidValue;
+#define STEP_LAUNCH(KIND, GUIDED) hipLaunchKernelGGL((step_update_kernel<KIND, GUIDED>), grid, block, 0, st, p)
+  switch (p.kind * 2 + (guided ? 1 : 0)) {
+    case STEP_DDIM * 2: STEP_LAUNCH(STEP_DDIM, false); break;
+    case STEP_DDIM * 2 + 1: STEP_LAUNCH(STEP_DDIM, true); break;
+    case STEP_NEW * 2 + 1: STEP_LAUNCH(STEP_NEW, true); break;
+    case STEP_STANDARD * 2 + 1: STEP_LAUNCH(STEP_STANDARD, true); break;
+    case STEP_DPM_FIRST * 2: STEP_LAUNCH(STEP_DPM_FIRST, false); break;
+    case STEP_DPM_FIRST * 2 + 1: STEP_LAUNCH(STEP_DPM_FIRST, true); break;
+    case STEP_DPM_SECOND * 2: STEP_LAUNCH(STEP_DPM_SECOND, false); break;
+    case STEP_DPM_SECOND * 2 + 1: STEP_LAUNCH(STEP_DPM_SECOND, true); break;
+    default: return hipErrorInvalidValue;   // (no such kind, or an unguided ancestral step)
   }
-  return hipGetLastError();
-}
-
-hipError_t launch_dpm_update(const DpmParams& p, hipStream_t st) {
-  const bool guided = p.halves == 2, second = p.second != 0;
-  if (step_bad_shape(p.rows, p.B, p.L, p.halves) || !p.base || !p.eps || !p.hist || (guided && !p.scale) || (!p.out && !p.out3) || (p.out3 && !p.pen))
-    return hipErrorInvalidValue;
-  const dim3 grid((unsigned)((p.rows + 255) / 256)), block(256);
-  if (second) {
-    if (guided) hipLaunchKernelGGL((dpm_update_kernel<true, true>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((dpm_update_kernel<true, false>), grid, block, 0, st, p);
-  } else {
-    if (guided) hipLaunchKernelGGL((dpm_update_kernel<false, true>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((dpm_update_kernel<false, false>), grid, block, 0, st, p);
-  }
+#undef STEP_LAUNCH
   return hipGetLastError();
 }

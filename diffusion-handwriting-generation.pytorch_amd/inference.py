@@ -389,6 +389,14 @@ def _order_kw(order, steps) -> dict:
     return {"order": _check_order(order)}
 
 
+def _ddim_kw(steps, order, guidance, candidates: int, B: int) -> dict:
+    """What a file front end passes on for ``steps``, ``order``, ``guidance``, checked in that order; nothing for a None: today's calls."""
+    kw = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}
+    kw.update(_order_kw(order, steps))
+    kw.update(_guided_kw(guidance, candidates, B))
+    return kw
+
+
 def _check_ddim_common(text, style_vector, B: int, lengths, L):
     if not isinstance(text, torch.Tensor) or text.dim() != 2 or text.shape[0] != B or text.dtype.is_floating_point:
         raise ValueError(f"text must be an integer tensor [B = {B}, Lt], got {tuple(text.shape) if isinstance(text, torch.Tensor) else type(text).__name__}")
@@ -831,9 +839,7 @@ def infer_file(prompt: str, source, config_path: str | None = None, checkpoint_p
 
     _check_renderer(renderer)
     candidates = _check_candidates(candidates)
-    ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}   # (no steps: today's calls, argument for argument)
-    ddim.update(_order_kw(order, steps))
-    ddim.update(_guided_kw(guidance, candidates, 1))
+    ddim = _ddim_kw(steps, order, guidance, candidates, 1)
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
     model = load_model(config_path, checkpoint_path, precision=precision, max_B=2 if guidance is not None else _rounds_capacity(1, candidates),
@@ -901,10 +907,8 @@ def infer_file_batch(prompts, source, config_path: str | None = None, checkpoint
 
     _check_renderer(renderer)
     candidates = _check_candidates(candidates)
-    ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}
-    ddim.update(_order_kw(order, steps))
     prompts = list(prompts)
-    ddim.update(_guided_kw(guidance, candidates, max(1, len(prompts))))
+    ddim = _ddim_kw(steps, order, guidance, candidates, max(1, len(prompts)))
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
     model = load_model(config_path, checkpoint_path, precision=precision,
@@ -1013,9 +1017,7 @@ def write_page_file(text: str, source, config_path: str | None = None, checkpoin
     if not lines:
         raise ValueError("write_page_file: the text holds no word")
     candidates = _check_candidates(candidates)
-    ddim = dict(steps=_check_int("steps", steps, 1)) if steps is not None else {}
-    ddim.update(_order_kw(order, steps))
-    ddim.update(_guided_kw(guidance, candidates, 1))
+    ddim = _ddim_kw(steps, order, guidance, candidates, 1)
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
     style = load_style(source, style_weights)
     model = load_model(config_path, checkpoint_path, precision=precision, max_B=_rounds_capacity(min(len(lines), 64), candidates),

@@ -5,7 +5,7 @@ Shapes, as tests/test_gpu_ddim.py: B = 3, L = 72, Lt = 7 with one padded token, 
 update kernel alone also at 5 x 104 = 520 rows (two full blocks and 8 rows).
 
 What is bit for bit: the update kernel against numpy float32 with the table dhw_dpm_coefs wrote (both kinds, guided and not,
-ragged, in place, hist); order 2 at S <= 2 against order 1; a ragged row against its alone run; a handed-back latent; a second
+ragged, in place, hist); its first-order form against dhw_ddim_update and, guided, against dhw_guide_update(kind = 0); order 2 at S <= 2 against order 1; a ragged row against its alone run; a handed-back latent; a second
 call on a handle against a fresh handle; ``sample`` and ``sample_ddim(order=1)`` before and after; a persistent-step handle.
 
 What has a bound, and where it comes from.  The fp32 denoiser is within TOL["fp32"] of the CPU oracle at every call
@@ -258,6 +258,45 @@ def test_guided_update_on_equal_halves_is_the_plain_update(kind, lens):
     x, hd = torch.cat((base, torch.full((Bq, Lq, 2), float("nan")))).cuda(), hist.cuda()
     _raw(x, torch.cat((e, e_u)).cuda(), hd, row, x, lens_dev, scale=scale)
     assert np.array_equal(_bits(x.cpu().numpy()), _bits(np.concatenate((want, want)))) and np.array_equal(_bits(hd.cpu().numpy()), _bits(want_x0))
+
+
+@pytest.mark.parametrize("lens", [None, [104, 40, 104, 8, 96]])
+def test_guided_first_order_update_is_the_guided_ddim_update(lens):
+    """A kind-1 row with a scale, on two DIFFERENT eps halves: out equals dhw_guide_update(kind = 0) on the same inputs bit for bit
+    in both halves (the two are one kernel template, apart in a template argument: DESIGN.md §41); hist receives the bits of
+    x0 = (base - c1 e) / c0 with e numpy's fp32 combine, 0 past a length.  520 rows: two full blocks and 8 rows; the lengths cut
+    inside blocks, with NaN behind them in base, eps and hist; hist is NaN throughout on entry (a first-order step never reads it)."""
+    Bq, Lq = 5, 104
+    g = torch.Generator().manual_seed(41)
+    base, e, e_u = torch.randn((Bq, Lq, 2), generator=g) * 3, torch.randn((Bq, Lq, 2), generator=g), torch.randn((Bq, Lq, 2), generator=g)
+    assert bool((e != e_u).all())
+    scales = [0.0, 1.0, SCALE, 4.0, 0.25]
+    scale = torch.tensor(scales).cuda()
+    comb = np_combine(e.numpy(), e_u.numpy(), scales)
+    bd, ed, ud = base.clone(), e.clone(), e_u.clone()
+    for b, n in enumerate(lens or []):
+        bd[b, n:], ed[b, n:], ud[b, n:] = float("nan"), float("nan"), float("nan")
+    bd, eps2 = bd.cuda(), torch.cat((ed, ud)).cuda()
+    lens_dev = None if lens is None else torch.tensor(lens, dtype=torch.int32).cuda()
+    tab = _table(dhg_amd.ddim_levels(T, 4), 2)
+    for row in (tab[0], tab[3], np.array([1.0, 3.0, 0.1, 1.0 / 3, 0.7, 0, 0, 0, 0], np.float32)):
+        assert row[0] == 1.0
+        plain = torch.full((2 * Bq, Lq, 2), float("nan")).cuda()
+        rc = _lib.lib().dhw_guide_update(0, bd.data_ptr(), eps2.data_ptr(), None, None if lens is None else lens_dev.data_ptr(), scale.data_ptr(), None, Bq, Lq,
+                                         float(row[1]), float(row[2]), float(row[3]), float(row[4]), plain.data_ptr(), None, _st())
+        assert rc == 0, _lib.lib().dhw_last_error(None).decode()
+        out, out_c = _with_canary(torch.full((2 * Bq, Lq, 2), float("nan")), Bq)
+        hd, hd_c = _with_canary(torch.full((Bq, Lq, 2), float("nan")), Bq)
+        _raw(bd, eps2, hd, row, out, lens_dev, scale=scale)
+        got, want = out.cpu().numpy(), plain.cpu().numpy()
+        want_x0 = np_step(base.numpy(), comb, None, row)[1]
+        assert np.isfinite(want).all() and not np.array_equal(_bits(want[:Bq]), _bits(np_step(base.numpy(), e.numpy(), None, row)[0]))   # (the halves differ: the combine acts)
+        assert np.array_equal(_bits(got[:Bq]), _bits(want[:Bq])) and np.array_equal(_bits(got[Bq:]), _bits(want[Bq:])), row
+        assert np.array_equal(_bits(got[Bq:]), _bits(got[:Bq])), row
+        assert np.array_equal(_bits(hd.cpu().numpy()), _bits(want_x0 if lens is None else _masked(want_x0, lens))), row
+        for b, n in enumerate(lens or []):
+            assert not _bits(got[b, n:]).any() and not _bits(got[Bq + b, n:]).any(), b
+        assert bool((out_c == CANARY).all()) and bool((hd_c == CANARY).all())
 
 
 # ---------------------------------------------------------------- 2. the sampling entries, bit for bit
