@@ -171,7 +171,9 @@ static void conv_block(Ctx& c, int id, const ConvBlockW& w, const void* x, int L
                             : (ch ? launch_convblock_chain(h->prec, q, *chain, c.st) : launch_convblock(h->prec, q, c.st));
       if (e != hipSuccess) c.err = fail(h, DHW_ERR_HIP, "convblock %s: %s", n, hipGetErrorString(e));
     }
-    tap(c, tap_conv(id), out, L, w.cout, out_f32);
+    // (dec1 with the heads fused in keeps its activation in LDS: there is no buffer to read, the tap stays unset)
+    if (q.out) tap(c, tap_conv(id), out, L, w.cout, out_f32);
+    if (pool) tap(c, TAP_POOL1, pool, L / 2, w.cout);   // (enc1 is the only ConvBlock with a pooled side output)
     return;
   }
   if (c.rec) { c.rec_fail = true; return; }
@@ -207,6 +209,7 @@ static void conv_block(Ctx& c, int id, const ConvBlockW& w, const void* x, int L
     run_gemm(c, "convblock.fc_skip", p);
   }
   tap(c, tap_conv(id), out, L, w.cout, out_f32);
+  if (pool) tap(c, TAP_POOL1, pool, L / 2, w.cout);
 }
 
 // the layer's text values are kept as rows [B*Lt, d] (fused bf16 EncoderLayer kernels) instead of transposed [B][d][lpadT]
@@ -326,6 +329,7 @@ static void enc_layer(Ctx& c, int li, const EncLayerW& w, const void* x, int Lk,
     }
     tap(c, tap_el(li, 1), ELB(c, li, x2), Lk, d);
     tap(c, tap_el(li, 0), ELB(c, li, out), Lk, d);
+    if (pool && li < 2) tap(c, li == 0 ? TAP_POOL3 : TAP_POOL5, pool, Lk / 2, d);
     return;
   }
   if (c.rec) { c.rec_fail = true; return; }
@@ -414,6 +418,7 @@ static void enc_layer(Ctx& c, int li, const EncLayerW& w, const void* x, int Lk,
   tap(c, tap_el(li, 1), ELB(c, li, x2), Lk, d);
   tap(c, tap_el(li, 2), ELB(c, li, x3), Lk, d);
   tap(c, tap_el(li, 0), ELB(c, li, out), Lk, d);
+  if (pool && li < 2) tap(c, li == 0 ? TAP_POOL3 : TAP_POOL5, pool, Lk / 2, d);
 }
 
 // sigma-independent prefix of TextStyleEncoder (text_style.py:92-97 up to the LayerNorms; Dropout is identity in eval)

@@ -34,7 +34,9 @@ struct TapSlot { std::string name; Tap t{}; bool set = false; };
 enum { CB_ENC1, CB_ENC2, CB_ENC4, CB_DEC3, CB_DEC2, CB_DEC1, CB_N };
 constexpr const char* kConvName[CB_N] = {"enc1", "enc2", "enc4", "dec3", "dec2", "dec1"};
 // EncoderLayer li: 0 = enc3, 1 = enc5, 2 + i = att_layers.i
-enum { TAP_SIGMA_FFN, TAP_INPUT_DENSE, TAP_TS, TAP_TS_STYLE, TAP_TS_T2, TAP_ATT_DENSE, TAP_UP3, TAP_UP2, TAP_UP1, TAP_CONV0 };
+enum { TAP_SIGMA_FFN, TAP_INPUT_DENSE, TAP_TS, TAP_TS_STYLE, TAP_TS_T2, TAP_ATT_DENSE, TAP_UP3, TAP_UP2, TAP_UP1,
+       TAP_POOL1, TAP_POOL3, TAP_POOL5,   // AvgPool1d side outputs of enc1 / enc3 / enc5: the exact inputs of enc2 / enc4 / att_dense
+       TAP_CONV0 };
 inline int tap_conv(int id) { return TAP_CONV0 + id; }
 inline int tap_el(int li, int which) { return TAP_CONV0 + CB_N + 3 * li + which; }   // which: 0 = layer output, 1 = .x2, 2 = .x3
 

@@ -147,6 +147,9 @@ void build_names(dhw_handle* h) {
   h->taps[TAP_UP3].name = "skip_conv3+up";
   h->taps[TAP_UP2].name = "skip_conv2+up";
   h->taps[TAP_UP1].name = "skip_conv1+up";
+  h->taps[TAP_POOL1].name = "enc1.pool";
+  h->taps[TAP_POOL3].name = "enc3.pool";
+  h->taps[TAP_POOL5].name = "enc5.pool";
   for (int i = 0; i < CB_N; ++i) h->taps[tap_conv(i)].name = kConvName[i];
   for (int li = 0; li < nel; ++li) {
     h->taps[tap_el(li, 0)].name = h->el_name[li];

@@ -12,7 +12,10 @@ extern "C" {
 /* Copy the named intermediate activation of the LAST dhw_forward call to the
  * host as fp32, C-last [B, rows, cols].  Names follow the reference's module
  * names ("enc1", "enc3", "att_layers.0", "text_style_model", "skip_conv3",
- * "sigma_ffn", "input_dense", "att_dense", ...).  Synchronises the device.
+ * "sigma_ffn", "input_dense", "att_dense", ...; "enc1.pool", "enc3.pool",
+ * "enc5.pool" are the AvgPool1d side outputs).  Only buffers the last call
+ * wrote have a name: after dhw_sample, whose dec1 keeps its activation in LDS
+ * for the fused heads, "dec1" is refused.  Synchronises the device.
  * Returns the number of floats written, or a negative dhw_status. */
 int64_t dhw_debug_read(dhw_handle*, const char* name, float* host_dst, int64_t max_floats,
                        int64_t shape_out[3]);
