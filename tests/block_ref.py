@@ -124,10 +124,13 @@ def film(W: Weights, name, x, sig, mut=None):
 def conv3(W: Weights, name, x, mut=None):
     """Conv1d k = 3, 'same' zero padding (cnn.py:33-47) on [B,L,Cin]: out[l] = b + sum_tap w[:,:,tap] x[l-1+tap].
     mut: {"shift": 1} reads x[l+tap] (one row late); {"halo": (rows, side)} reads ZERO instead of the neighbour on `side`
-    (-1 / +1) for each output row in `rows` - the row a tile would miss if its halo were one row short."""
+    (-1 / +1) for each output row in `rows` - the row a tile would miss if its halo were one row short; {"tail": t [B,1,Cin]} reads
+    t instead of zero as the row behind the last one - what a ragged tile reads when its halo row past the sample's end is not zeroed."""
     w = W.w(name + ".weight")
     B, L, _ = x.shape
     xp = torch.nn.functional.pad(x, (0, 0, 1, 1))
+    if mut and "tail" in mut:
+        xp = torch.cat((xp[:, :-1], mut["tail"][:, :1]), dim=1)
     off = 1 if (mut and mut.get("shift")) else 0
     if off:
         xp = torch.nn.functional.pad(xp, (0, 0, 0, off))
@@ -243,15 +246,32 @@ def conv_block(W: Weights, name, x, sig, rnd=exact, out_f32=False, up=None, mut=
     """cnn.py:64-87 on x [B,L,Cin] (already held in the element type), or with the decoder input stage up = (skip_name, low, h).
     Rounding points (convblock_core.h): the staged x of a decoder block :228; SiLU(x) tile :233 / :264 / :314 (silu_piece);
     h1 tile :357 (epilogue_pairs with SiLU -> H1); h2 tile :391; the stored output :480 (store_tiles<T>) - dec1 keeps fp32 (:441).
-    The one-launch-per-GEMM path (sampler/denoiser.cpp:178-208) stores the same three tensors h1, h2, out."""
+    The one-launch-per-GEMM path (sampler/denoiser.cpp:178-208) stores the same three tensors h1, h2, out.
+    WRONG variants of a ragged tile (the sample ends at row n = x.shape[1]; the buffers hold other rows behind it):
+      {"x_tail": t [B,2,Cin], "leak": "conv1"}  conv1 reads x row n from the buffer instead of zero (the x halo is not cut at the end);
+      {"x_tail": t, "leak": "conv2"}            conv2 reads h1 row n as a tile computes it from x rows n - 1 .. n + 1, instead of zero;
+      {"up_tail": (low rows [B,1,C], h rows [B,2,Ch])}   the decoder input stage evaluates x row n from the low-resolution row and
+                                                the skip rows past the end, and conv1 reads it."""
     m = mut or {}
     r = rnd
+    tail, leak = m.get("x_tail"), m.get("leak", "conv1")
     if up is not None:
-        x = up_skip(W, up[0], up[1], up[2], r, m.get("up"))
+        if "up_tail" in m:
+            n = up[2].shape[1]
+            xe = up_skip(W, up[0], torch.cat((up[1], m["up_tail"][0]), dim=1), torch.cat((up[2], m["up_tail"][1]), dim=1), r)
+            x, tail = xe[:, :n], xe[:, n:]
+        else:
+            x = up_skip(W, up[0], up[1], up[2], r, m.get("up"))
     xs = r(silu(x))
     fm = m.get("film")   # (a per-sample FiLM row mix-up hits all three affines of the block: one row pointer, gam = film + b * film_bs)
-    h1 = r(silu(film(W, name + ".affine1", conv3(W, name + ".conv1", xs, m.get("conv1")), sig, fm)))
-    h2 = r(silu(film(W, name + ".affine2", conv3(W, name + ".conv2", h1, m.get("conv2")), sig, fm)))
+    c1, c2 = m.get("conv1"), m.get("conv2")
+    if tail is not None and leak == "conv1":
+        c1 = dict(c1 or {}, tail=r(silu(tail[:, :1])))
+    h1 = r(silu(film(W, name + ".affine1", conv3(W, name + ".conv1", xs, c1), sig, fm)))
+    if tail is not None and leak == "conv2":
+        h1e = r(silu(film(W, name + ".affine1", conv3(W, name + ".conv1", torch.cat((xs, r(silu(tail))), dim=1)), sig, fm)))
+        c2 = dict(c2 or {}, tail=h1e[:, x.shape[1]:x.shape[1] + 1])
+    h2 = r(silu(film(W, name + ".affine2", conv3(W, name + ".conv2", h1, c2), sig, fm)))
     out = film(W, name + ".affine3", lin(W, name + ".fc", h2), sig, fm) + conv3(W, name + ".conv_skip", x)
     return out if out_f32 else r(out)
 

@@ -8,7 +8,8 @@ exactly what ``dhw_debug_read`` returns) plus eps / pen.  Three kinds of switch:
   static : function-static in the library (DHW_CHAIN_CONV, DHW_CONV_TIGHT, DHW_CONV_ASYM, DHW_CONV_RT, DHW_GEMM_W8, DHW_FLAT_TEXT):
            the first launch of the process freezes them, so such a case only means something in a process started with them.
 
-    python tests/blocks_worker.py OUT.npz GROUP [cases-only]      runs every case of static group GROUP in both precisions (and, for the
+    python tests/blocks_worker.py OUT.npz GROUP [cases-only]      runs every case of static group GROUP in both precisions, uniform and once
+                                                     per length set of the case (keys "<case>+r<k>/<prec>/<tap>") (and, for the
                                                      DHW_CHAIN_CONV and DHW_FLAT_TEXT groups, the short sampling run of
                                                      test_conv_chain_switch_... / test_flat_text_switch_does_not_change_the_samples)
                                                      and writes OUT.npz
@@ -16,7 +17,8 @@ exactly what ``dhw_debug_read`` returns) plus eps / pen.  Three kinds of switch:
 ``expect`` lists the bf16 kernel instantiations the launchers select for the case (worked out from launch_convblock /
 launch_convblock_chain in csrc/convblock.hip and pick_bm / launch_pair in csrc/enclayer.hip; profiles/block_variants.txt is the
 traced list).  Notation: cb<BM,CO,NW,OCC,UPC,CH,CIN,TIGHT,PP> = convblock_kernel<bf16_t, ...> with trailing defaults dropped,
-a<DM,BM> = enc_a_kernel, bc<DM,BM,NEXT> = enc_bc_kernel.
+a<DM,BM> = enc_a_kernel, bc<DM,BM,NEXT> = enc_bc_kernel.  The ragged kernels carry the same template names, and the launchers pick
+tiles from B and the padded L only, so a case's list also holds for its ragged runs (run_case(..., lengths=), length_sets()).
 """
 import contextlib
 import os
@@ -98,11 +100,205 @@ CASES = [
     # the group's sampling run, test_flat_text_switch_does_not_change_the_samples)
     _case("w8off_unfused_L208", 208, B=3, Lt=40, pad=11, handle={"DHW_FUSE": "0"}, static={"DHW_GEMM_W8": "0", "DHW_FLAT_TEXT": "1"}, expect=[]),
 ]
+
+
+# ---- the run-time store-policy build (csrc/policy/*_policy.hip; ragged calls: the ragged build reading another word): handles
+# created with DHW_STORE_POLICY = 0 (every class plain) / 42 (every class EARLY) at the shapes and switches of a base case.  The
+# policy decides how a tile is stored, never what: same tiling, same `expect`, and the base case's bits
+def _policy_case(base_id, word):
+    b = next(c for c in CASES if c["id"] == base_id)
+    return dict(b, id=f"pol{word}_{base_id}", handle=dict(b["handle"], DHW_STORE_POLICY=str(word)), base=base_id)
+
+
+CASES += [_policy_case(b, w) for b, w in (("default_L488", 0), ("default_L488", 42), ("default_L208", 0), ("default_L208", 42),
+                                          ("wgs2_L488", 0), ("wgs2_L488", 42), ("enc_bm64_L488", 0))]
 CASE = {c["id"]: c for c in CASES}
 SIGMAS = (0.25, 0.85, 0.55)   # one per sample
 
 # the short sampling run of tests/test_gpu_parity.py::test_sampler_switches_do_not_change_the_samples
 SAMPLE_SHAPE = dict(B=3, L=80, Lt=9, T=7, seed=12, pad=1)
+
+
+# ---------------------------------------------------------------- row tiles per case and level, and the sample ends that probe them
+# A level is the divisor of the stroke length: 1 (enc1, dec1), 2 (enc2, enc3, dec2), 4 (enc4, enc5, dec3), 8 (att_dense, att_layers).
+# The launchers pick tiles from B and the PADDED L only - launch_convblock[_ragged] / pick_bm read p.B, p.L / p.Lk and the switches,
+# never p.lens (csrc/convblock.hip:112-166, csrc/enclayer.hip:100-116, csrc/gemm.hip:395-424; the _ragged files are the same source
+# under DHW_LENS) - so the functions below, which restate those choices, hold for the uniform and the ragged launches alike.
+LEVELS = (1, 2, 4, 8)
+KEY_BLOCK = {"bf16": 64, "fp32": 32}   # self_kbs<T, DM, BM>() (csrc/enc_bc_core.h:45): 64 keys per block on bf16 handles, 32 on fp32 handles
+
+
+def _tiles(n, h):
+    return -(-n // h)
+
+
+def _gemm_rows(n, prec):
+    """gemm_tile_for (csrc/gemm.hip:395-398): the row tile of the one-launch-per-GEMM path."""
+    return 64 if prec == "bf16" and n >= 48 and _tiles(n, 64) * 64 * 4 <= _tiles(n, 32) * 32 * 5 else 32
+
+
+def conv_heights(case, prec="bf16"):
+    """{level: set of OUTPUT rows per ConvBlock tile} (BMO = BM - 2 - 2 TIGHT, or BM for the asymmetric tiles, TIGHT = 2)."""
+    B, L, la, st, ha = case["B"], case["L"], case["launch"], case["static"], case["handle"]
+    if ha.get("DHW_FUSE") == "0":
+        return {lv: {_gemm_rows(L // lv, prec)} for lv in (1, 2, 4)}
+    if prec == "fp32":
+        return {lv: {30} for lv in (1, 2, 4)}                      # convblock_kernel<float, 32, CO, 4>
+    wgs, bm = int(la.get("DHW_CONV_WGS", 256)), la.get("DHW_CONV_BM")
+    fused_up = ha.get("DHW_FUSE_UP") != "0"
+
+    def tight(n, b):
+        return st.get("DHW_CONV_TIGHT") != "0" and _tiles(n, b - 4) == _tiles(n, b - 2)
+
+    big = B * _tiles(L, 62) > wgs
+    full = {62 if la.get("DHW_CONV_OCC") == "2" or not big or bm == "64" else 126}                     # enc1
+    full.add(((124 if tight(L, 128) else 126) if big else 62) if fused_up else (126 if big and bm != "64" else 62))   # dec1
+    n = L // 4
+    asym = st.get("DHW_CONV_ASYM") != "0" and bm is None and B * _tiles(n, 32) <= wgs and _tiles(n, 32) > _tiles(n, 46)
+    bm48 = bm == "48" if bm is not None else (B * _tiles(n, 62) < wgs and B * _tiles(n, 46) <= wgs and _tiles(n, 46) > _tiles(n, 62))
+    quarter = {32 if asym else 46 if bm48 else 30 if bm == "32" else 62}                               # enc4
+    if fused_up:                                                                                       # dec3
+        quarter.add(32 if asym else (44 if tight(n, 48) else 46) if bm48 else 62)
+    else:
+        quarter.add(46 if bm48 else 30 if bm == "32" else 62)
+    return {1: full, 2: {62}, 4: quarter}
+
+
+def enc_heights(case, prec="bf16"):
+    """{level: set of rows per EncoderLayer tile} (pick_bm; the query tile of attn.hip and the GEMM tile on DHW_FUSE=0 handles)."""
+    B, L, la, ha = case["B"], case["L"], case["launch"], case["handle"]
+    out = {}
+    for lv, dm in ((2, 192), (4, 256), (8, 384)):
+        n = L // lv
+        if ha.get("DHW_FUSE") == "0":
+            out[lv] = {_gemm_rows(n, prec), 64}   # attn.hip: 64 query rows per workgroup
+            continue
+        bm = 64
+        if B * _tiles(n, 64) < 256:
+            bm = 32
+        if dm % 128 == 0 and B * _tiles(n, 32) < 256:
+            bm = 16
+        force = la.get(f"DHW_ENC_BM{dm}") or la.get("DHW_ENC_BM")
+        if force:
+            bm = int(force)
+        fits = {192: (64, 32, 16), 256: (64, 32, 16), 384: (32, 16)} if prec == "bf16" else {192: (64, 32), 256: (32, 16), 384: (16,)}
+        while bm > 16 and bm not in fits[dm]:
+            bm //= 2
+        if dm % 128 and bm < 32:
+            bm = 32
+        if dm == 256 and prec == "bf16" and ha.get("DHW_CHAIN") != "0":
+            bm = max(bm, 32)   # bm_min = 32: enc5's second half continues into AvgPool + att_dense + att_layers.0.a (mode 2)
+        out[lv] = {bm}
+    return out
+
+
+def tile_table(case, prec):
+    """{level: sorted row-tile heights in use at that level} on a handle of precision prec."""
+    tab = {lv: set() for lv in LEVELS}
+    for d in (conv_heights(case, prec), enc_heights(case, prec)):
+        for lv, hs in d.items():
+            tab[lv] |= hs
+    return {lv: sorted(hs) for lv, hs in tab.items()}
+
+
+def expect_heights(case):
+    """[(level, rows per tile)] of the bf16 instantiations in the case's ``expect`` list."""
+    out = []
+    for v in case["expect"]:
+        kind, args = v[:-1].split("<")
+        a = [int(x) for x in args.split(",")]
+        if kind == "cb":
+            t = a[7] if len(a) > 7 else 0
+            out.append(({128: 1, 192: 2, 256: 4}[a[1]], a[0] if t == 2 else a[0] - 2 - 2 * t))
+        else:
+            out.append(({192: 2, 256: 4, 384: 8}[a[0]], a[1]))
+    return out
+
+
+def end_classes(case, prec, n):
+    """The (level, tile height, class) triples a sample of n stroke rows realises in this case.  Lengths are multiples of 8, so the
+    sample's end at level lv is e = n / lv, a multiple of g = 8 / lv.  With m0 = k h (k >= 1) a tile start:
+      "a"  e = m0 < L / lv          the next tile exits early; the previous tile's lower halo rows lie past the end
+      "b"  0 < e - m0 = the smallest such distance a multiple of g allows for this h (1 or 2 where g allows, never more than g):
+           the tile holding the end has the minimum of valid rows
+      "c"  m0 - e in {1, 2}         the x halo (2 rows), the h1 halo (1) and the up-stage halo straddle the end inside a live tile
+      "d0" / "d1" / "d-1" at (level, KBS)   the self-attention key count n / lv leaves 0, 1 or KBS - 1 keys in the last key block."""
+    out = set()
+    for lv, hs in tile_table(case, prec).items():
+        e, g, top = n // lv, 8 // lv, case["L"] // lv
+        for h in hs:
+            if e % h == 0 and e < top:
+                out.add((lv, h, "a"))
+            if e > h and e % h and e % h == _least_past(h, g, top):
+                out.add((lv, h, "b"))
+            if any((e + d) % h == 0 and e + d <= top for d in (1, 2)):
+                out.add((lv, h, "c"))
+        if lv > 1:
+            kb = KEY_BLOCK[prec]
+            if e % kb in (0, 1, kb - 1):
+                out.add((lv, kb, "d%d" % (e % kb if e % kb < 2 else -1)))
+    return out
+
+
+def _least_past(h, g, top):
+    d = [e - e // h * h for e in range(g, top + 1, g) if e > h and e % h]
+    return min(d) if d else None
+
+
+def wanted_classes(case, prec):
+    """(realisable, unrealisable): every (level, tile height, class) triple of the case, split by whether ANY multiple of 8 in
+    [8, L] realises it."""
+    every = set()
+    for lv, hs in tile_table(case, prec).items():
+        every |= {(lv, h, c) for h in hs for c in "abc"}
+        if lv > 1:
+            every |= {(lv, KEY_BLOCK[prec], c) for c in ("d0", "d1", "d-1")}
+    can = set()
+    for n in range(8, case["L"] + 1, 8):
+        can |= end_classes(case, prec, n)
+    return can & every, every - can
+
+
+# The LENGTH SETS of the ragged runs: (cases, precision, sets), each set one length per sample.  Chosen against the tile table of that
+# precision's launches (a sample end only probes the tiling of the launch that runs it): the union of a case's sets realises every
+# realisable class of end_classes() for every (level, tile height) of tile_table(), holds the extremes 8 and L, and every set has a
+# sample shorter than L by more than the tallest full-resolution tile, so early-exit tiles exist
+# (tests/test_block_ref_cpu.py::test_length_sets_cover_every_tile_class).  The lists are the smallest covers a search found: 8 - 11
+# lengths where B = 2, hence up to six sets there.
+_LENGTH_SETS = [
+    (("default_L488", "enc_nochain_L488", "cc0_L488", "cc2_rt_L488"), "bf16", [[8, 184], [64, 248], [120, 256], [128, 480], [136, 488]]),
+    (("default_L488", "wgs2_L488", "wgs2_pp1_L488", "wgs2_pp3_L488", "bm64_L488", "enc_bm64_L488", "enc_bm32_nochain_L488", "enc_nochain_L488",
+      "enc_bm32_nl4_L488", "noup_L488", "noup_wgs2_L488", "cc3_wgs2_L488", "cc0_L488", "cc1_noasym_notight_L488", "cc1_notight_wgs2_L488",
+      "cc2_rt_L488", "cc2_rt_wgs2_L488"), "fp32", [[8, 120], [56, 248], [64, 256], [88, 392], [112, 488]]),
+    (("default_L208", "cc3_L208"), "bf16", [[8, 128, 184], [64, 136, 192], [104, 168, 200], [120, 176, 208]]),
+    (("default_L208", "cc3_L208"), "fp32", [[8, 88, 128], [32, 104, 136], [56, 112, 200], [64, 120, 208]]),
+    (("default_nl4",), "bf16", [[8, 64, 128], [16, 120, 136]]),
+    (("default_nl4",), "fp32", [[8, 64, 120], [32, 88, 128], [56, 112, 136]]),
+    (("wgs2_L488", "wgs2_pp1_L488", "wgs2_pp3_L488", "noup_wgs2_L488", "cc3_wgs2_L488", "cc1_notight_wgs2_L488", "cc2_rt_wgs2_L488"), "bf16",
+     [[8, 248], [120, 256], [128, 376], [136, 480], [240, 488]]),
+    (("wgs2_L504", "wgs2_pp2_L504"), "bf16", [[8, 248], [120, 256], [128, 376], [136, 496], [240, 504]]),
+    (("wgs2_L504", "wgs2_pp2_L504"), "fp32", [[8, 120], [56, 128], [64, 256], [88, 392], [112, 504]]),
+    (("wgs2_L128",), "bf16", [[8, 72, 120], [64, 112, 128]]),
+    (("wgs2_L128",), "fp32", [[8, 64, 112], [32, 72, 120], [56, 88, 128]]),
+    (("bm64_L488",), "bf16", [[8, 184], [64, 240], [120, 248], [128, 256], [136, 488]]),
+    (("bm48_L368",), "bf16", [[8, 184], [64, 192], [120, 248], [128, 256], [136, 360], [176, 368]]),
+    (("bm48_L368",), "fp32", [[8, 120], [32, 136], [56, 248], [64, 256], [88, 360], [112, 368]]),
+    (("occ2_L208",), "bf16", [[8, 168], [64, 176], [120, 184], [128, 192], [136, 208]]),
+    (("occ2_L208", "noup_bm32_L208"), "fp32", [[8, 112], [32, 120], [56, 128], [64, 136], [88, 208]]),
+    (("enc_bm64_L488", "enc_bm32_nochain_L488", "enc_bm32_nl4_L488"), "bf16", [[8, 248], [64, 256], [120, 264], [128, 480], [184, 488]]),
+    (("noup_L488", "cc1_noasym_notight_L488"), "bf16", [[8, 248], [64, 256], [136, 368], [176, 376], [184, 488]]),
+    (("noup_bm32_L208",), "bf16", [[8, 128], [64, 136], [112, 184], [120, 208]]),
+    (("unfused_L208", "w8off_unfused_L208"), "bf16", [[8, 128, 200], [104, 136, 208]]),
+    (("unfused_L208", "w8off_unfused_L208"), "fp32", [[8, 128, 200], [120, 136, 208]]),
+]
+POLICY_SET = 1   # a store-policy case runs ONE of its base case's sets
+
+
+def length_sets(case, prec):
+    """The case's length sets on a handle of precision prec: [[length of sample 0, ...], ...]."""
+    base = case.get("base", case["id"])
+    sets = next(s for ids, p, s in _LENGTH_SETS if p == prec and base in ids)
+    return [sets[POLICY_SET]] if "base" in case else sets
 
 
 def static_group(case) -> str:
@@ -166,19 +362,43 @@ def tap_names(nl):
     return n
 
 
-def run_case(case, prec):
-    """One dhw_forward under the case's handle / launch switches -> {tap name: float32 array} + eps, pen."""
+TEXT_SIDE = ("sigma_ffn", "text_style_model", "text_style_model.style", "text_style_model.t2")   # no stroke length: checked by the uniform run
+
+
+def run_case(case, prec, lengths=None):
+    """One dhw_forward under the case's handle / launch switches -> {tap name: float32 array} + eps, pen.
+
+    lengths (one per sample): the ragged call.  Immediately before it a UNIFORM forward at the case's B, L, Lt with NaN in every
+    stroke row runs on the same handle, so every row of every stroke-path workspace buffer holds NaN - the rows the ragged call's
+    early-exit tiles never touch included - and the ragged call's strokes are NaN past each sample's end: whatever a valid row reads
+    from past its sample's end makes it NaN.  "poisoned" says that the uniform forward did come out all NaN.  The stroke-path taps
+    of a ragged run are cut to the rows of its longest sample (rows past a sample's end are stale by design and never inspected);
+    eps / pen stay whole (they are exactly 0 past each end)."""
     from dhg_amd import _lib
     m = model_for(case["nl"], prec, case["handle"])
     inp = case_inputs(case)
+    tx, sg, sv = (torch.from_numpy(inp[k]).cuda() for k in ("text", "sigma", "style"))
+    out = {}
     with environ(case["launch"]):
-        eps, pen, _ = m(*(torch.from_numpy(inp[k]).cuda() for k in ("strokes", "text", "sigma", "style")))
-    out = {"eps": eps.cpu().numpy(), "pen": pen.cpu().numpy()}
+        if lengths is None:
+            eps, pen, _ = m(torch.from_numpy(inp["strokes"]).cuda(), tx, sg, sv)
+        else:
+            assert len(lengths) == case["B"]
+            e0, p0, _ = m(torch.full(inp["strokes"].shape, float("nan")).cuda(), tx, sg, sv)
+            out["poisoned"] = np.array(bool(torch.isnan(e0).all() and torch.isnan(p0).all()))
+            st = inp["strokes"].copy()
+            for b, n in enumerate(lengths):
+                st[b, n:] = np.nan
+            eps, pen, _ = m(torch.from_numpy(st).cuda(), tx, sg, sv, lengths=list(lengths))
+    out.update(eps=eps.cpu().numpy(), pen=pen.cpu().numpy())
     for name in tap_names(case["nl"]):
         try:
-            out[name] = m.debug_read(name).numpy()
+            a = m.debug_read(name).numpy()
         except _lib.DhwError:   # the call did not set this tap
-            pass
+            continue
+        if lengths is not None and name not in TEXT_SIDE:
+            a = a[:, :max(lengths) * a.shape[1] // case["L"]]
+        out[name] = a
     return out
 
 
@@ -212,6 +432,9 @@ def main():
         for prec in ("fp32", "bf16"):
             for k, v in run_case(c, prec).items():
                 res[f"{c['id']}/{prec}/{k}"] = v
+            for r, lens in enumerate(length_sets(c, prec)):   # the ragged runs of the case, in the same child
+                for k, v in run_case(c, prec, lens).items():
+                    res[f"{c['id']}+r{r}/{prec}/{k}"] = v
     if sys.argv[3:] != ["cases-only"]:
         if list(env) == ["DHW_CHAIN_CONV"]:
             for prec in ("fp32", "bf16"):

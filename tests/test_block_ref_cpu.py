@@ -5,7 +5,10 @@
   * the bound discriminates: wrong variants of a block (what a subtly broken kernel computes) exceed the GPU bound -
     FACTOR x the rounding model's worst row - by at least 10 x in the per-row measure;
   * the case table of tests/blocks_worker.py, the traced list profiles/block_variants.txt and the instantiations named in
-    convblock_init() / enclayer_init() agree.
+    convblock_init() / enclayer_init() agree;
+  * the ragged runs: the tile table holds every expected instantiation's tile, the length sets realise every sample-end class
+    against every tile height (the unrealisable ones are a literal), the bound table per sample at the chosen lengths, and
+    ragged wrong variants (a halo row, key or source row read from past a sample's end) exceed the GPU bound tenfold.
 """
 import os
 import re
@@ -289,6 +292,228 @@ def test_case_table_traced_list_and_compiled_instantiations_agree():
     assert len(comp) >= 45, remedy
     assert comp - got == set(UNREACHED), ("named in convblock_init() / enclayer_init() but not traced", sorted(comp - got), remedy)
     assert got <= comp, ("traced but not named in the init lists", sorted(got - comp), remedy)
+
+
+# ---------------------------------------------------------------- ragged runs: the tile table and the length sets
+RAGGED_CASES = [c for c in BW.CASES if "base" not in c]   # (a store-policy case runs one set of its base case: no coverage of its own)
+
+
+def test_tile_table_holds_the_tiles_of_every_expected_instantiation():
+    """tile_table() restates the launchers' row-tile choice; every bf16 instantiation a case's `expect` list names must run at a
+    height the table has for its level, and the table has no height beyond the ones the kernels are compiled for."""
+    for c in BW.CASES:
+        tab = BW.tile_table(c, "bf16")
+        for lv, h in BW.expect_heights(c):
+            assert h in tab[lv], (c["id"], lv, h, tab)
+        for prec in ("bf16", "fp32"):
+            for lv, hs in BW.tile_table(c, prec).items():
+                assert hs and set(hs) <= {16, 30, 32, 44, 46, 62, 64, 124, 126}, (c["id"], prec, lv, hs)
+    assert BW.tile_table(BW.CASE["default_L208"], "bf16") == {1: [62], 2: [32, 62], 4: [32, 44, 46], 8: [16]}
+    assert BW.tile_table(BW.CASE["wgs2_L488"], "bf16") == {1: [124, 126], 2: [32, 62], 4: [32, 62], 8: [16]}
+    assert BW.tile_table(BW.CASE["enc_bm64_L488"], "bf16") == {1: [62], 2: [62, 64], 4: [32, 64], 8: [32]}
+    assert BW.tile_table(BW.CASE["default_L488"], "fp32") == {1: [30], 2: [30, 32], 4: [16, 30], 8: [16]}
+    assert BW.tile_table(BW.CASE["pol42_wgs2_L488"], "bf16") == BW.tile_table(BW.CASE["wgs2_L488"], "bf16")
+
+
+# The (level / tile height or key block: classes) that NO multiple of 8 in [8, L] realises, per precision and padded length L; a
+# case owns the entries whose height its tile table has at that level (classes a b c) and those of its key block (d0 d1 d-1).
+# Why: an end at level lv is a multiple of g = 8 / lv, so "c" (1 or 2 rows before k h) never happens for h = 32 or 64 at g >= 4 and
+# "d1" / "d-1" (key count = 1 or -1 mod KBS) never at g >= 2; the rest are tiles or key blocks no shorter than the level itself
+# (L / 8 = 61 < 64 keys; 4 x 126 = 504; one 124-row tile start inside L = 128 ...).
+UNREALISABLE = {
+    ("bf16", 128): {"1/124": "a c", "1/126": "a c", "2/32": "c", "2/62": "a", "2/64": "d-1 d1", "4/32": "a b", "4/62": "a b c", "4/64": "d-1 d0 d1", "8/16": "a b", "8/64": "d-1 d0"},
+    ("bf16", 136): {"1/62": "a c", "2/32": "c", "2/62": "a", "2/64": "d-1 d1", "4/64": "d-1 d0 d1", "8/64": "d-1 d0"},
+    ("bf16", 208): {"1/62": "a", "1/64": "c", "2/32": "c", "2/62": "a", "2/64": "c d-1 d1", "4/64": "a b c d-1 d0 d1", "8/32": "a b c", "8/64": "a b c d-1 d0"},
+    ("bf16", 368): {"2/32": "c", "2/64": "d-1 d1", "4/64": "d-1 d1", "8/64": "d-1 d0"},
+    ("bf16", 488): {"1/124": "c", "1/126": "a", "2/32": "c", "2/64": "c d-1 d1", "4/64": "d-1 d1", "8/64": "d-1 d0"},
+    ("bf16", 504): {"1/126": "a", "2/32": "c", "2/64": "d-1 d1", "4/64": "d-1 d1", "8/64": "d0"},
+    ("fp32", 128): {"2/32": "c d-1 d1", "4/32": "d-1 d1", "8/16": "a b", "8/32": "d-1 d0"},
+    ("fp32", 136): {"2/32": "c d-1 d1", "4/32": "d-1 d1", "8/32": "d-1 d0"},
+    ("fp32", 208): {"1/32": "c", "2/32": "c d-1 d1", "2/64": "c", "4/32": "d-1 d1", "4/64": "a b c", "8/32": "a b c d-1 d0", "8/64": "a b c"},
+    ("fp32", 368): {"2/32": "c d-1 d1", "4/32": "d-1 d1"},
+    ("fp32", 488): {"2/32": "c d-1 d1", "2/64": "c", "4/32": "d-1 d1"},
+    ("fp32", 504): {"2/32": "c d-1 d1", "4/32": "d-1 d1"},
+}
+
+
+def _owned(case, prec):
+    tab, out = BW.tile_table(case, prec), set()
+    for key, classes in UNREALISABLE[prec, case["L"]].items():
+        lv, h = (int(x) for x in key.split("/"))
+        for cl in classes.split():
+            if (h in tab[lv]) if cl in "abc" else (lv > 1 and h == BW.KEY_BLOCK[prec]):
+                out.add((lv, h, cl))
+    return out
+
+
+def test_length_sets_cover_every_tile_class():
+    """For every case and precision: the union of the length sets realises every class of BW.end_classes() - an end at a tile
+    start, the least distance past one, 1 or 2 rows before one, key counts 0 / 1 / -1 mod the key block - at every level and tile
+    height of the case's tile table, except the triples no multiple of 8 realises, which are exactly the literal above."""
+    used = set()
+    for c in RAGGED_CASES:
+        for prec in ("bf16", "fp32"):
+            sets = BW.length_sets(c, prec)
+            assert 1 <= len(sets) <= 6, (c["id"], prec)
+            tallest = max(BW.tile_table(c, prec)[1])
+            for s in sets:
+                assert len(s) == c["B"] and all(n % 8 == 0 and 8 <= n <= c["L"] for n in s), (c["id"], prec, s)
+                # one sample shorter than L by more than a whole full-resolution tile (L = 128 under 124 / 126-row tiles has no
+                # such length: there, one that ends at or before the start of the second tile): early-exit tiles exist
+                assert min(s) < c["L"] - tallest if c["L"] > 2 * tallest else min(s) <= min(BW.tile_table(c, prec)[1]), (c["id"], prec, s, "no early-exit tile")
+            lens = {n for s in sets for n in s}
+            assert 8 in lens and c["L"] in lens, (c["id"], prec)
+            can, cannot = BW.wanted_classes(c, prec)
+            got = set().union(*(BW.end_classes(c, prec, n) for n in lens))
+            assert can <= got, (c["id"], prec, sorted(can - got))
+            assert cannot == _owned(c, prec), (c["id"], prec, sorted(cannot ^ _owned(c, prec)))
+            used |= {(prec, c["L"], lv, h, cl) for lv, h, cl in cannot}
+    every = {(p, L, int(k.split("/")[0]), int(k.split("/")[1]), cl) for (p, L), d in UNREALISABLE.items() for k, v in d.items() for cl in v.split()}
+    assert used == every, sorted(used ^ every)
+    for c in BW.CASES:
+        if "base" in c:   # a store-policy case: one set, one of its base case's
+            for prec in ("bf16", "fp32"):
+                assert BW.length_sets(c, prec) == [BW.length_sets(BW.CASE[c["base"]], prec)[BW.POLICY_SET]]
+    # the examples of the classes: 248 ends at a 62-row tile start at full and half resolution; 184 two rows before one; 64 two past one
+    d = BW.CASE["default_L488"]
+    assert {(1, 62, "a"), (2, 62, "a")} <= BW.end_classes(d, "bf16", 248) and (1, 62, "c") in BW.end_classes(d, "bf16", 184)
+    assert (1, 62, "b") in BW.end_classes(d, "bf16", 64) and {(4, 32, "a"), (8, 16, "a"), (2, 64, "d0")} <= BW.end_classes(d, "bf16", 128)
+    assert (8, 64, "d1") in BW.end_classes(d, "bf16", 8) and (8, 32, "d-1") in BW.end_classes(d, "fp32", 248)
+
+
+# ---------------------------------------------------------------- ragged runs: the bound table per sample
+_CHAIN = {}
+
+
+def _level(L, t):
+    return L // t.shape[1]
+
+
+def sample_parts(shape, b, n, ext=None, loud=4.0):
+    """(inputs, stand-in taps) of sample b of a GPU case shape cut to n stroke rows - what the ragged reference of
+    tests/test_gpu_blocks.py is evaluated on.  ext > n: the taps keep ext rows and the rows past n, which a ragged call must never
+    read into a valid row, are `loud` times larger (finite stale workspace contents; the GPU test puts NaN there)."""
+    W, inp, taps, _ = bound_table(shape)
+    L, m = shape[1], ext or n
+    i = {k: v[b:b + 1] for k, v in inp.items()}
+    i["strokes"] = i["strokes"][:, :m]
+    d = {}
+    for k, v in taps.items():
+        if k in BW.TEXT_SIDE:
+            d[k] = v[b:b + 1]
+            continue
+        lv = _level(L, v)
+        t = v[b:b + 1, :m // lv].clone()
+        if t.dim() == 3:   # (pen is [B, L])
+            t[:, n // lv:] = R.bf16_round(t[:, n // lv:] * loud)
+        d[k] = t
+    return W, i, d
+
+
+def ragged_bound(shape, b, n):
+    """{tap: (exact rows, model rows)} of sample b at length n: every stroke-path block's rounding model against its exact
+    reference on the same cut inputs."""
+    if (shape, b, n) not in _CHAIN:
+        W, i, d = sample_parts(shape, b, n)
+        out = {}
+        for name in R.block_names(shape[4]):
+            if name in BW.TEXT_SIDE:
+                continue
+            ex = R.block_output(W, name, d.__getitem__, i, R.exact)
+            mo = R.block_output(W, name, d.__getitem__, i, R.bf16_round)
+            for k in ex:
+                out[k] = (ex[k].reshape(-1, ex[k].shape[-1]) if ex[k].dim() == 3 else ex[k].reshape(-1),
+                          mo[k].reshape(-1, mo[k].shape[-1]) if mo[k].dim() == 3 else mo[k].reshape(-1))
+        _CHAIN[shape, b, n] = out
+    return _CHAIN[shape, b, n]
+
+
+RAGGED_SHAPES = sorted({(_shape_key(c), tuple(map(tuple, BW.length_sets(c, "bf16")))) for c in RAGGED_CASES})
+
+
+@pytest.mark.parametrize("shape,sets", RAGGED_SHAPES, ids=["B%d-L%d-Lt%d-pad%d-nl%d-" % s + "+".join("_".join(map(str, x)) for x in ls) for s, ls in RAGGED_SHAPES])
+def test_bound_table_ragged(shape, sets):
+    """test_bound_table at the ragged shapes: the float64 chain per sample at the chosen lengths, the valid rows of a set
+    concatenated as the GPU test does.  The model's error stays in the range of the uniform table, and the reference alone keeps
+    the share of rows measured against the floor at or below 1 % (a length that broke that would be replaced, not the cap)."""
+    print()
+    for r, lens in enumerate(sets):
+        per = [ragged_bound(shape, b, n) for b, n in enumerate(lens)]
+        for k in per[0]:
+            ex, mo = torch.cat([p[k][0] for p in per]), torch.cat([p[k][1] for p in per])
+            row, share = R.row_error(mo, ex)
+            mx = R.max_error(mo, ex)
+            print(f"BOUND {shape} +r{r} {'_'.join(map(str, lens))} {k:18s} row {row:.3e}  max {mx:.3e}  floor {share:.4f}")
+            assert share <= 0.01, (k, lens, share)
+            if k in ("eps", "pen"):
+                assert row == 0 and mx == 0, k
+                continue
+            assert 5e-4 < row < 1e-2, (k, lens, row)
+            assert 5e-4 < mx < 2e-2, (k, lens, mx)
+
+
+# ---------------------------------------------------------------- ragged runs: the bound discriminates
+# (name, block, shape, sample, n, what the broken kernel does).  n is a length of the case's sets whose end lies at / next to a start
+# of the tile height named: the broken row is the sample's last one, whatever the height, so the height only picks the length.
+#   leak conv1 / conv2 / up : ONE halo row past the end is read from the buffer instead of zero (block_ref.conv_block);
+#   ("long", m)             : the whole block runs as if the sample had m > n rows - every halo row, pooled pair, Upsample source and
+#                             self-attention key past the end is live - and its first n rows are kept.  m = 2 n: the end taken with
+#                             the level shift one off; m = the next sample's length: lens[b + 1] for lens[b]; m = L: all Lk keys;
+#   ("drop", KB)            : the last partial block of KB keys of the short sample is left out.
+# The rows past the end are the stand-in taps' own rows, 4 x louder (sample_parts): finite stale values; for the key-block variants
+# the inputs are chosen as for the uniform ones (tail keys 8 x louder).
+RAGGED_WRONG = [
+    ("x_halo_past_end_62", "enc1", S488, 1, 184, "conv1"), ("x_halo_past_end_126", "enc1", S488, 1, 376, "conv1"),
+    ("x_halo_past_end_62_half", "enc2", S488, 0, 120, "conv1"), ("x_halo_past_end_32", "enc4", S488, 0, 120, "conv1"),
+    ("x_halo_past_end_46", "enc4", S208, 1, 176, "conv1"),
+    ("h1_halo_past_end_62", "enc1", S488, 1, 248, "conv2"), ("h1_halo_past_end_124", "dec1", S488, 1, 248, "conv2"),
+    ("h1_halo_past_end_62_half", "dec2", S488, 1, 248, "conv2"), ("h1_halo_past_end_32", "enc4", S488, 0, 128, "conv2"),
+    ("h1_halo_past_end_44", "dec3", S208, 1, 168, "conv2"), ("h1_halo_past_end_30", "enc2", S208, 0, 120, "conv2"),
+    ("up_stage_row_past_end_dec3", "dec3", S488, 0, 120, "up"), ("up_stage_row_past_end_dec2", "dec2", S488, 1, 248, "up"),
+    ("up_stage_row_past_end_dec1", "dec1", S208, 1, 128, "up"),
+    ("self_attention_all_Lk_keys", "att_layers.0", S488, 0, 136, ("long", 488)), ("self_attention_all_Lk_keys_enc3", "enc3", S208, 0, 64, ("long", 208)),
+    ("short_sample_last_key_block_dropped", "enc3", S488, 1, 184, ("drop", 64)), ("short_sample_last_key_block_dropped_f32", "att_layers.1", S488, 1, 392, ("drop", 32)),
+    ("end_with_the_shift_one_level_off", "enc4", S488, 0, 120, ("long", 240)), ("end_with_the_shift_one_level_off_enc5", "enc5", S488, 0, 64, ("long", 128)),
+    ("length_of_the_next_sample", "enc1", S488, 0, 120, ("long", 256)), ("length_of_the_next_sample_dec2", "dec2", S208, 0, 120, ("long", 176)),
+    ("length_of_the_next_sample_att", "att_layers.1", S488, 0, 8, ("long", 184)),
+]
+
+
+@pytest.mark.parametrize("name,block,shape,b,n,what", RAGGED_WRONG, ids=[m[0] for m in RAGGED_WRONG])
+def test_ragged_wrong_variants_exceed_the_gpu_bound_tenfold(name, block, shape, b, n, what):
+    L = shape[1]
+    lv = LEVEL.get(block) or _level(L, bound_table(shape)[2][block])
+    W, i, d = sample_parts(shape, b, n)
+    if isinstance(what, tuple) and what[0] == "drop":
+        src = "enc2" if block == "enc3" else f"att_layers.{int(block[-1]) - 1}"
+        d = _chosen_taps(d, ("tail", src, what[1], 8.0), n // lv)
+        assert (n // lv) % what[1], "no partial key block at this length"
+    ex = R.block_output(W, block, d.__getitem__, i, R.exact)[block]
+    model_row = max(bound_table(shape)[3][block][0], R.row_error(R.block_output(W, block, d.__getitem__, i, R.bf16_round)[block], ex)[0])
+    if isinstance(what, tuple) and what[0] == "drop":
+        bad = R.block_output(W, block, d.__getitem__, i, R.exact, mut={"self": {"drop_tail": what[1]}})[block]
+    elif isinstance(what, tuple):
+        _, i2, d2 = sample_parts(shape, b, n, ext=what[1])
+        bad = R.block_output(W, block, d2.__getitem__, i2, R.exact)[block][:, :ex.shape[1]]
+    else:
+        _, _, d2 = sample_parts(shape, b, n, ext=n + 2 * lv * 2)   # two more rows at the block's level (one at the level below)
+        e = n // lv
+        if what == "up":
+            sk, low, h = {"dec3": ("skip_conv3", "att_layers.1", "enc5"), "dec2": ("skip_conv2", "dec3", "enc3"), "dec1": ("skip_conv1", "dec2", "enc1")}[block]
+            mut = {"up_tail": (d2[low][:, e // 2:e // 2 + 1], d2[h][:, e:e + 2])}
+        else:
+            src = {"enc1": "input_dense", "enc2": "enc1.pool", "enc4": "enc3.pool"}.get(block)
+            if src is None:   # a decoder block: the rows its input stage would compute past the end
+                sk, low, h = {"dec3": ("skip_conv3", "att_layers.1", "enc5"), "dec2": ("skip_conv2", "dec3", "enc3"), "dec1": ("skip_conv1", "dec2", "enc1")}[block]
+                xt = R.up_skip(W, sk, d2[low][:, :e // 2 + 1], d2[h][:, :e + 2], R.bf16_round)[:, e:e + 2]
+            else:
+                xt = d2[src][:, e:e + 2]
+            mut = {"x_tail": xt, "leak": what}
+        bad = R.block_output(W, block, d.__getitem__, i, R.exact, mut=mut)[block]
+    row, _ = R.row_error(bad, ex)
+    bound = FACTOR * model_row
+    print(f"\nMUTATION ragged {name} {block} L={L} sample {b} n={n}: worst row {row:.3e}, GPU bound {bound:.3e}, ratio {row / bound:.1f}")
+    assert row >= 10 * bound, (name, row, bound)
 
 
 # ---------------------------------------------------------------- the GPU module's child-process bookkeeping (no GPU, no process)

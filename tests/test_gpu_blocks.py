@@ -15,6 +15,16 @@ Tolerances
       Outputs that no bf16 value enters between input and output (sigma_ffn, the heads on the float32 dec1 activation) keep
       the absolute float32 bound in both precisions.
 Every figure is printed before it is asserted (pytest -s): "BLOCKS <case> <prec> <tap> gpu_row model_row ratio gpu_max model_max ratio".
+
+Ragged runs ("<case>+r<k>"): every case also runs with per-sample lengths - the ragged build, csrc/ragged/*_ragged.hip, in the same
+tiling, because the launchers pick tiles from B and the padded L only - once per length set of BW.length_sets(), the lengths chosen
+so that sample ends fall at, just past and just before tile starts and key blocks.  The contract is "row b computes what prompt b
+computes alone at L = lengths[b]": the reference is evaluated PER SAMPLE on the taps cut to that sample's rows, the valid rows of
+all samples are concatenated, and the measures and bounds above apply unchanged.  Before each ragged call a uniform all-NaN forward
+fills every stroke-path workspace row with NaN, and the ragged call's strokes are NaN past each end: anything read from past a
+sample's end into a valid row makes it NaN (0 x NaN does not hide).  Every valid row must be finite; eps / pen past each end are
+exactly 0; taps past an end are stale by design and not inspected.  The store-policy cases ("pol<word>_<base case>") are also tied
+bit for bit to their base case's default-policy run.
 """
 import os
 import subprocess
@@ -49,42 +59,81 @@ def weights(nl, prec):
     return _WEIGHTS[nl, prec]
 
 
-def check_case(case, prec, got):
-    """got: {tap name: float32 array} of one dhw_forward.  Every block of the call against its float64 reference."""
-    nl = case["nl"]
-    W = weights(nl, prec)
+def _parts(case, got, lengths):
+    """[(inputs, taps)] the references are evaluated on.  Uniform: the whole batch at once.  Ragged: one part PER SAMPLE b - the
+    contract is "row b computes what prompt b computes alone at L = lengths[b]" - with every stroke-path tap cut to
+    [b : b + 1, : lengths[b] >> level], the strokes to lengths[b] rows, and text, style and sigma the rows of sample b."""
     inp = {k: torch.from_numpy(v) for k, v in BW.case_inputs(case).items()}
     dev = {k: torch.from_numpy(np.asarray(v)).to(torch.float64) for k, v in got.items()}
+    if lengths is None:
+        return [(inp, dev)]
+    parts = []
+    for b, n in enumerate(lengths):
+        d = {}
+        for k, v in dev.items():
+            if k in BW.TEXT_SIDE:
+                d[k] = v[b:b + 1]
+            elif k in ("eps", "pen"):
+                d[k] = v[b:b + 1, :n]
+            else:
+                lv = max(lengths) // v.shape[1]   # (BW.run_case cut the tap to the longest sample's rows at its level)
+                assert lv in BW.LEVELS and v.shape[1] * lv == max(lengths), (k, v.shape, lengths)
+                d[k] = v[b:b + 1, :n // lv]
+        i = {k: v[b:b + 1] for k, v in inp.items()}
+        i["strokes"] = i["strokes"][:, :n]
+        parts.append((i, d))
+    return parts
 
-    def get(name):
-        return dev[name]
+
+def check_case(case, prec, got, lengths=None, tag=None):
+    """got: {tap name: float32 array} of one dhw_forward.  Every block of the call against its float64 reference.  With lengths
+    (a ragged call behind a NaN-poisoned workspace, BW.run_case): the stroke-path blocks per sample, the valid rows of all samples
+    concatenated along the row axis under the SAME measures and bounds; every valid row finite; eps / pen exactly 0 past each end."""
+    nl = case["nl"]
+    W = weights(nl, prec)
+    tag = tag or case["id"]
+    ragged = lengths is not None
+    if ragged:
+        assert bool(got["poisoned"]), "the all-NaN uniform forward in front of the ragged call did not come out all NaN"
+        for b, n in enumerate(lengths):
+            assert not np.asarray(got["eps"])[b, n:].any() and not np.asarray(got["pen"])[b, n:].any(), (tag, b, "eps / pen past the end")
+    parts = _parts(case, {k: v for k, v in got.items() if k != "poisoned"}, lengths)
+    dev = parts[0][1]
 
     fused_up = "skip_conv3+up" not in dev
     names = R.block_names(nl)
     if not fused_up:
         names = names[:names.index("dec3")] + ["skip_conv3+up", "dec3", "skip_conv2+up", "dec2", "skip_conv1+up", "dec1", "heads"]
     seen, failures = set(), []
+
+    def rows_of(t):   # [1 or B, rows, C] -> [rows, C]; pen [B, rows] -> [rows]
+        return t.reshape(-1, t.shape[-1]) if t.dim() == 3 else t.reshape(-1)
+
     for name in names:
-        ref = R.block_output(W, name, get, inp, R.exact, fused_up)
-        model = R.block_output(W, name, get, inp, R.bf16_round, fused_up) if prec == "bf16" else None
-        for key, want in ref.items():
+        if ragged and name in BW.TEXT_SIDE:
+            continue
+        refs = [R.block_output(W, name, d.__getitem__, i, R.exact, fused_up) for i, d in parts]
+        models = [R.block_output(W, name, d.__getitem__, i, R.bf16_round, fused_up) for i, d in parts] if prec == "bf16" else None
+        for key in refs[0]:
             if key not in dev:
                 # sub-taps exist only where the launch writes them (`must` below names the cases in which it does)
-                assert key.endswith((".x3", ".style", ".t2")), f"{case['id']}: the call left no tap '{key}'"
+                assert key.endswith((".x3", ".style", ".t2")), f"{tag}: the call left no tap '{key}'"
                 continue
             seen.add(key)
-            have = dev[key].reshape(want.shape)
-            assert torch.isfinite(have).all(), key
+            want = torch.cat([rows_of(r[key]) for r in refs])
+            have = torch.cat([rows_of(d[key].reshape(r[key].shape)) for (_, d), r in zip(parts, refs)])
+            assert torch.isfinite(have).all(), (tag, key, "a valid row is not finite")
             amax = (have - want).abs().max().item()
             if prec == "fp32" or key in F32_EXACT:
-                print(f"BLOCKS {case['id']} {prec} {key} abs {amax:.3e}")
+                print(f"BLOCKS {tag} {prec} {key} abs {amax:.3e}")
                 if not amax <= TOL_F32:
                     failures.append((key, "abs", amax, TOL_F32))
                 continue
+            mod = torch.cat([rows_of(m[key].reshape(r[key].shape)) for m, r in zip(models, refs)])
             g_row, share = R.row_error(have, want)
-            m_row, _ = R.row_error(model[key].reshape(want.shape), want)
-            g_max, m_max = R.max_error(have, want), R.max_error(model[key].reshape(want.shape), want)
-            print(f"BLOCKS {case['id']} {prec} {key} {g_row:.3e} {m_row:.3e} {g_row / m_row:.2f} {g_max:.3e} {m_max:.3e} {g_max / m_max:.2f} floor {share:.4f}")
+            m_row, _ = R.row_error(mod, want)
+            g_max, m_max = R.max_error(have, want), R.max_error(mod, want)
+            print(f"BLOCKS {tag} {prec} {key} {g_row:.3e} {m_row:.3e} {g_row / m_row:.2f} {g_max:.3e} {m_max:.3e} {g_max / m_max:.2f} floor {share:.4f}")
             if not g_row <= FACTOR * m_row:
                 failures.append((key, "row", g_row, m_row))
             if not g_max <= FACTOR * m_max:
@@ -103,14 +152,51 @@ def check_case(case, prec, got):
         must |= {"text_style_model.style", "text_style_model.t2"}
     if case["handle"].get("DHW_FUSE_UP") == "0" or prec == "fp32":
         must |= {"skip_conv3+up", "skip_conv2+up", "skip_conv1+up"}
+    if ragged:
+        must -= set(BW.TEXT_SIDE)   # (the text side has no stroke length: the uniform run of the case checks it)
     assert must <= seen, sorted(must - seen)
-    assert not failures, (case["id"], prec, failures)
+    assert not failures, (tag, prec, failures)
 
 
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
 @pytest.mark.parametrize("case", INPROC, ids=[c["id"] for c in INPROC])
 def test_every_block_matches_its_float64_reference(case, prec):
     check_case(case, prec, BW.run_case(case, prec))
+
+
+def _ragged_params(cases):
+    return [pytest.param(c, prec, r, id=f"{c['id']}+r{r}-{prec}") for c in cases for prec in ("fp32", "bf16") for r in range(len(BW.length_sets(c, prec)))]
+
+
+@pytest.mark.parametrize("case,prec,r", _ragged_params(INPROC))
+def test_every_block_of_a_ragged_call_matches_its_float64_reference_per_sample(case, prec, r):
+    """The ragged build (csrc/ragged/*_ragged.hip) in the case's tiling, one length set: sample ends at, just past and just before
+    tile starts and key blocks (BW.end_classes), behind a workspace poisoned with NaN."""
+    lens = BW.length_sets(case, prec)[r]
+    check_case(case, prec, BW.run_case(case, prec, lens), lens, f"{case['id']}+r{r}")
+
+
+POLICY = [c for c in INPROC if "base" in c]
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+@pytest.mark.parametrize("case", POLICY, ids=[c["id"] for c in POLICY])
+def test_store_policy_build_stores_the_bits_of_the_default_build(case, prec):
+    """The policy decides how tiles are stored, never what: every tap the base case shares, uniform and ragged, bit for
+    bit against the base case's default-policy run in this process (ragged: the valid rows; eps / pen whole)."""
+    base = BW.CASE[case["base"]]
+    for lens in (None, BW.length_sets(case, prec)[0]):
+        a, b = BW.run_case(base, prec, lens), BW.run_case(case, prec, lens)
+        shared = (set(a) & set(b)) - {"poisoned"}
+        assert {"input_dense", "enc1", "enc1.pool", "enc2", "enc3", "enc3.x2", "enc4", "enc5", "enc5.pool", "att_dense", "att_layers.0", "att_layers.1",
+                "dec3", "dec2", "dec1", "eps", "pen", "text_style_model"} <= shared and set(a) == set(b), sorted(set(a) ^ set(b))
+        for k in sorted(shared):
+            if lens is None or k in BW.TEXT_SIDE or k in ("eps", "pen"):
+                assert np.array_equal(a[k], b[k]), (case["id"], prec, lens, k)
+                continue
+            lv = max(lens) // a[k].shape[1]
+            for s, n in enumerate(lens):
+                assert np.array_equal(a[k][s, :n // lv], b[k][s, :n // lv]), (case["id"], prec, lens, k, s)
 
 
 # ---------------------------------------------------------------- switches frozen at first use: fresh child processes
@@ -160,6 +246,14 @@ def test_every_block_under_a_frozen_switch_matches_its_float64_reference(case, p
     res = child_results(BW.static_group(case), tmp_path_factory)
     pre = f"{case['id']}/{prec}/"
     check_case(case, prec, {k[len(pre):]: v for k, v in res.items() if k.startswith(pre)})
+
+
+@pytest.mark.parametrize("case,prec,r", _ragged_params(STATIC))
+def test_every_block_of_a_ragged_call_under_a_frozen_switch_matches_its_float64_reference_per_sample(case, prec, r, tmp_path_factory):
+    """The ragged runs of the frozen-switch cases, from the SAME child of their group (the worker adds them to its .npz)."""
+    res = child_results(BW.static_group(case), tmp_path_factory)
+    pre = f"{case['id']}+r{r}/{prec}/"
+    check_case(case, prec, {k[len(pre):]: v for k, v in res.items() if k.startswith(pre)}, BW.length_sets(case, prec)[r], f"{case['id']}+r{r}")
 
 
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
