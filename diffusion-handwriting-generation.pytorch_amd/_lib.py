@@ -120,6 +120,11 @@ SIGNATURES = {
     "dhw_set_streams": (C.c_int, [_P, C.c_int]),
     "dhw_debug_plane_reuse": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "dhw_debug_plane_tag": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
+    "dhw_debug_conv_plan": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "dhw_debug_enc_plan": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "dhw_debug_gemm_plan": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)]),
+    "dhw_debug_tile_knobs": (C.c_int, [C.POINTER(C.c_int64)]),
+    "dhw_debug_tile_variants": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     # include/dhw_style.h
     "dhw_style_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "dhw_style_load": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),

@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libdhw_hip.so")
 SOURCES = ["train/sgemm_f32.hip", "train/sgemm_bf16.hip", "train/sgemm_group.hip", "convblock.hip", "ragged/convblock_ragged.hip", "enclayer.hip",
            "ragged/enclayer_ragged.hip", "policy/convblock_policy.hip", "policy/enclayer_policy.hip", "gemm.hip", "ragged/gemm_ragged.hip", "ragged/attn_ragged.hip", "persist.hip", "attn.hip", "misc.hip", "style.hip", "textside.hip",
            "train.hip", "train/sgemm_launch.hip", "train/elementwise.hip", "train/film_table.hip", "train/batch.hip", "render/render.hip", "cond/cond.hip", "score/score.hip", "attnmap/attnmap.hip",
-           "dhw_api.cpp", "dhw_style_api.cpp", "dhw_train_api.cpp",
+           "dhw_api.cpp", "dhw_style_api.cpp", "dhw_train_api.cpp", "plan/tile_knobs.cpp",
            "render/dhw_render_api.cpp", "cond/dhw_cond_api.cpp", "score/dhw_score_api.cpp", "attnmap/dhw_attnmap_api.cpp", "sampler/weights.cpp", "sampler/workspace.cpp", "sampler/denoiser.cpp", "sampler/sample.cpp", "sampler/debug.cpp",
            "step/step.hip", "step/dhw_step_api.cpp", "page/page.hip", "page/dhw_page_api.cpp", "encode/encode.hip", "encode/dhw_encode_api.cpp",
            "prep/prep.hip", "prep/dhw_prep_api.cpp", "train/cond_drop.hip", "moments/moments.hip", "moments/dhw_moments_api.cpp",

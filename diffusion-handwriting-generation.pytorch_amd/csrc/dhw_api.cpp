@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "host/error.h"
+#include "plan/tile_plan.h"
 #include "sampler/handle.h"
 #include "xcd_swizzle.h"
 
@@ -256,6 +257,67 @@ int dhw_debug_plane_tag(const int64_t resident[10], const int64_t call[10], int 
       return t;
     };
     return (int)plane_host_ok(tag(resident), tag(call), PlaneGate{(gates & 1) != 0, (gates & 2) != 0, (gates & 4) != 0});
+  });
+}
+
+// ---------------------------------------------------------------- the tile plan of the stroke kernels (plan/tile_plan.h), no device
+int dhw_debug_conv_plan(int prec, int B, int L, int Cin, int Cout, int up_cin, int chain, const int64_t knobs[7], int out[12]) {
+  DHW_GUARD(nullptr, "dhw_debug_conv_plan", int, {
+    if (!knobs || !out || B < 1 || L < 1 || Cin < 0 || up_cin < 0) return fail(nullptr, DHW_ERR_ARG, "dhw_debug_conv_plan: bad args");
+    ConvKnobs k;
+    k.wgs = (long)knobs[0]; k.bm = (int)knobs[1]; k.occ = (int)knobs[2]; k.pp = (int)knobs[3];
+    k.asym = knobs[4] != 0; k.tight = knobs[5] != 0; k.rt = knobs[6] != 0;
+    const int i = out[0] = convblock_plan(prec, B, L, Cin, Cout, up_cin, chain != 0, k);
+    if (i < 0) return 0;
+    CONV_VARIANTS[i].row(out + 1);
+    return 0;
+  });
+}
+
+int dhw_debug_enc_plan(int prec, int d, int B, int Lk, int bm_min, const int64_t knobs[2], int out[4]) {
+  DHW_GUARD(nullptr, "dhw_debug_enc_plan", int, {
+    if (!knobs || !out || B < 1 || Lk < 1) return fail(nullptr, DHW_ERR_ARG, "dhw_debug_enc_plan: bad args");
+    EncKnobs k;
+    k.bm = (int)knobs[0]; k.wgs = (long)knobs[1];
+    const EncVariant v{prec != PREC_BF16, d, enclayer_plan_bm(prec, d, B, Lk, bm_min, k)};
+    out[0] = enc_find(v); out[1] = v.f32; out[2] = v.DM; out[3] = v.BM;
+    return 0;
+  });
+}
+
+int dhw_debug_gemm_plan(int prec, int B, int L, int N, int n_store, int ln, int out[2]) {
+  DHW_GUARD(nullptr, "dhw_debug_gemm_plan", int, {
+    if (!out || B < 1 || L < 1 || N < 1) return fail(nullptr, DHW_ERR_ARG, "dhw_debug_gemm_plan: bad args");
+    GemmParams p{};
+    p.B = B; p.L = L; p.N = N; p.n_store = n_store; p.ln = ln;
+    gemm_tile_for(prec, p, &out[0], &out[1]);
+    return 0;
+  });
+}
+
+int dhw_debug_tile_knobs(int64_t out[12]) {
+  DHW_GUARD(nullptr, "dhw_debug_tile_knobs", int, {
+    if (!out) return fail(nullptr, DHW_ERR_ARG, "dhw_debug_tile_knobs: null argument");
+    const ConvKnobs c = conv_knobs();
+    const int64_t v[12] = {c.wgs, c.bm, c.occ, c.pp, c.asym, c.tight, c.rt, conv_stagger(0), enc_knobs(192).bm, enc_knobs(256).bm, enc_knobs(384).bm, enc_knobs(192).wgs};
+    std::copy(v, v + 12, out);
+    return 0;
+  });
+}
+
+int dhw_debug_tile_variants(int kind, int i, int out[11]) {
+  DHW_GUARD(nullptr, "dhw_debug_tile_variants", int, {
+    if (kind != 0 && kind != 1) return fail(nullptr, DHW_ERR_ARG, "dhw_debug_tile_variants: kind must be 0 (ConvBlock) or 1 (EncoderLayer)");
+    const int n = kind == 0 ? N_CONV_VARIANTS : N_ENC_VARIANTS;
+    if (!out || i < 0 || i >= n) return n;   // (the length of the list alone)
+    if (kind == 0) {
+      CONV_VARIANTS[i].row(out);
+    } else {
+      const EncVariant& v = ENC_VARIANTS[i];
+      out[0] = v.f32; out[1] = v.DM; out[2] = v.BM;
+      enclayer_variant_facts(i, &out[3], &out[4]);
+    }
+    return n;
   });
 }
 

@@ -1,5 +1,5 @@
 // enclayer.hip — the stroke side of one EncoderLayer (reference model.py:37-58) in TWO launches instead of
-// eight.  A workgroup (8 waves) owns 64 / 32 / 16 stroke rows of one sample (pick_bm: enough tiles for every CU);
+// eight.  A workgroup (8 waves) owns 64 / 32 / 16 stroke rows of one sample (enc_plan_bm, plan/tile_plan.h: enough tiles for every CU);
 // every intermediate of its rows lives in LDS.  The only hand-off through global memory is the one the algorithm
 // forces: self-attention needs the K/V of ALL rows of the sample, so the layer is cut between the q/k/v projection
 // and the attention — and since everything between two self-attentions is row-local, enc_bc<NEXT> goes on with the
@@ -15,7 +15,9 @@
 // one or two heads (attn_core.h).  Workgroup ids are XCD-aware (xcd_swizzle.h): a sample's tiles share one L2.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include "enc_bc_core.h"
+#include "plan/tile_plan.h"
 
 namespace {
 
@@ -95,51 +97,26 @@ hipError_t attr() {
   return hipSuccess;
 }
 
-// row tile: 64 rows when that still gives every CU a workgroup, else 32, else 16 (twice / four times the workgroups)
-template <typename T, int DM>
-int pick_bm(int B, int Lk, int bm_min = 0) {
-  const char* e = getenv(DM == 384 ? "DHW_ENC_BM384" : DM == 256 ? "DHW_ENC_BM256" : "DHW_ENC_BM192");   // experiments only
-  if (!e) e = getenv("DHW_ENC_BM");
-  const int force = e ? atoi(e) : 0;
-  const char* t = getenv("DHW_ENC_WGS");
-  const long target = t ? atol(t) : 256;   // smallest tile count that still gives every CU a workgroup
-  int bm = 64;
-  if ((long)B * ((Lk + 63) / 64) < target) bm = 32;
-  if (DM % 128 == 0 && (long)B * ((Lk + 31) / 32) < target) bm = 16;   // (the 4x2 wave layout of DM=192 needs >= 32 rows)
-  if (force) bm = force;
-  // LDS budget (160 KiB) of both halves: shrink the row tile until the combination fits (fp32 tiles are twice as wide)
-  auto ok = [](int m) { return m == 64 ? fits<T, DM, 64>() : m == 32 ? fits<T, DM, 32>() : fits<T, DM, 16>(); };
-  while (bm > 16 && !ok(bm)) bm /= 2;
-  if (DM % 128 != 0 && bm < 32) bm = 32;
-  if (bm < bm_min) bm = bm_min;
-  return bm == 16 || bm == 32 ? bm : 64;
-}
+template <int F32> using elem_t = std::conditional_t<F32 != 0, float, bf16_t>;
 
-template <typename T, int DM>
-hipError_t launch_bm(const EncLayerParams& p, int which, hipStream_t st, const EncChain* chain) {
-  const int bm = pick_bm<T, DM>(p.B, p.Lk, p.bm_min);
-  if (bm == 16) return launch_pair<T, DM, (DM % 128 == 0 ? 16 : 32)>(p, which, st, chain);
-  return bm == 32 ? launch_pair<T, DM, 32>(p, which, st, chain) : launch_pair<T, DM, 64>(p, which, st, chain);
-}
+// per row of ENC_VARIANTS (plan/tile_plan.h): fits(), and the chain modes has_chain() gives it (bit 0 = mode 1, bit 1 = mode 2)
+#define X(F32, DM, BM) fits<elem_t<F32>, DM, BM>(),
+constexpr bool FIT[] = {DHW_ENC_VARIANTS(X)};
+#undef X
+#define X(F32, DM, BM) has_chain<elem_t<F32>, DM, BM>(1) | has_chain<elem_t<F32>, DM, BM>(2) << 1,
+constexpr int CHAIN_MODES[] = {DHW_ENC_VARIANTS(X)};
+#undef X
+
+int plan_bm(int prec, int d, int B, int Lk, int bm_min) { return enc_plan_bm(prec != PREC_BF16, d, B, Lk, bm_min, enc_knobs(d), FIT); }
 
 }  // namespace
 
 hipError_t enclayer_init() {
   hipError_t e;
-  if ((e = attr<bf16_t, 192, 64>()) != hipSuccess) return e;
-  if ((e = attr<bf16_t, 256, 64>()) != hipSuccess) return e;
-  if ((e = attr<bf16_t, 384, 64>()) != hipSuccess) return e;
-  if ((e = attr<bf16_t, 192, 32>()) != hipSuccess) return e;
-  if ((e = attr<bf16_t, 256, 32>()) != hipSuccess) return e;
-  if ((e = attr<bf16_t, 384, 32>()) != hipSuccess) return e;
-  if ((e = attr<bf16_t, 256, 16>()) != hipSuccess) return e;
-  if ((e = attr<bf16_t, 384, 16>()) != hipSuccess) return e;
-  // fp32 parity mode: the same kernels (exact-f32 MFMA), the row tiles that fit LDS
-  if ((e = attr<float, 192, 64>()) != hipSuccess) return e;
-  if ((e = attr<float, 192, 32>()) != hipSuccess) return e;
-  if ((e = attr<float, 256, 32>()) != hipSuccess) return e;
-  if ((e = attr<float, 256, 16>()) != hipSuccess) return e;
-  return attr<float, 384, 16>();
+#define X(F32, DM, BM) if ((e = attr<elem_t<F32>, DM, BM>()) != hipSuccess) return e;
+  DHW_ENC_VARIANTS(X)
+#undef X
+  return hipSuccess;
 }
 
 bool enclayer_supported(int prec, int d, int heads) {
@@ -150,8 +127,8 @@ bool enclayer_supported(int prec, int d, int heads) {
 // which: 0 = enc_a (cross attention half + q/k/v projection), 1 = enc_bc (self attention + FFN half)
 bool enclayer_chain_supported(int prec, int d, int B, int Lk, int mode, int d_next) {
   if (prec != PREC_BF16) return false;
-  if (mode == 1) return d == 384 && d_next == 384 && pick_bm<bf16_t, 384>(B, Lk) <= 32;
-  if (mode == 2) return d == 256 && d_next == 384 && (Lk & 1) == 0 && pick_bm<bf16_t, 256>(B, Lk, 32) == 32;   // (with bm_min = 32)
+  if (mode == 1) return d == 384 && d_next == 384 && plan_bm(prec, 384, B, Lk, 0) <= 32;
+  if (mode == 2) return d == 256 && d_next == 384 && (Lk & 1) == 0 && plan_bm(prec, 256, B, Lk, 32) == 32;   // (with bm_min = 32)
   return false;
 }
 
@@ -159,17 +136,17 @@ hipError_t launch_enclayer(int prec, const EncLayerParams& p, int which, hipStre
   if (!enclayer_supported(prec, p.d, p.heads) || (p.pool && (p.Lk & 1)) || (chain && chain->mode && which != 1)) return hipErrorInvalidValue;
   if (prec == PREC_F32) {
     if (chain && chain->mode) return hipErrorInvalidValue;
-    switch (p.d) {
-      case 192: return launch_bm<float, 192>(p, which, st, nullptr);
-      case 256: return launch_bm<float, 256>(p, which, st, nullptr);
-      case 384: return launch_bm<float, 384>(p, which, st, nullptr);
-    }
-    return hipErrorInvalidValue;
+    chain = nullptr;
   }
-  switch (p.d) {
-    case 192: return launch_bm<bf16_t, 192>(p, which, st, chain);
-    case 256: return launch_bm<bf16_t, 256>(p, which, st, chain);
-    case 384: return launch_bm<bf16_t, 384>(p, which, st, chain);
+  switch (enc_find({prec != PREC_BF16, p.d, plan_bm(prec, p.d, p.B, p.Lk, p.bm_min)})) {
+#define X(F32, DM, BM) case enc_find({F32, DM, BM}): return launch_pair<elem_t<F32>, DM, BM>(p, which, st, chain);
+    DHW_ENC_VARIANTS(X)
+#undef X
   }
   return hipErrorInvalidValue;
 }
+
+#ifndef DHW_STORE_RT   // (the uniform build alone exports the queries behind dhw_debug_enc_plan / dhw_debug_tile_variants)
+int enclayer_plan_bm(int prec, int d, int B, int Lk, int bm_min, const EncKnobs& k) { return enc_plan_bm(prec != PREC_BF16, d, B, Lk, bm_min, k, FIT); }
+void enclayer_variant_facts(int i, int* fits, int* chain_modes) { *fits = FIT[i], *chain_modes = CHAIN_MODES[i]; }
+#endif

@@ -78,6 +78,32 @@ int dhw_debug_raise(dhw_handle*, int kind);
  * use, bit 2 = fused bf16 text-side kernels serve the call. */
 int dhw_debug_plane_tag(const int64_t resident[10], const int64_t call[10], int gates);
 
+/* The tile plan of the stroke kernels (csrc/plan/tile_plan.h): which compiled kernel variant a launch runs.  None of
+ * these needs a device or a handle.  Variants are reported as their template arguments:
+ *   ConvBlock     {f32, BM, CO, NW, OCC, UPC, CH, CIN, TIGHT, PP, output rows per tile}      (convblock_kernel, csrc/convblock.hip)
+ *   EncoderLayer  {f32, DM, BM}                                                               (enc_a_kernel / enc_bc_kernel, csrc/enclayer.hip)
+ * prec: 0 = bf16, 1 = fp32.
+ *
+ * dhw_debug_conv_plan: the variant of one ConvBlock launch at (B, L, Cin, Cout); up_cin != 0 = a decoder block with the fused input
+ * stage over a skip activation of that width; chain != 0 = the block continues into the next EncoderLayer's first half.  A pure
+ * function of its arguments: the switches come in as knobs = {wgs, bm, occ, pp, asym, tight, rt} (the environment unset:
+ * {256, 0, 0, 0, 1, 1, 0}; bm / occ: 0 = not forced), never from the environment.  out[0] = the variant's index in the compiled
+ * list, or -1 = the launch is refused; out[1..11] = the variant. */
+int dhw_debug_conv_plan(int prec, int B, int L, int Cin, int Cout, int up_cin, int chain, const int64_t knobs[7], int out[12]);
+/* The same for both halves of an EncoderLayer of width d at (B, Lk) with EncLayerParams.bm_min; knobs = {forced row tile, wgs}
+ * ({0, 256}).  out = {index in the compiled list or -1, f32, DM, BM}. */
+int dhw_debug_enc_plan(int prec, int d, int B, int Lk, int bm_min, const int64_t knobs[2], int out[4]);
+/* gemm_tile_for (csrc/gemm.hip) for a GEMM of B samples x L rows x N columns: out = {row tile, column tile}. */
+int dhw_debug_gemm_plan(int prec, int B, int L, int N, int n_store, int ln, int out[2]);
+/* The switch values the library reads from the environment right now: {DHW_CONV_WGS, _BM, _OCC, _PP, _ASYM, _TIGHT, _RT, _STAGGER,
+ * DHW_ENC_BM as it holds for d = 192, 256, 384, DHW_ENC_WGS}.  ASYM / TIGHT / RT are frozen by the first read in the process, this
+ * call included. */
+int dhw_debug_tile_knobs(int64_t out[12]);
+/* Row i of the compiled list of kind 0 (ConvBlock: out = the 11 values above) or 1 (EncoderLayer: out = {f32, DM, BM, whether
+ * fits() holds, i.e. the kernels exist, chain modes of has_chain(): bit 0 = mode 1, bit 1 = mode 2}).  Returns the length of the
+ * list (for any i; out may be NULL), or a negative dhw_status. */
+int dhw_debug_tile_variants(int kind, int i, int out[11]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,11 +14,10 @@ exactly what ``dhw_debug_read`` returns) plus eps / pen.  Three kinds of switch:
                                                      test_conv_chain_switch_... / test_flat_text_switch_does_not_change_the_samples)
                                                      and writes OUT.npz
 
-``expect`` lists the bf16 kernel instantiations the launchers select for the case (worked out from launch_convblock /
-launch_convblock_chain in csrc/convblock.hip and pick_bm / launch_pair in csrc/enclayer.hip; profiles/block_variants.txt is the
-traced list).  Notation: cb<BM,CO,NW,OCC,UPC,CH,CIN,TIGHT,PP> = convblock_kernel<bf16_t, ...> with trailing defaults dropped,
-a<DM,BM> = enc_a_kernel, bc<DM,BM,NEXT> = enc_bc_kernel.  The ragged kernels carry the same template names, and the launchers pick
-tiles from B and the padded L only, so a case's list also holds for its ragged runs (run_case(..., lengths=), length_sets()).
+``expect`` lists the bf16 kernel instantiations the launchers select for the case (the tile plan of csrc/plan/tile_plan.h gives
+exactly these: tests/test_tile_plan_cpu.py; profiles/block_variants.txt is the traced list).  Notation: cb<BM,CO,NW,OCC,UPC,CH,CIN,TIGHT,PP> = convblock_kernel<bf16_t, ...> with trailing defaults dropped,
+a<DM,BM> = enc_a_kernel, bc<DM,BM,NEXT> = enc_bc_kernel.  The ragged kernels carry the same template names, and the plan sees
+B and the padded L only, so a case's list also holds for its ragged runs (run_case(..., lengths=), length_sets()).
 """
 import contextlib
 import os
@@ -33,7 +32,7 @@ if ROOT not in sys.path:
 
 MAX_B, MAX_L, MAX_LT = 3, 512, 40
 
-# the EncoderLayer launches of an unforced call at B <= 3, L <= 512 (pick_bm: every level has fewer than 256 tiles):
+# the EncoderLayer launches of an unforced call at B <= 3, L <= 512 (enc_plan_bm: every level has fewer than 256 tiles):
 # enc2 continues into enc3.a, enc5.bc into AvgPool + att_dense + att_layers.0.a, every attention layer into the next one's first half
 _EL_DEFAULT = ["bc<192,32,0>", "bc<256,32,2>", "bc<384,16,1>", "bc<384,16,0>"]
 _EL_NOCHAIN = ["a<192,32>", "bc<192,32,0>", "a<256,16>", "bc<256,16,0>", "a<384,16>", "bc<384,16,0>"]
@@ -74,7 +73,7 @@ CASES = [
     _case("occ2_L208", 208, launch={"DHW_CONV_OCC": "2"}, expect=["cb<64,128,8,2,0,0,128>", "cb<64,192,8,2,0,0,128>"]),
     # ---- EncoderLayer row tiles.  64 rows: enc3 4 tiles (last 52), enc5 2 (last 58), the attention layers one partial tile of 61;
     # no chain fits a 64-row tile.  DHW_CHAIN=0 handles: every half as its own launch
-    _case("enc_bm64_L488", 488, handle={"DHW_CHAIN": "0"}, launch={"DHW_ENC_BM": "64"}, expect=["a<192,64>", "bc<192,64,0>", "a<256,64>", "bc<256,64,0>", "a<384,32>", "bc<384,32,0>",   # (d = 384 on 64 rows exceeds LDS: pick_bm halves it)
+    _case("enc_bm64_L488", 488, handle={"DHW_CHAIN": "0"}, launch={"DHW_ENC_BM": "64"}, expect=["a<192,64>", "bc<192,64,0>", "a<256,64>", "bc<256,64,0>", "a<384,32>", "bc<384,32,0>",   # (d = 384 on 64 rows exceeds LDS: enc_plan_bm halves it)
                                                                                               "cb<64,192,8,1,0,0,128>", "cb<32,256,8,1,0,0,192,2>"]),
     _case("enc_bm32_nochain_L488", 488, handle={"DHW_CHAIN": "0"}, launch={"DHW_ENC_BM": "32"}, expect=["a<192,32>", "bc<192,32,0>", "a<256,32>", "bc<256,32,0>", "a<384,32>", "bc<384,32,0>"]),
     _case("enc_nochain_L488", 488, handle={"DHW_CHAIN": "0"}, expect=_EL_NOCHAIN + ["cb<64,192,8,1,0,0,128>", "cb<32,256,8,1,0,0,192,2>"]),
@@ -121,75 +120,105 @@ SAMPLE_SHAPE = dict(B=3, L=80, Lt=9, T=7, seed=12, pad=1)
 
 # ---------------------------------------------------------------- row tiles per case and level, and the sample ends that probe them
 # A level is the divisor of the stroke length: 1 (enc1, dec1), 2 (enc2, enc3, dec2), 4 (enc4, enc5, dec3), 8 (att_dense, att_layers).
-# The launchers pick tiles from B and the PADDED L only - launch_convblock[_ragged] / pick_bm read p.B, p.L / p.Lk and the switches,
-# never p.lens (csrc/convblock.hip:112-166, csrc/enclayer.hip:100-116, csrc/gemm.hip:395-424; the _ragged files are the same source
-# under DHW_LENS) - so the functions below, which restate those choices, hold for the uniform and the ragged launches alike.
+# The tiles are the LIBRARY's answer: its tile plan (csrc/plan/tile_plan.h) is pure host logic behind dhw_debug_conv_plan /
+# dhw_debug_enc_plan / dhw_debug_gemm_plan, asked here with the case's switches as explicit arguments - no device, no child process.
+# The plan's inputs hold B and the PADDED L and no per-sample length, and the uniform, ragged and store-policy launchers all call
+# it, so one answer holds for the uniform and the ragged launches alike.
 LEVELS = (1, 2, 4, 8)
 KEY_BLOCK = {"bf16": 64, "fp32": 32}   # self_kbs<T, DM, BM>() (csrc/enc_bc_core.h:45): 64 keys per block on bf16 handles, 32 on fp32 handles
+PREC = {"bf16": 0, "fp32": 1}
+# the ConvBlocks of the model per level: (name, Cin, Cout, width of the skip activation of the fused input stage)
+CONV_BLOCKS = {1: (("enc1", 128, 128, 0), ("dec1", 192, 128, 128)), 2: (("enc2", 128, 192, 0), ("dec2", 256, 192, 192)), 4: (("enc4", 192, 256, 0), ("dec3", 384, 256, 256))}
+ENC_WIDTH = {2: 192, 4: 256, 8: 384}   # enc3, enc5, att_layers
 
 
 def _tiles(n, h):
     return -(-n // h)
 
 
-def _gemm_rows(n, prec):
-    """gemm_tile_for (csrc/gemm.hip:395-398): the row tile of the one-launch-per-GEMM path."""
-    return 64 if prec == "bf16" and n >= 48 and _tiles(n, 64) * 64 * 4 <= _tiles(n, 32) * 32 * 5 else 32
+def _forced(env, name):
+    """A forced-tile switch as the library reads it: 0 = unset, else its value (-1 for a value that reads as 0)."""
+    return 0 if env.get(name) is None else int(env[name]) or -1
+
+
+def conv_knobs(case):
+    """ConvKnobs {wgs, bm, occ, pp, asym, tight, rt} of a case: its launch switches and the ones its process is started with."""
+    la, st = case["launch"], case["static"]
+    return [int(la.get("DHW_CONV_WGS", 256)), _forced(la, "DHW_CONV_BM"), _forced(la, "DHW_CONV_OCC"), int(la.get("DHW_CONV_PP", 0)),
+            int(st.get("DHW_CONV_ASYM", "1") != "0"), int(st.get("DHW_CONV_TIGHT", "1") != "0"), int(st.get("DHW_CONV_RT", "0") != "0")]
+
+
+def enc_knobs(case, dm):
+    la = case["launch"]
+    return [int(la.get(f"DHW_ENC_BM{dm}", la.get("DHW_ENC_BM", 0))), int(la.get("DHW_ENC_WGS", 256))]
+
+
+def conv_plan(prec, B, n, cin, cout, up_cin, chain, knobs):
+    """The library's plan for one ConvBlock launch -> ([BM, CO, NW, OCC, UPC, CH, CIN, TIGHT, PP], output rows per tile), or None = refused."""
+    import ctypes as C
+    from dhg_amd import _lib
+    out = (C.c_int * 12)()
+    assert _lib.lib().dhw_debug_conv_plan(PREC[prec], B, n, cin, cout, up_cin, int(chain), (C.c_int64 * 7)(*knobs), out) == 0
+    assert out[0] < 0 or out[1] == PREC[prec]
+    return None if out[0] < 0 else (list(out[2:11]), out[11])
+
+
+def enc_plan(prec, dm, B, n, bm_min, knobs):
+    """The library's row tile for both halves of an EncoderLayer of width dm."""
+    import ctypes as C
+    from dhg_amd import _lib
+    out = (C.c_int * 4)()
+    assert _lib.lib().dhw_debug_enc_plan(PREC[prec], dm, B, n, bm_min, (C.c_int64 * 2)(*knobs), out) == 0 and out[0] >= 0
+    return out[3]
+
+
+def _gemm_rows(B, n, width, prec):
+    """gemm_tile_for (csrc/gemm.hip): the row tile of the one-launch-per-GEMM path."""
+    import ctypes as C
+    from dhg_amd import _lib
+    out = (C.c_int * 2)()
+    assert _lib.lib().dhw_debug_gemm_plan(PREC[prec], B, n, width, width, 0, out) == 0
+    return out[0]
+
+
+def expect_args(v):
+    """'cb<64,192,8,1,0,1,128>' -> ('cb', [64, 192, 8, 1, 0, 1, 128, 0, 0]) (trailing defaults filled in); a<...> / bc<...> as they are."""
+    kind, args = v[:-1].split("<")
+    a = [int(x) for x in args.split(",")]
+    if kind == "cb":
+        a += [1, 0, 0, 0, 0, 0][len(a) - 3:]
+    return kind, a
+
+
+def conv_chained(case, cout, prec="bf16"):
+    """Whether the case's encoder block of width cout continues into the next EncoderLayer.  That is the launch sequence's decision (DHW_CHAIN,
+    DHW_CHAIN_CONV, convblock_chain_auto: csrc/sampler/denoiser.cpp), which the `expect` list records.  A block the list does not
+    name is asked unchained: the chained and the unchained plan of a shape differ in height only under DHW_CONV_RT, and both cases
+    with that switch name their chained block."""
+    return prec == "bf16" and any(k == "cb" and a[1] == cout and a[5] == 1 for k, a in map(expect_args, case["expect"]))
 
 
 def conv_heights(case, prec="bf16"):
     """{level: set of OUTPUT rows per ConvBlock tile} (BMO = BM - 2 - 2 TIGHT, or BM for the asymmetric tiles, TIGHT = 2)."""
-    B, L, la, st, ha = case["B"], case["L"], case["launch"], case["static"], case["handle"]
+    B, L, ha = case["B"], case["L"], case["handle"]
     if ha.get("DHW_FUSE") == "0":
-        return {lv: {_gemm_rows(L // lv, prec)} for lv in (1, 2, 4)}
-    if prec == "fp32":
-        return {lv: {30} for lv in (1, 2, 4)}                      # convblock_kernel<float, 32, CO, 4>
-    wgs, bm = int(la.get("DHW_CONV_WGS", 256)), la.get("DHW_CONV_BM")
-    fused_up = ha.get("DHW_FUSE_UP") != "0"
+        return {lv: {_gemm_rows(B, L // lv, blocks[0][2], prec)} for lv, blocks in CONV_BLOCKS.items()}
+    fused_up = prec == "bf16" and ha.get("DHW_FUSE_UP") != "0"   # (fp32 handles run the decoder's input stage as launches of its own)
+    return {lv: {conv_plan(prec, B, L // lv, cin, cout, up if fused_up else 0, name.startswith("enc") and conv_chained(case, cout, prec), conv_knobs(case))[1]
+                 for name, cin, cout, up in blocks} for lv, blocks in CONV_BLOCKS.items()}
 
-    def tight(n, b):
-        return st.get("DHW_CONV_TIGHT") != "0" and _tiles(n, b - 4) == _tiles(n, b - 2)
 
-    big = B * _tiles(L, 62) > wgs
-    full = {62 if la.get("DHW_CONV_OCC") == "2" or not big or bm == "64" else 126}                     # enc1
-    full.add(((124 if tight(L, 128) else 126) if big else 62) if fused_up else (126 if big and bm != "64" else 62))   # dec1
-    n = L // 4
-    asym = st.get("DHW_CONV_ASYM") != "0" and bm is None and B * _tiles(n, 32) <= wgs and _tiles(n, 32) > _tiles(n, 46)
-    bm48 = bm == "48" if bm is not None else (B * _tiles(n, 62) < wgs and B * _tiles(n, 46) <= wgs and _tiles(n, 46) > _tiles(n, 62))
-    quarter = {32 if asym else 46 if bm48 else 30 if bm == "32" else 62}                               # enc4
-    if fused_up:                                                                                       # dec3
-        quarter.add(32 if asym else (44 if tight(n, 48) else 46) if bm48 else 62)
-    else:
-        quarter.add(46 if bm48 else 30 if bm == "32" else 62)
-    return {1: full, 2: {62}, 4: quarter}
+def enc_bm_min(case, dm, prec="bf16"):
+    """EncLayerParams.bm_min: 32 for enc5 where its second half continues into AvgPool + att_dense + att_layers.0.a (mode 2)."""
+    return 32 if dm == 256 and prec == "bf16" and case["handle"].get("DHW_CHAIN") != "0" else 0
 
 
 def enc_heights(case, prec="bf16"):
-    """{level: set of rows per EncoderLayer tile} (pick_bm; the query tile of attn.hip and the GEMM tile on DHW_FUSE=0 handles)."""
-    B, L, la, ha = case["B"], case["L"], case["launch"], case["handle"]
-    out = {}
-    for lv, dm in ((2, 192), (4, 256), (8, 384)):
-        n = L // lv
-        if ha.get("DHW_FUSE") == "0":
-            out[lv] = {_gemm_rows(n, prec), 64}   # attn.hip: 64 query rows per workgroup
-            continue
-        bm = 64
-        if B * _tiles(n, 64) < 256:
-            bm = 32
-        if dm % 128 == 0 and B * _tiles(n, 32) < 256:
-            bm = 16
-        force = la.get(f"DHW_ENC_BM{dm}") or la.get("DHW_ENC_BM")
-        if force:
-            bm = int(force)
-        fits = {192: (64, 32, 16), 256: (64, 32, 16), 384: (32, 16)} if prec == "bf16" else {192: (64, 32), 256: (32, 16), 384: (16,)}
-        while bm > 16 and bm not in fits[dm]:
-            bm //= 2
-        if dm % 128 and bm < 32:
-            bm = 32
-        if dm == 256 and prec == "bf16" and ha.get("DHW_CHAIN") != "0":
-            bm = max(bm, 32)   # bm_min = 32: enc5's second half continues into AvgPool + att_dense + att_layers.0.a (mode 2)
-        out[lv] = {bm}
-    return out
+    """{level: set of rows per EncoderLayer tile} (the plan's row tile; the query tile of attn.hip and the GEMM tile on DHW_FUSE=0 handles)."""
+    B, L, ha = case["B"], case["L"], case["handle"]
+    if ha.get("DHW_FUSE") == "0":
+        return {lv: {_gemm_rows(B, L // lv, dm, prec), 64} for lv, dm in ENC_WIDTH.items()}   # attn.hip: 64 query rows per workgroup
+    return {lv: {enc_plan(prec, dm, B, L // lv, enc_bm_min(case, dm, prec), enc_knobs(case, dm))} for lv, dm in ENC_WIDTH.items()}
 
 
 def tile_table(case, prec):
@@ -204,12 +233,9 @@ def tile_table(case, prec):
 def expect_heights(case):
     """[(level, rows per tile)] of the bf16 instantiations in the case's ``expect`` list."""
     out = []
-    for v in case["expect"]:
-        kind, args = v[:-1].split("<")
-        a = [int(x) for x in args.split(",")]
+    for kind, a in map(expect_args, case["expect"]):
         if kind == "cb":
-            t = a[7] if len(a) > 7 else 0
-            out.append(({128: 1, 192: 2, 256: 4}[a[1]], a[0] if t == 2 else a[0] - 2 - 2 * t))
+            out.append(({128: 1, 192: 2, 256: 4}[a[1]], a[0] if a[7] == 2 else a[0] - 2 - 2 * a[7]))
         else:
             out.append(({192: 2, 256: 4, 384: 8}[a[0]], a[1]))
     return out

@@ -4,14 +4,13 @@
   * the bound table: the rounding model's error against the exact reference, per block, at the shapes of the GPU cases;
   * the bound discriminates: wrong variants of a block (what a subtly broken kernel computes) exceed the GPU bound -
     FACTOR x the rounding model's worst row - by at least 10 x in the per-row measure;
-  * the case table of tests/blocks_worker.py, the traced list profiles/block_variants.txt and the instantiations named in
-    convblock_init() / enclayer_init() agree;
+  * the case table of tests/blocks_worker.py, the traced list profiles/block_variants.txt and the library's variant lists
+    (convblock_init() / enclayer_init() expand them) agree;
   * the ragged runs: the tile table holds every expected instantiation's tile, the length sets realise every sample-end class
     against every tile height (the unrealisable ones are a literal), the bound table per sample at the chosen lengths, and
     ragged wrong variants (a halo row, key or source row read from past a sample's end) exceed the GPU bound tenfold.
 """
 import os
-import re
 import sys
 
 import numpy as np
@@ -249,20 +248,21 @@ def _norm(kind, args):
 
 
 def compiled_in():
-    """The bf16 instantiations convblock_init() / enclayer_init() name (fits() / has_chain() decide which EncoderLayer ones exist)."""
-    csrc = os.path.join(ROOT, "diffusion-handwriting-generation.pytorch_amd", "csrc")
-    src = open(os.path.join(csrc, "convblock.hip")).read()
-    body = src[src.index("hipError_t convblock_init()"):src.index("#undef A")]
-    out = {_norm("cb", m.split(",")) for m in re.findall(r"A\(bf16_t,\s*([0-9,\s]+)\)", body)}
-    src = open(os.path.join(csrc, "enclayer.hip")).read()
-    body = src[src.index("hipError_t enclayer_init()"):src.index("bool enclayer_supported")]
-    for dm, bm in re.findall(r"attr<bf16_t,\s*(\d+),\s*(\d+)>", body):
-        dm, bm = int(dm), int(bm)
-        out |= {f"a<{dm},{bm}>", f"bc<{dm},{bm},0>"}
-        if dm == 384 and bm <= 32:
-            out.add(f"bc<{dm},{bm},1>")     # has_chain(1)
-        if dm == 256 and bm == 32:
-            out.add(f"bc<{dm},{bm},2>")     # has_chain(2)
+    """The bf16 instantiations convblock_init() / enclayer_init() name: the library's own variant lists (DHW_CONV_VARIANTS /
+    DHW_ENC_VARIANTS, csrc/plan/tile_plan.h) through dhw_debug_tile_variants, which for an EncoderLayer row also reports the chain
+    modes has_chain() gives it (csrc/enclayer.hip)."""
+    import ctypes as C
+    from dhg_amd import _lib
+    lib, row, out = _lib.lib(), (C.c_int * 11)(), set()
+    for i in range(lib.dhw_debug_tile_variants(0, 0, row)):
+        assert lib.dhw_debug_tile_variants(0, i, row) > i
+        if not row[0]:
+            out.add(_norm("cb", row[1:10]))
+    for i in range(lib.dhw_debug_tile_variants(1, 0, row)):
+        assert lib.dhw_debug_tile_variants(1, i, row) > i
+        f32, dm, bm, _, modes = row[:5]
+        if not f32:
+            out |= {f"a<{dm},{bm}>", f"bc<{dm},{bm},0>"} | {f"bc<{dm},{bm},{m}>" for m in (1, 2) if modes >> (m - 1) & 1}
     return out
 
 
@@ -279,12 +279,11 @@ def traced():
 
 
 def test_case_table_traced_list_and_compiled_instantiations_agree():
-    """A tripwire: compiled_in() reads the init lists with regular expressions and restates has_chain() by hand, and the traced file
-    is a recording.  When a kernel instantiation is added or removed, or has_chain() / fits() change, this fails by design."""
+    """compiled_in() is the library's own report of its variant lists; the traced file is a recording.  When a kernel instantiation
+    is added or removed, or has_chain() / fits() change, this fails by design."""
     remedy = ("profiles/block_variants.txt is a RECORDING: do not edit it or the sets here to match.  Add a case that selects the new "
               "instantiation to tests/blocks_worker.py (or an entry with its reason to UNREACHED), trace tests/test_gpu_blocks.py on the "
-              "GPU again and regenerate the file with tools/block_variants.py (usage in its docstring); if has_chain() / fits() "
-              "changed, bring compiled_in() in line with csrc/enclayer.hip.")
+              "GPU again and regenerate the file with tools/block_variants.py (usage in its docstring).")
     table = {v for c in BW.CASES for v in c["expect"]}
     got = {v for v in traced() if v.startswith(("cb<", "a<", "bc<"))}
     assert table == got, ("case table vs traced list", sorted(table - got), sorted(got - table), remedy)
@@ -299,8 +298,9 @@ RAGGED_CASES = [c for c in BW.CASES if "base" not in c]   # (a store-policy case
 
 
 def test_tile_table_holds_the_tiles_of_every_expected_instantiation():
-    """tile_table() restates the launchers' row-tile choice; every bf16 instantiation a case's `expect` list names must run at a
-    height the table has for its level, and the table has no height beyond the ones the kernels are compiled for."""
+    """tile_table() asks the library's tile plan; every bf16 instantiation a case's `expect` list names must run at a height the
+    table has for its level, and the table has no height beyond the ones the kernels are compiled for.  The literal tables pin one
+    case per tiling family (worked out by hand from the rule: the comments)."""
     for c in BW.CASES:
         tab = BW.tile_table(c, "bf16")
         for lv, h in BW.expect_heights(c):
@@ -313,6 +313,19 @@ def test_tile_table_holds_the_tiles_of_every_expected_instantiation():
     assert BW.tile_table(BW.CASE["enc_bm64_L488"], "bf16") == {1: [62], 2: [62, 64], 4: [32, 64], 8: [32]}
     assert BW.tile_table(BW.CASE["default_L488"], "fp32") == {1: [30], 2: [30, 32], 4: [16, 30], 8: [16]}
     assert BW.tile_table(BW.CASE["pol42_wgs2_L488"], "bf16") == BW.tile_table(BW.CASE["wgs2_L488"], "bf16")
+    # DHW_CONV_BM=64: 62-row tiles at every level; enc3 / enc5 on 32 rows (fewer than 256 tiles; bm_min = 32), the attention layers on 16
+    assert BW.tile_table(BW.CASE["bm64_L488"], "bf16") == {1: [62], 2: [32, 62], 4: [32, 62], 8: [16]}
+    # DHW_CONV_BM=48 at L / 4 = 92: two full 46-row tiles; 44-row tiles would need a third, so dec3 stays at 46
+    assert BW.tile_table(BW.CASE["bm48_L368"], "bf16") == {1: [62], 2: [32, 62], 4: [32, 46], 8: [16]}
+    # DHW_CONV_OCC=2 changes residency, not rows: L / 4 = 52 is two 46-row tiles (enc4) or two 44-row ones (dec3, TIGHT = 1)
+    assert BW.tile_table(BW.CASE["occ2_L208"], "bf16") == {1: [62], 2: [32, 62], 4: [32, 44, 46], 8: [16]}
+    # DHW_CONV_BM=32 without the fused input stage: the run-time-width 30-row tiles for enc4 and dec3 alike
+    assert BW.tile_table(BW.CASE["noup_bm32_L208"], "bf16") == {1: [62], 2: [32, 62], 4: [30, 32], 8: [16]}
+    # DHW_FUSE=0: gemm_tile_for's 64 rows from 48 rows per sample up (208, 104, 52), 32 below (26); attn.hip's 64 query rows
+    assert BW.tile_table(BW.CASE["unfused_L208"], "bf16") == {1: [64], 2: [64], 4: [64], 8: [32, 64]}
+    assert BW.tile_table(BW.CASE["unfused_L208"], "fp32") == {1: [32], 2: [32, 64], 4: [32, 64], 8: [32, 64]}
+    # no asymmetric and no BM - 4 tiles: L / 4 = 122 on three 46-row tiles for enc4 and dec3
+    assert BW.tile_table(BW.CASE["cc1_noasym_notight_L488"], "bf16") == {1: [62], 2: [32, 62], 4: [32, 46], 8: [16]}
 
 
 # The (level / tile height or key block: classes) that NO multiple of 8 in [8, L] realises, per precision and padded length L; a
