@@ -105,6 +105,7 @@ SIGNATURES = {
     "dhw_version": (C.c_char_p, []),
     "dhw_destroy": (None, [_P]),
     "dhw_debug_read": (C.c_int64, [_P, C.c_char_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
+    "dhw_debug_read_plane": (C.c_int64, [_P, C.c_int, C.c_char_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
     "dhw_profile_enable": (C.c_int, [_P, C.c_int]),
     "dhw_profile_reset": (C.c_int, [_P]),
     "dhw_profile_count": (C.c_int, [_P]),

@@ -20,7 +20,25 @@
 // KB = keys per block (32, 64 or 128).  All K and V^T operands of a block are requested up front, so a block
 // costs ONE L2/MALL round trip and its MFMAs / exps are independent; the serial part per block (max/sum
 // shuffles, rescale) is amortised over KB keys.  Keys past Lk are masked to -inf (P = 0 exactly); the V^T rows
-// are zero/finite-padded by the producer, the K rows past Lk are never used unmasked.
+// of the block that holds Lk are read as ZERO past Lk (frag_keep_keys): what lies there is the producer's zero padding only up to
+// its own row tile - behind it come the stale columns of an earlier, longer call, the next channel's row (KB = 128 reaches past
+// lpad) or, behind a sample's last channel, another sample's values - and P = 0 does not cancel an Inf or a NaN.  The K rows
+// past Lk are never used unmasked (their scores are REPLACED by -inf).
+// keep elements [0, n0) of the fragment's first half and [0, n1) of its second, zero the rest
+DHW_DEV void frag_keep_keys(Frag<bf16_t>& f, int n0, int n1) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f.v[i] = i < n0 ? f.v[i] : (bf16_t)0.0f;
+    f.v[4 + i] = i < n1 ? f.v[4 + i] : (bf16_t)0.0f;
+  }
+}
+DHW_DEV void frag_keep_keys(Frag<float>& f, int n0, int n1) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f.lo[i] = i < n0 ? f.lo[i] : 0.f;
+    f.hi[i] = i < n1 ? f.hi[i] : 0.f;
+  }
+}
 template <typename T, int D, int KB>
 DHW_DEV void attn_wave16(const Frag<T> (&qf)[(D + 31) / 32], const T* krow, int ldk, const T* vrow, int lpad,
                          const int64_t* trow, int Lk, f32x4 (&o)[D / 16]) {
@@ -48,6 +66,12 @@ DHW_DEV void attn_wave16(const Frag<T> (&qf)[(D + 31) / 32], const T* krow, int 
         vf[t][pp] = frag_load_halves(vp, vp + 16);
       }
     __builtin_amdgcn_sched_barrier(0);   // keep every operand request of the block ahead of the math
+    if (kb + KB > Lk) {   // (wave-uniform) the block that holds the end of the keys: values past it count as zero, whatever they are
+#pragma unroll
+      for (int t = 0; t < DT; ++t)
+#pragma unroll
+        for (int pp = 0; pp < NPF; ++pp) frag_keep_keys(vf[t][pp], Lk - (kb + 32 * pp + 4 * g), Lk - (kb + 32 * pp + 16 + 4 * g));
+    }
     f32x4 s[NTILE];
 #pragma unroll
     for (int t = 0; t < NTILE; ++t) {

@@ -205,6 +205,10 @@ int64_t dhw_debug_read(dhw_handle* h, const char* name, float* host_dst, int64_t
   DHW_GUARD(h, "dhw_debug_read", int64_t, { return debug_read(h, name, host_dst, max_floats, shape_out); });
 }
 
+int64_t dhw_debug_read_plane(dhw_handle* h, int workspace_slot, const char* name, float* host_dst, int64_t max_floats, int64_t shape_out[3]) {
+  DHW_GUARD(h, "dhw_debug_read_plane", int64_t, { return debug_read_plane(h, workspace_slot, name, host_dst, max_floats, shape_out); });
+}
+
 int dhw_debug_xcd_swizzle(int block_id, int nwg) { return xcd_swizzle(block_id, nwg); }
 
 int dhw_debug_raise(dhw_handle* h, int kind) {

@@ -26,6 +26,51 @@ int64_t debug_read(dhw_handle* h, const char* name, float* host_dst, int64_t max
   return n;
 }
 
+// The all-steps text plane of workspace `slot` as the last dhw_sample* call left it: "text_style_model" [pairs, Lt, 2 c2],
+// "<layer>.k1" [pairs, Lt, d], "<layer>.v1" as stored ([pairs, Lt, d] rows, or V^T [pairs, d, lpadT]).  pairs = every slot the
+// call's chunking wrote (Workspace::plane_pairs).  Reads only: the plane tag and the reuse flag are left alone.
+int64_t debug_read_plane(dhw_handle* h, int slot, const char* name, float* host_dst, int64_t max_floats, int64_t shape_out[3]) {
+  if (!h || !name || !host_dst) return fail(h, DHW_ERR_ARG, "dhw_debug_read_plane: null argument");
+  if (slot < 0 || slot >= (int)h->ws.size()) return fail(h, DHW_ERR_ARG, "dhw_debug_read_plane: no workspace %d", slot);
+  const Workspace& w = h->ws[slot];
+  if (!h->plane || !w.plane_cap) return fail(h, DHW_ERR_STATE, "dhw_debug_read_plane: the handle has no all-steps text plane");
+  if (!w.plane_pairs) return fail(h, DHW_ERR_STATE, "dhw_debug_read_plane: no dhw_sample call has written the plane of workspace %d", slot);
+  if (w.plane_last_gen != h->plane_gen || w.plane_pairs > w.plane_cap)
+    return fail(h, DHW_ERR_STATE, "dhw_debug_read_plane: the last call replayed a graph that writes an earlier allocation of the plane");
+  const std::string nm(name);
+  const void* src = nullptr;
+  int64_t rows = w.plane_Lt, cols = 0;
+  if (nm == "text_style_model") {
+    src = w.tsT.text_out;
+    cols = 2 * h->dims.c2;
+  } else {
+    for (size_t li = 0; li < h->el.size() && li < w.el.size() && !src; ++li) {
+      const EncLayerW& lw = h->el[li];
+      if (nm == h->el_name[li] + ".k1") {
+        src = w.el[li].tT.k1;
+        cols = lw.d;
+      } else if (nm == h->el_name[li] + ".v1") {
+        src = w.el[li].tT.vt1;
+        if (v_rows(h, lw)) cols = lw.d;
+        else { rows = lw.d; cols = h->lpadT; }
+      }
+    }
+  }
+  if (!src) return fail(h, DHW_ERR_ARG, "no plane buffer named %s", name);
+  const int64_t n = w.plane_pairs * rows * cols;
+  if (n > max_floats) return fail(h, DHW_ERR_ARG, "buffer too small for %s", name);
+  if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(h, DHW_ERR_HIP, "sync failed: %s", hipGetErrorString(hipGetLastError()));
+  if (shape_out) { shape_out[0] = w.plane_pairs; shape_out[1] = rows; shape_out[2] = cols; }
+  if (h->prec == PREC_F32) {
+    if (hipMemcpy(host_dst, src, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, DHW_ERR_HIP, "memcpy failed");
+  } else {
+    std::vector<uint16_t> tmp(n);
+    if (hipMemcpy(tmp.data(), src, n * 2, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, DHW_ERR_HIP, "memcpy failed");
+    for (int64_t i = 0; i < n; ++i) host_dst[i] = bf2f(tmp[i]);
+  }
+  return n;
+}
+
 // Tests of the no-throw barrier itself (needs no device, handle may be null): raise a C++ exception INSIDE the guarded body of an
 // entry point, exactly where a std::map::at / vector::resize / new of the host code would.  Must come back as DHW_ERR_INTERNAL.
 int debug_raise(dhw_handle* h, int kind) {

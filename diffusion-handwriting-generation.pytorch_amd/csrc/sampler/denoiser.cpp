@@ -212,8 +212,13 @@ static void conv_block(Ctx& c, int id, const ConvBlockW& w, const void* x, int L
   if (pool) tap(c, TAP_POOL1, pool, L / 2, w.cout);
 }
 
-// the layer's text values are kept as rows [B*Lt, d] (fused bf16 EncoderLayer kernels) instead of transposed [B][d][lpadT]
-static bool v_rows(const dhw_handle* h, const EncLayerW& w) { return h->fuse && h->prec == PREC_BF16 && enclayer_supported(h->prec, w.d, w.heads); }
+// the per-call text keys / values of layer li as dhw_debug_read reports them: v1 as it is stored (handle.h v_rows)
+static void tap_text_kv(Ctx& c, int li, const EncLayerW& w, bool rows) {
+  if (c.planeT) return;   // (the all-steps plane: dhw_debug_read_plane)
+  tap(c, tap_el(li, 3), ELT(c, li, k1), c.Lt, w.d);
+  if (rows) tap(c, tap_el(li, 4), ELT(c, li, vt1), c.Lt, w.d);
+  else tap(c, tap_el(li, 4), ELT(c, li, vt1), w.d, c.h->lpadT);
+}
 
 // model.py:37-58.  The text-side projections (tl, k1, vt1) are produced by enc_layer_text.
 static void enc_layer_text(Ctx& c, int li, const EncLayerW& w) {
@@ -251,6 +256,7 @@ static void enc_layer_text(Ctx& c, int li, const EncLayerW& w) {
     p.vt_lpad = h->lpadT;
     run_gemm(c, "enc.kv_text", p);
   }
+  tap_text_kv(c, li, w, v_rows(h, w));
 }
 
 // parameters of the fused EncoderLayer kernels for layer n (x may be null when the tile is handed over in LDS)
@@ -491,6 +497,7 @@ void text_style_dynamic(Ctx& c) {
       Launch l(h, c.st, "enc.text_fused", n * c.Lt * (2.0 * dt * dd + 4.0 * dd * dd), n * c.Lt * (dt + 2.0 * dd) * h->es + (dt * dd + 2.0 * dd * dd) * h->es, pcall);
       hipError_t e = launch_text_layer(h->prec, t, c.st);
       if (e != hipSuccess) c.err = fail(h, DHW_ERR_HIP, "text layer %s: %s", h->el_name[i].c_str(), hipGetErrorString(e));
+      tap_text_kv(c, (int)i, w, true);   // (text_layer_kernel copies v1 out as rows)
     }
     return;
   }

@@ -38,7 +38,8 @@ enum { TAP_SIGMA_FFN, TAP_INPUT_DENSE, TAP_TS, TAP_TS_STYLE, TAP_TS_T2, TAP_ATT_
        TAP_POOL1, TAP_POOL3, TAP_POOL5,   // AvgPool1d side outputs of enc1 / enc3 / enc5: the exact inputs of enc2 / enc4 / att_dense
        TAP_CONV0 };
 inline int tap_conv(int id) { return TAP_CONV0 + id; }
-inline int tap_el(int li, int which) { return TAP_CONV0 + CB_N + 3 * li + which; }   // which: 0 = layer output, 1 = .x2, 2 = .x3
+constexpr int TAPS_PER_EL = 5;
+inline int tap_el(int li, int which) { return TAP_CONV0 + CB_N + TAPS_PER_EL * li + which; }   // which: 0 = layer output, 1 = .x2, 2 = .x3, 3 = .k1, 4 = .v1
 
 // One full activation workspace.  dhw_sample splits a prompt batch into independent sub-batches, each
 // with its own workspace on its own (captured) stream, so several small kernels are in flight at once.
@@ -63,6 +64,11 @@ struct Workspace {
   float* d_xt = nullptr;   // fp32 sampler state [B*L, 2]
   long cap_B = 0;          // prompts this workspace was sized for
   long plane_cap = 0;      // (steps x prompts) the all-steps text plane (".T" buffers) is sized for
+  // what the last enqueued dhw_sample* call left in the ".T" buffers (dhw_debug_read_plane): the pair slots its chunking wrote,
+  // the row count of a slot, and the plane allocation (plane_gen) the call's launches - or the graph it replayed - wrote into
+  long plane_pairs = 0;
+  int plane_Lt = 0;
+  uint64_t plane_last_gen = 0;
 };
 constexpr int MAX_STREAMS = 8;
 
@@ -221,6 +227,9 @@ struct dhw_handle {
 
 int fail(dhw_handle* h, int code, const char* fmt, ...) noexcept;   // (dhw_api.cpp) records the message, returns code
 
+// the layer's text values are kept as rows [B*Lt, d] (fused bf16 EncoderLayer kernels) instead of transposed [B][d][lpadT]
+inline bool v_rows(const dhw_handle* h, const EncLayerW& w) { return h->fuse && h->prec == PREC_BF16 && enclayer_supported(h->prec, w.d, w.heads); }
+
 // The conditioning block of dhw_sample_cond (include/dhw.h), as the caller passed it: device pointers or null.
 struct CondArgs {
   const float* known;
@@ -281,6 +290,7 @@ int work_impl(dhw_handle* h, int L, int Lt, double* flops_out, double* bytes_out
 
 // ---------------------------------------------------------------- sampler/debug.cpp
 int64_t debug_read(dhw_handle* h, const char* name, float* host_dst, int64_t max_floats, int64_t shape_out[3]);
+int64_t debug_read_plane(dhw_handle* h, int workspace_slot, const char* name, float* host_dst, int64_t max_floats, int64_t shape_out[3]);
 int debug_raise(dhw_handle* h, int kind);
 int debug_randn(dhw_handle* h, uint64_t seed, int64_t first_sample, int B, int L, int iter, float* host_dst);
 int debug_attention_time(dhw_handle* h, int layer, int iters, double* us_with, double* us_without, double* flops_out, void* hip_stream);

@@ -540,6 +540,14 @@ int sample_impl(dhw_handle* h, const char* fn, const int64_t* text, const float*
     if (rc == 0) {   // enqueued: after this call the ".T" buffers hold the plane of call_tag (computed by it, or found valid)
       ++h->plane_calls;
       if (gate.plane && gate.text_fused) h->plane_tag = call_tag;
+      // what dhw_debug_read_plane may copy out: every chunk writes from slot 0 on, so the longest chunk's slots were written
+      const int ns = std::min(h->nstreams, B), per = (B + ns - 1) / ns;
+      for (int s = 0; s < (int)h->ws.size(); ++s) {
+        const int Bs = s < ns ? std::min(per, B - s * per) : 0;
+        h->ws[s].plane_pairs = h->plane && Bs > 0 ? (long)plane_chunk(cond ? cond->t_start : T) * Bs : 0;
+        h->ws[s].plane_Lt = Lt;
+        h->ws[s].plane_last_gen = call_tag.plane_gen;
+      }
     }
     return rc;
   }

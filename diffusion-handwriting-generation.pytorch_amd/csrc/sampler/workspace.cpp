@@ -137,7 +137,7 @@ void build_names(dhw_handle* h) {
   h->el_name.push_back("enc3");
   h->el_name.push_back("enc5");
   for (int i = 0; i < h->dims.num_layers; ++i) h->el_name.push_back("att_layers." + std::to_string(i));
-  h->taps.assign(TAP_CONV0 + CB_N + 3 * nel, TapSlot{});
+  h->taps.assign(TAP_CONV0 + CB_N + TAPS_PER_EL * nel, TapSlot{});
   h->taps[TAP_SIGMA_FFN].name = "sigma_ffn";
   h->taps[TAP_INPUT_DENSE].name = "input_dense";
   h->taps[TAP_TS].name = "text_style_model";
@@ -155,6 +155,8 @@ void build_names(dhw_handle* h) {
     h->taps[tap_el(li, 0)].name = h->el_name[li];
     h->taps[tap_el(li, 1)].name = h->el_name[li] + ".x2";
     h->taps[tap_el(li, 2)].name = h->el_name[li] + ".x3";
+    h->taps[tap_el(li, 3)].name = h->el_name[li] + ".k1";   // the layer's text keys [Lt, d]
+    h->taps[tap_el(li, 4)].name = h->el_name[li] + ".v1";   // its text values as stored: rows [Lt, d] (v_rows) or V^T [d, lpadT]
   }
 }
 

@@ -433,8 +433,20 @@ class DiffusionModel(nn.Module):
         import numpy as np
         shape = (C.c_int64 * 3)()
         cap = self._cap
-        buf = np.empty(cap["max_B"] * max(cap["max_L"], cap["max_Lt"], cap["S"] * 5) * 768, np.float32)
+        # (the widest rows: 768 columns; "<layer>.v1" as V^T holds up to 384 rows of pad32(max_Lt) columns per sample)
+        buf = np.empty(cap["max_B"] * max(cap["max_L"], cap["max_Lt"], cap["S"] * 5, (cap["max_Lt"] + 31) // 32 * 16) * 768, np.float32)
         n = _lib.lib().dhw_debug_read(self._handle, name.encode(), buf.ctypes.data_as(C.POINTER(C.c_float)), buf.size, shape)
+        _lib.check(int(n), self._handle)
+        return torch.from_numpy(buf[:n].reshape(shape[0], shape[1], shape[2]).copy())
+
+    def debug_read_plane(self, name: str, workspace: int = 0, max_pairs: int = 1024) -> torch.Tensor:
+        """The all-steps text plane the last ``sample`` call left in the handle (include/dhw_debug.h dhw_debug_read_plane):
+        "text_style_model", "<layer>.k1" or "<layer>.v1" as float32 [pairs, rows, cols], v1 as the handle stores it."""
+        import numpy as np
+        shape = (C.c_int64 * 3)()
+        cap = self._cap
+        buf = np.empty(max_pairs * max(cap["max_Lt"], (cap["max_Lt"] + 31) // 32 * 32) * 384, np.float32)
+        n = _lib.lib().dhw_debug_read_plane(self._handle, workspace, name.encode(), buf.ctypes.data_as(C.POINTER(C.c_float)), buf.size, shape)
         _lib.check(int(n), self._handle)
         return torch.from_numpy(buf[:n].reshape(shape[0], shape[1], shape[2]).copy())
 

@@ -20,6 +20,21 @@ extern "C" {
 int64_t dhw_debug_read(dhw_handle*, const char* name, float* host_dst, int64_t max_floats,
                        int64_t shape_out[3]);
 
+/* After dhw_forward the text keys and values of every EncoderLayer are activations too: "<layer>.k1" [B, Lt, d] and
+ * "<layer>.v1", reported AS STORED - rows [B, Lt, d] where the fused bf16 EncoderLayer kernels read them, else the
+ * transposed V^T [B, d, lpadT] (lpadT = the handle's max_Lt rounded up to 32; columns >= Lt are not part of the call). */
+
+/* The all-steps text plane of dhw_sample (one slot per (step, prompt) pair), as the LAST dhw_sample* call left it in
+ * workspace `workspace_slot` (0 unless dhw_set_streams split the batch), copied to the host as fp32 [pairs, rows, cols].
+ * Names: "text_style_model" [pairs, Lt, 2 c2], "<layer>.k1" [pairs, Lt, d], "<layer>.v1" (as above: [pairs, Lt, d] or
+ * [pairs, d, lpadT]).  Slot k * Bs + b of a chunk of up to 64 steps holds step (first + chunk start + k) of prompt b; a later
+ * chunk overwrites the slots from 0 on, and every slot the call's chunking wrote is returned: pairs = min(64, steps run) * Bs.
+ * DHW_ERR_STATE where the handle keeps no plane (DHW_PLANE=0), no sample call has run, or the last call replayed a graph
+ * captured before the plane was re-allocated.  Synchronises the device; reads only (the plane-reuse tag is left alone).
+ * Returns the number of floats written, or a negative dhw_status. */
+int64_t dhw_debug_read_plane(dhw_handle*, int workspace_slot, const char* name, float* host_dst, int64_t max_floats,
+                             int64_t shape_out[3]);
+
 /* Per-kernel timing: when enabled every launch is bracketed by HIP events on
  * the launch stream (graph replay is disabled while profiling). */
 int dhw_profile_enable(dhw_handle*, int on);

@@ -144,6 +144,8 @@ def encoder_layer(sd, name, x, text, sig, mask, heads: int, pos_factor, taps=Non
         taps[name + ".x2"] = x2
         taps[name + ".x3"] = x3
         taps[name] = out
+        taps[name + ".k1"] = _lin(sd, name + ".mha.wk", t_pe)   # the layer's text keys and values as mha() projects them
+        taps[name + ".v1"] = _lin(sd, name + ".mha.wv", t)
     return out
 
 

@@ -191,18 +191,42 @@ def attention(q, k, v, heads, mask=None, rnd=exact, mut=None):
     True = padded token.  Rounding model: the probabilities enter the PV product as bf16 (attn_core.h:317 frag_from_f32 of
     exp2(s - m), un-normalised; the row sum psum is taken from the unrounded values, attn_core.h:313-315) and the division by
     the sum happens on the fp32 accumulator (enc_a_core.h:319-323, enc_bc_core.h:218-222).
-    mut: {"drop_tail": KB} leaves out the last partial block of KB keys; {"unmask": True} attends padded keys."""
+    mut: {"drop_tail": KB} leaves out the last partial block of KB keys; {"unmask": True} attends padded keys;
+      {"drop_key": j} leaves out key j (j < 0: from the end); {"unmask_from": j0} ignores the padding mask for keys >= j0;
+      {"alias": KB} keys and values j >= KB are those of j - KB (a later key block reads the first block's staged tile);
+      {"extra_key": (k_row [d], v_row [d])} one more key behind the last (a padded tile row the mask does not cut);
+      {"vt_stride": (lpad, wrong)} the values are read from their transposed store [d][lpad] (zero past Lk) with row stride `wrong`."""
+    m = mut or {}
     B, Lq, d = q.shape
+    if "alias" in m and k.shape[1] > m["alias"]:
+        kb, n = m["alias"], k.shape[1]
+        k = torch.cat((k[:, :kb], k[:, :n - kb]), dim=1)
+        v = torch.cat((v[:, :kb], v[:, :n - kb]), dim=1)
+    if "extra_key" in m:
+        k = torch.cat((k, m["extra_key"][0].expand(B, 1, d)), dim=1)
+        v = torch.cat((v, m["extra_key"][1].expand(B, 1, d)), dim=1)
+    if "vt_stride" in m:
+        lpad, wrong = m["vt_stride"]
+        vt = torch.zeros(B, d * lpad + lpad, dtype=F64)
+        vt[:, :d * lpad].view(B, d, lpad)[:, :, :v.shape[1]] = v.transpose(1, 2)
+        idx = torch.arange(d)[:, None] * wrong + torch.arange(v.shape[1])[None, :]
+        v = vt[:, idx].transpose(1, 2)
     Lk = k.shape[1]
     D = d // heads
     qh = q.reshape(B, Lq, heads, D).transpose(1, 2)
     kh = k.reshape(B, Lk, heads, D).transpose(1, 2)
     vh = v.reshape(B, Lk, heads, D).transpose(1, 2)
     s = qh @ kh.transpose(-1, -2) / math.sqrt(D)
-    if mask is not None and not (mut and mut.get("unmask")):
-        s = s + mask.to(F64)[:, None, None, :] * -1e9
-    if mut and mut.get("drop_tail") and Lk % mut["drop_tail"]:
-        keep = Lk - Lk % mut["drop_tail"]
+    if mask is not None and not m.get("unmask"):
+        mk = mask.to(F64).clone()
+        if "unmask_from" in m:
+            mk[:, m["unmask_from"]:] = 0
+        s = s + mk[:, None, None, :] * -1e9
+    if "drop_key" in m:
+        s = s.clone()
+        s[..., m["drop_key"]] = -math.inf
+    if m.get("drop_tail") and Lk % m["drop_tail"]:
+        keep = Lk - Lk % m["drop_tail"]
         s, vh = s[..., :keep], vh[:, :, :keep]
     e = torch.exp(s - s.amax(dim=-1, keepdim=True))
     o = (rnd(e) @ vh) / e.sum(dim=-1, keepdim=True)
@@ -278,15 +302,32 @@ def conv_block(W: Weights, name, x, sig, rnd=exact, out_f32=False, up=None, mut=
 
 # ------------------------------------------------------------------------------------------------ EncoderLayer
 class LayerOut:
-    def __init__(self, out, x2, x3):
-        self.out, self.x2, self.x3 = out, x2, x3
+    def __init__(self, out, x2, x3, k1=None, v1=None):
+        self.out, self.x2, self.x3, self.k1, self.v1 = out, x2, x3, k1, v1
+
+
+def text_half(W: Weights, name, text, sig, rnd=exact, pe_args="f32", mut=None):
+    """The text half of an EncoderLayer (model.py:38-42) -> (k1, v1) [B,Lt,d] as the layer stores them: tl = FiLM0(LN(text_dense(
+    SiLU(text)))), k1 = Wk(tl + PE), v1 = Wv tl.  Rounding points: textside.hip text_layer_kernel - SiLU(text) :374, tl :404 (the LDS
+    operand tile of the two projections), k1 :432, v1 :453 (both staged in the element type and copied out); the generic path
+    (sampler/denoiser.cpp enc_layer_text :224-252) stores the same three tensors, with SiLU applied to the staged operand.
+    mut: {"pe_clamp": True} WRONG: token Lt - 1 gets the position row of token Lt - 2 (the clamp of :431 one row early)."""
+    r = rnd
+    Lt = text.shape[1]
+    d = W.w(name + ".mha.wk.weight").shape[0]
+    tl = r(film(W, name + ".affine0", layer_norm(lin(W, name + ".text_dense", r(silu(text)))), sig))
+    pb = pos_bias(W, name + ".mha.wk", Lt, d, 1.0, pe_args)
+    if mut and mut.get("pe_clamp") and Lt > 1:
+        pb = torch.cat((pb[:Lt - 1], pb[Lt - 2:Lt - 1]))
+    k1 = r(lin(W, name + ".mha.wk", tl) + pb)
+    v1 = r(lin(W, name + ".mha.wv", tl))
+    return k1, v1
 
 
 def encoder_layer(W: Weights, name, x, text, sig, mask, heads_n, pos_factor, rnd=exact, pe_args="f32", mut=None):
     """model.py:35-58.  x [B,Lk,d] stroke rows, text [B,Lt,2 c2] the TextStyleEncoder output, mask [B,Lt] bool (True = padded).
     Rounding points:
-      text half (textside.hip text_layer_kernel; generic: sampler/denoiser.cpp:216-250): SiLU(text) :374, tl (the LDS operand
-        tile behind :384), k1 :416, v1 :440;
+      text half: text_half() above - its k1 / v1 are outputs of the layer too ("<layer>.k1", "<layer>.v1");
       enc_a (enc_a_core.h): q1 :279, a1 :322-323, x2 :364, [q2 | k2 | v2] :415 / :437; probabilities attn_core.h:317;
       enc_bc (enc_bc_core.h): a2 :221-222, x3 :281, SiLU(x3) :283-284 (of the UNROUNDED x3), FFN hidden :316, out :350.
     LayerNorm statistics, FiLM and residual sums are fp32 on the accumulators (ln_rows)."""
@@ -295,9 +336,7 @@ def encoder_layer(W: Weights, name, x, text, sig, mask, heads_n, pos_factor, rnd
     d = x.shape[-1]
     Lk, Lt = x.shape[1], text.shape[1]
     pf = m.get("pos_factor", pos_factor)   # WRONG variant: another layer's factor
-    tl = r(film(W, name + ".affine0", layer_norm(lin(W, name + ".text_dense", r(silu(text)))), sig))
-    k1 = r(lin(W, name + ".mha.wk", tl) + pos_bias(W, name + ".mha.wk", Lt, d, 1.0, pe_args))
-    v1 = r(lin(W, name + ".mha.wv", tl))
+    k1, v1 = text_half(W, name, text, sig, r, pe_args, m.get("text"))
     q1 = r(lin(W, name + ".mha.wq", x) + pos_bias(W, name + ".mha.wq", Lk, d, pf, pe_args))
     a1 = r(attention(q1, k1, v1, heads_n, mask, r, m.get("cross")))
     x2 = r(film(W, name + ".affine1", layer_norm(lin(W, name + ".mha.dense", a1)), sig) + x)
@@ -309,7 +348,7 @@ def encoder_layer(W: Weights, name, x, text, sig, mask, heads_n, pos_factor, rnd
     x3 = r(x3u)
     f = r(silu(lin(W, name + ".ffn.1", r(silu(x3u)))))
     out = r(film(W, name + ".affine3", layer_norm(lin(W, name + ".ffn.3", f) + x3), sig))
-    return LayerOut(out, x2, x3)
+    return LayerOut(out, x2, x3, k1, v1)
 
 
 # ------------------------------------------------------------------------------------------------ TextStyleEncoder
@@ -318,12 +357,15 @@ class TextOut:
         self.out, self.style, self.t2 = out, style, t2
 
 
-def text_style_encoder(W: Weights, text, style, sig, rnd=exact):
+def text_style_encoder(W: Weights, text, style, sig, rnd=exact, mut=None):
     """text_style.py:91-104 (eval) from the call's own inputs: token ids [B,Lt] and the float32 style vector [B,S,1280].
     Rounding points: the style cast (misc.hip cast kernel), SiLU(style) operand / hidden layer / LayerNorm output of the two
     style GEMMs and the embedding LayerNorm (sampler/denoiser.cpp:420-441: each a stored activation); then textside.hip
     text_style_kernel: s and t1 :125-126 (stage_film_384), V^T :183, K :199, q :211, the attention output :232, t1 again as the
-    residual :257, t2 :270, SiLU of the rounded t2 :272-273, the FFN hidden layer :300, out :320."""
+    residual :257, t2 :270, SiLU of the rounded t2 :272-273, the FFN hidden layer :300, out :320.
+    mut (WRONG variants of the style attention, attn_once's mask :48 and the zero fill of V^T :183 / of the staged rows :114):
+      {"drop_last_key": True} key S5 - 1 is masked away; {"unmasked_pad": True} key S5 - a zero-filled style row, so K is the
+      projection's bias and V is 0 - takes part in the softmax."""
     r = rnd
     n = "text_style_model"
     B, S, C = style.shape
@@ -334,7 +376,12 @@ def text_style_encoder(W: Weights, text, style, sig, rnd=exact):
     q = r(lin(W, n + ".mha.wq", t1))
     k = r(lin(W, n + ".mha.wk", s))
     v = r(lin(W, n + ".mha.wv", s))
-    mh = r(attention(q, k, v, 8, None, r))
+    am = None
+    if mut and mut.get("drop_last_key"):
+        am = {"drop_key": -1}
+    elif mut and mut.get("unmasked_pad"):
+        am = {"extra_key": (r(W.w(n + ".mha.wk.bias")), torch.zeros(q.shape[-1], dtype=F64))}
+    mh = r(attention(q, k, v, 8, None, r, am))
     t2 = r(film(W, n + ".affine3", layer_norm(t1 + lin(W, n + ".mha.dense", mh)), sig))
     hid2 = r(silu(lin(W, n + ".text_ffn.1", r(silu(t2)))))
     out = r(film(W, n + ".affine4", layer_norm(lin(W, n + ".text_ffn.3", hid2)), sig))
@@ -365,7 +412,7 @@ def block_output(W: Weights, name, get, inputs, rnd=exact, fused_up=True, pe_arg
     if name == "sigma_ffn":
         return {name: sigma_ffn(W, inputs["sigma"])}
     if name == "text_style_model":
-        o = text_style_encoder(W, text, inputs["style"], sig, rnd)
+        o = text_style_encoder(W, text, inputs["style"], sig, rnd, mut)
         return {name: o.out, name + ".style": o.style, name + ".t2": o.t2}
     if name == "input_dense":
         return {name: input_dense(W, inputs["strokes"].to(F64), rnd)}
@@ -382,7 +429,7 @@ def block_output(W: Weights, name, get, inputs, rnd=exact, fused_up=True, pe_arg
             src = {"enc3": "enc2", "enc5": "enc4"}[name]
         hn, pf = layer_geom(name)
         o = encoder_layer(W, name, get(src), get("text_style_model"), sig, mask, hn, pf, rnd, pe_args, mut)
-        return {name: o.out, name + ".x2": o.x2, name + ".x3": o.x3}
+        return {name: o.out, name + ".x2": o.x2, name + ".x3": o.x3, name + ".k1": o.k1, name + ".v1": o.v1}
     if name == "att_dense":
         return {name: att_dense(W, get("enc5.pool"), rnd)}
     dec = {"dec3": ("skip_conv3", f"att_layers.{nl - 1}" if nl else "att_dense", "enc5"), "dec2": ("skip_conv2", "dec3", "enc3"),

@@ -38,8 +38,13 @@ _EL_DEFAULT = ["bc<192,32,0>", "bc<256,32,2>", "bc<384,16,1>", "bc<384,16,0>"]
 _EL_NOCHAIN = ["a<192,32>", "bc<192,32,0>", "a<256,16>", "bc<256,16,0>", "a<384,16>", "bc<384,16,0>"]
 
 
-def _case(id, L, B=2, Lt=23, pad=3, nl=2, handle=None, launch=None, static=None, expect=()):
-    return dict(id=id, B=B, L=L, Lt=Lt, pad=pad, nl=nl, handle=handle or {}, launch=launch or {}, static=static or {}, expect=list(expect))
+def _case(id, L, B=2, Lt=23, pad=3, nl=2, handle=None, launch=None, static=None, expect=(), S=14, tight=None, weights=None, style=None):
+    """S: style rows of the call (and of the handle: S5 = 5 S keys of the style attention).  tight: the handle's capacity - None: the
+    shared handle of CASES (MAX_B, MAX_L, MAX_LT); False ("loose"): max_B = 3, max_Lt = Lt + 24, max_L = L; True: max_B = B,
+    max_Lt = Lt, max_L = L (handle_caps).  weights: None = spec.synthetic_state_dict, or a name of WEIGHT_SETS; style: None = the
+    synthetic style rows, or "flat_last" (case_inputs)."""
+    return dict(id=id, B=B, L=L, Lt=Lt, pad=pad, nl=nl, handle=handle or {}, launch=launch or {}, static=static or {}, expect=list(expect), S=S, tight=tight,
+                weights=weights, style=style)
 
 
 CASES = [
@@ -116,6 +121,92 @@ SIGMAS = (0.25, 0.85, 0.55)   # one per sample
 
 # the short sampling run of tests/test_gpu_parity.py::test_sampler_switches_do_not_change_the_samples
 SAMPLE_SHAPE = dict(B=3, L=80, Lt=9, T=7, seed=12, pad=1)
+
+
+# ---------------------------------------------------------------- the text-shape cases
+# What the text side and the cross-attention compute depends on the prompt length Lt, the padded tail, the style rows S (S5 = 5 S keys
+# of the style attention) and the handle's capacity (lpadT = pad32(max_Lt) is the row stride of V^T on the fp32 / generic paths; a
+# loose handle leaves foreign prompts' rows behind the call's).  None of it depends on L: L = 64 keeps every block alive (8 rows at the
+# bottleneck) and the float64 references cheap.  These cases are not run ragged and carry no `expect`.
+TEXT_L = 64
+FUSED_MAX_LT, FUSED_MAX_S = 32, 16   # textside_supported (csrc/textside.hip): above either the call runs the generic GEMM + attn.hip path
+LOOSE_B, LOOSE_LT = 3, 24            # a loose handle: max_B = 3, max_Lt = Lt + 24
+
+# (Lt, pad): 16-key tiles of the cross-attention fragments (15 | 16 | 17), the 32-key blocks of enc_a_tile - its prologue stages the
+# first, attn_stage_kv every later one - (31 | 32 | 33, 63 | 64 | 65, 96 | 97: four blocks, the last with one key), the fused / generic
+# switch at 32 | 33, one real token (31 / 30), a later block that is all padding (33 / 1, 64 / 32) or mostly (65 / 40)
+LT_SWEEP = [(1, 0), (2, 1), (15, 0), (16, 3), (17, 0), (31, 30), (32, 0), (32, 5), (33, 0), (33, 1), (47, 0), (48, 9), (63, 0), (64, 0),
+            (64, 32), (65, 0), (65, 40), (96, 7), (97, 0)]
+TIGHT_LT = (1, 32, 33, 64, 65)       # these also run on a handle with no room behind the call's rows
+# S: S5 = 5 S against the 10-row strides of the style staging (5 | 15 | 20 | 30 | 35 | 45 | 50), the 16-key tiles of its one-shot softmax
+# (15 | 20: one or two tiles; 30 | 35: the odd third tile without a partner; 45 | 50, 60 | 65: the fourth, the odd fifth), the full
+# 80 keys and the first generic count 85
+S_SWEEP = (1, 3, 4, 6, 7, 9, 10, 12, 13, 16, 17)
+S_SWEEP_AT = ((23, 3), (32, 0))
+CORNERS = [(1, 1), (1, 16), (1, 17), (32, 16), (33, 16), (32, 17), (33, 17)]   # (Lt, S), pad 0
+UNFUSED_ENVS = ({"DHW_FUSE_TEXT": "0"}, {"DHW_FUSE": "0"})                   # bf16 handles created with one of these
+UNFUSED_EXTRA = [(16, 3, 14), (33, 0, 14), (64, 32, 14)]                     # (Lt, pad, S) beside the corners
+
+
+# CHOSEN INPUTS.  With the synthetic weights both attentions of the text side are nearly uniform over their keys, so one key more or
+# less moves an output row by ~1 / sqrt(keys) of the attention's share of it: a style key left out or a padded style row let in stays
+# UNDER the bf16 bound of text_style_model (ratios 0.2 - 2.8), a text key left out of 65 reaches 5 x where 10 x is asked
+# (tests/test_text_ref_cpu.py prints them).  The "peaky" weight set scales the query projections of the style attention and of every
+# cross-attention, so that single keys carry rows, and the style attention's output projection, so that it weighs against the
+# residual; "flat_last" style rows - every 256-wide style row of a sample equal to its first, except the last - make key S5 - 1 the one
+# key that differs and give whole rows negative logits against every real key, which is where a zero-filled key takes over.
+WEIGHT_SETS = {"peaky": {"text_style_model.mha.wq.weight": 6.0, "text_style_model.mha.dense.weight": 4.0, ".mha.wq.weight": 4.0}}
+PEAKY_LT = [(32, 0), (33, 0), (33, 1), (64, 0), (64, 32), (65, 0)]   # (Lt, pad) under the peaky weights, S = 14
+
+
+def state_dict_for(nl, weights=None):
+    """spec.synthetic_state_dict(nl), with the tensors of WEIGHT_SETS[weights] scaled (a key that starts with "." names that tensor
+    of every EncoderLayer)."""
+    from dhg_amd import spec
+    sd = dict(spec.synthetic_state_dict(nl))
+    for k, f in (WEIGHT_SETS[weights] if weights else {}).items():
+        for name in ([l + k for l in layer_names(nl)] if k.startswith(".") else [k]):
+            sd[name] = (sd[name] * np.float32(f)).astype(np.float32)
+    return sd
+
+
+def _text_case(Lt, pad, S=14, tight=False, B=2, handle=None, weights=None, style=None):
+    tag = "".join(f"_{k[4:].lower()}{v}" for k, v in sorted((handle or {}).items())) + (f"_{weights}" if weights else "") + (f"_{style}" if style else "")
+    return _case(f"text_Lt{Lt}_pad{pad}_S{S}{'_B3' if B == 3 else ''}{'_tight' if tight else ''}{tag}", TEXT_L, B=B, Lt=Lt, pad=pad, handle=handle, S=S, tight=tight,
+                 weights=weights, style=style)
+
+
+def _text_cases():
+    out = [_text_case(Lt, pad) for Lt, pad in LT_SWEEP] + [_text_case(Lt, pad, tight=True) for Lt, pad in LT_SWEEP if Lt in TIGHT_LT]
+    out += [_text_case(Lt, pad, S) for Lt, pad in S_SWEEP_AT for S in S_SWEEP]
+    out += [_text_case(Lt, 0, S) for Lt, S in CORNERS] + [_text_case(32, 0, 16, B=3)]
+    for env in UNFUSED_ENVS:
+        out += [_text_case(Lt, 0, S, handle=env) for Lt, S in CORNERS] + [_text_case(Lt, pad, S, handle=env) for Lt, pad, S in UNFUSED_EXTRA]
+    out += [_text_case(23, 3, S, weights="peaky", style="flat_last") for S in S_SWEEP if S <= FUSED_MAX_S]
+    out += [_text_case(Lt, pad, weights="peaky") for Lt, pad in PEAKY_LT]
+    out = list({c["id"]: c for c in out}.values())   # ((32, 0) of the S sweep at S = 16 / 17 are corners too)
+    return sorted(out, key=lambda c: (handle_key(c, ""), c["pad"], c["B"]))   # cases of one handle next to each other
+
+
+def handle_caps(case):
+    """(max_B, max_L, max_Lt) of the case's handle."""
+    if case["tight"] is None:
+        return MAX_B, MAX_L, MAX_LT
+    return (case["B"], case["L"], case["Lt"]) if case["tight"] else (LOOSE_B, case["L"], case["Lt"] + LOOSE_LT)
+
+
+def handle_key(case, prec):
+    return (case["nl"], prec, tuple(sorted(case["handle"].items())), case["S"], handle_caps(case), case["weights"] or "")
+
+
+def text_fused(case, prec):
+    """Whether the call runs text_style_kernel / text_layer_kernel (else the generic GEMM + attn.hip text side)."""
+    ha = case["handle"]
+    return prec == "bf16" and ha.get("DHW_FUSE") != "0" and ha.get("DHW_FUSE_TEXT") != "0" and case["Lt"] <= FUSED_MAX_LT and case["S"] <= FUSED_MAX_S
+
+
+TEXT_CASES = _text_cases()
+TEXT_CASE = {c["id"]: c for c in TEXT_CASES}
 
 
 # ---------------------------------------------------------------- row tiles per case and level, and the sample ends that probe them
@@ -372,10 +463,33 @@ def model_for(nl, prec, handle_env):
     return _MODELS[key]
 
 
+_TEXT_MODEL = {}   # at most one handle of the text cases is alive: they are ordered by handle key
+
+
+def text_model_for(case, prec):
+    """The handle of a text case: one per (depth, precision, create-time switches, style rows, capacity), created at first use -
+    by the first forward on it, under the case's handle switches - and kept until a case asks for another one."""
+    import dhg_amd
+    key = handle_key(case, prec)
+    if key not in _TEXT_MODEL:
+        for m in _TEXT_MODEL.values():
+            m._destroy()
+        _TEXT_MODEL.clear()
+        mb, ml, mlt = handle_caps(case)
+        m = dhg_amd.DiffusionModel(case["nl"], precision=prec, max_B=mb, max_L=ml, max_Lt=mlt, style_rows=case["S"]).eval()
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in state_dict_for(case["nl"], case["weights"]).items()}, strict=True)
+        _TEXT_MODEL[key] = m
+    return _TEXT_MODEL[key]
+
+
 def case_inputs(case):
     from dhg_amd import spec
-    inp = spec.synthetic_inputs(case["B"], case["L"], case["Lt"], seed=4000 + case["L"], pad=case["pad"])
+    inp = spec.synthetic_inputs(case["B"], case["L"], case["Lt"], S=case["S"], seed=case.get("seed", 4000 + case["L"]), pad=case["pad"])
     inp.pop("noise")
+    if case["style"] == "flat_last":   # every 256-wide style row of a sample equal to its first, except the last (WEIGHT_SETS)
+        st = inp["style"].reshape(case["B"], case["S"] * 5, 256).copy()
+        st[:, :-1] = st[:, :1]
+        inp["style"] = st.reshape(inp["style"].shape)
     inp["sigma"] = np.array(SIGMAS[:case["B"]], np.float32).reshape(-1, 1)
     return inp
 
@@ -424,6 +538,66 @@ def run_case(case, prec, lengths=None):
             continue
         if lengths is not None and name not in TEXT_SIDE:
             a = a[:, :max(lengths) * a.shape[1] // case["L"]]
+        out[name] = a
+    return out
+
+
+def layer_names(nl):
+    return ["enc3", "enc5"] + [f"att_layers.{i}" for i in range(nl)]
+
+
+LAYER_WIDTH = {"enc3": 192, "enc5": 256}   # att_layers.*: 384
+
+
+def text_tap_names(nl):
+    """The taps of a text case: every tap of tap_names() and the text keys / values of every EncoderLayer."""
+    return tap_names(nl) + [l + s for l in layer_names(nl) for s in (".k1", ".v1")]
+
+
+def values_as_rows(a, Lt, d, lpadT):
+    """"<layer>.v1" as dhw_debug_read reports it -> (rows [B, Lt, d], the stored form).  The tap's shape says which form the handle
+    keeps: rows [B, Lt, d] (fused bf16 EncoderLayer kernels) or V^T [B, d, lpadT], of which columns [0, Lt) belong to the call."""
+    if tuple(a.shape[1:]) == (Lt, d):
+        return a, "rows"
+    assert tuple(a.shape[1:]) == (d, lpadT), (a.shape, Lt, d, lpadT)
+    return np.ascontiguousarray(np.swapaxes(a[:, :, :Lt], 1, 2)), "vt"
+
+
+def pad32(n):
+    return (n + 31) // 32 * 32
+
+
+def run_text_case(case, prec):
+    """One dhw_forward of a text case -> {tap: float32 array} + eps, pen, with every "<layer>.v1" as rows [B, Lt, d].
+
+    Immediately before it a forward at the HANDLE's max_B and max_Lt (the case's L) with a style tensor of NaN runs on the same
+    handle: the style rows, hence the style attention's keys and values, hence every row of text_out and of every layer's k1 / v1
+    - the rows behind the call's prompts and tokens included - hold NaN afterwards.  "poisoned" says that the poison call's
+    text_style_model, k1 and v1 taps did come out all NaN.  Whatever the case's call reads from a row it did not write is NaN."""
+    from dhg_amd import _lib
+    m = text_model_for(case, prec)
+    mb, _, mlt = handle_caps(case)
+    nl, L, Lt = case["nl"], case["L"], case["Lt"]
+    inp = case_inputs(case)
+    out = {}
+    with environ(case["handle"]):   # (the handle is created by the first call on it)
+        m(torch.zeros(mb, L, 2).cuda(), torch.ones(mb, mlt, dtype=torch.int64).cuda(), torch.full((mb, 1), 0.5).cuda(),
+          torch.full((mb, case["S"], 1280), float("nan")).cuda())
+        nan = []
+        for l in layer_names(nl):
+            d = LAYER_WIDTH.get(l, 384)
+            nan += [np.isnan(m.debug_read(l + ".k1").numpy()).all(), np.isnan(values_as_rows(m.debug_read(l + ".v1").numpy(), mlt, d, pad32(mlt))[0]).all()]
+        nan.append(np.isnan(m.debug_read("text_style_model").numpy()).all())
+        out["poisoned"] = np.array(all(nan))
+        eps, pen, _ = m(*(torch.from_numpy(inp[k]).cuda() for k in ("strokes", "text", "sigma", "style")))
+    out.update(eps=eps.cpu().numpy(), pen=pen.cpu().numpy())
+    for name in text_tap_names(nl):
+        try:
+            a = m.debug_read(name).numpy()
+        except _lib.DhwError:   # the call did not set this tap
+            continue
+        if name.endswith(".v1"):
+            a, out[name + ".stored"] = values_as_rows(a, Lt, LAYER_WIDTH.get(name[:-3], 384), pad32(mlt))
         out[name] = a
     return out
 

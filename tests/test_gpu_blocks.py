@@ -52,11 +52,11 @@ WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "blocks_worker
 _WEIGHTS = {}
 
 
-def weights(nl, prec):
-    from dhg_amd import spec
-    if (nl, prec) not in _WEIGHTS:
-        _WEIGHTS[nl, prec] = R.Weights(spec.synthetic_state_dict(nl), prec)
-    return _WEIGHTS[nl, prec]
+def weights(nl, prec, name=None):
+    """The weights as a handle of precision prec holds them: the synthetic state dict, or a named set of BW.WEIGHT_SETS."""
+    if (nl, prec, name) not in _WEIGHTS:
+        _WEIGHTS[nl, prec, name] = R.Weights(BW.state_dict_for(nl, name), prec)
+    return _WEIGHTS[nl, prec, name]
 
 
 def _parts(case, got, lengths):
@@ -90,7 +90,7 @@ def check_case(case, prec, got, lengths=None, tag=None):
     (a ragged call behind a NaN-poisoned workspace, BW.run_case): the stroke-path blocks per sample, the valid rows of all samples
     concatenated along the row axis under the SAME measures and bounds; every valid row finite; eps / pen exactly 0 past each end."""
     nl = case["nl"]
-    W = weights(nl, prec)
+    W = weights(nl, prec, case["weights"])
     tag = tag or case["id"]
     ragged = lengths is not None
     if ragged:
@@ -117,7 +117,8 @@ def check_case(case, prec, got, lengths=None, tag=None):
         for key in refs[0]:
             if key not in dev:
                 # sub-taps exist only where the launch writes them (`must` below names the cases in which it does)
-                assert key.endswith((".x3", ".style", ".t2")), f"{tag}: the call left no tap '{key}'"
+                # (".k1" / ".v1", the layers' text keys and values, are read by the text cases only: BW.run_text_case)
+                assert key.endswith((".x3", ".style", ".t2", ".k1", ".v1")), f"{tag}: the call left no tap '{key}'"
                 continue
             seen.add(key)
             want = torch.cat([rows_of(r[key]) for r in refs])
@@ -174,6 +175,34 @@ def test_every_block_of_a_ragged_call_matches_its_float64_reference_per_sample(c
     tile starts and key blocks (BW.end_classes), behind a workspace poisoned with NaN."""
     lens = BW.length_sets(case, prec)[r]
     check_case(case, prec, BW.run_case(case, prec, lens), lens, f"{case['id']}+r{r}")
+
+
+# ---------------------------------------------------------------- the text side and the cross-attention at every prompt / style edge
+def _text_params():
+    """(case, precision) ordered by handle, so that each handle is created once (BW.text_model_for keeps one alive).  Every case runs
+    on a default bf16 handle - or the bf16 handle its switches name - and, the cases without switches, on an fp32 handle too."""
+    ps = [(c, p) for c in BW.TEXT_CASES for p in (("bf16", "fp32") if not c["handle"] else ("bf16",))]
+    return sorted(ps, key=lambda cp: (BW.handle_key(*cp), cp[0]["pad"], cp[0]["B"]))
+
+
+@pytest.mark.parametrize("case,prec", [pytest.param(c, p, id=f"{c['id']}-{p}") for c, p in _text_params()])
+def test_text_side_and_cross_attention_at_every_prompt_and_style_edge(case, prec):
+    """BW.TEXT_CASES: prompt lengths around the 16-key tiles, the 32-key blocks and the fused / generic switch, style rows around the
+    staging strides and the softmax tiles, loose and tight handles; every block of the call, the layers' text keys and values
+    included, against float64 under the bounds of check_case - behind text-side buffers poisoned with NaN."""
+    got = BW.run_text_case(case, prec)
+    assert bool(got.pop("poisoned")), "the poison call's text_style_model / k1 / v1 taps did not come out all NaN"
+    stored = {k[:-7]: got.pop(k) for k in [k for k in got if k.endswith(".stored")]}
+    fused = BW.text_fused(case, prec)
+    rows_kernels = prec == "bf16" and case["handle"].get("DHW_FUSE") != "0"   # the fused bf16 EncoderLayer kernels read v1 as rows
+    layers = BW.layer_names(case["nl"])
+    assert set(stored) == {l + ".v1" for l in layers} and set(stored.values()) == {"rows" if rows_kernels else "vt"}, (stored, fused)
+    assert all(l + ".k1" in got for l in layers)
+    # the generic text side writes the FiLM'd style rows and t2; the fused kernels keep them in LDS
+    assert ("text_style_model.t2" in got) == (not fused) and ("text_style_model.style" in got) == (not fused), (sorted(got), fused)
+    for k, v in got.items():
+        assert np.isfinite(v).all(), (case["id"], prec, k, "not finite behind the poison")
+    check_case(case, prec, got)
 
 
 POLICY = [c for c in INPROC if "base" in c]
