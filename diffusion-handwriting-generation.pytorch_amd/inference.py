@@ -1007,10 +1007,13 @@ def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, 
 def write_page_file(text: str, source, config_path: str | None = None, checkpoint_path: str | None = None,
                     experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
                     precision: str = "bf16", seed: int = 0, style_weights: str | None = None, candidates: int = 1,
-                    steps: int | None = None, guidance=None, order: int | None = None, **page_kwargs) -> list:
+                    steps: int | None = None, guidance=None, order: int | None = None, svg: bool = False, **page_kwargs) -> list:
     """``infer.py --page-file``: resolve config / checkpoint as ``infer_file`` does, ``write_page`` the text in the hand of
-    ``source`` and save ``./<output>_p<k>.png`` per page (``vis.save_page_png``).  Returns the list of [L_i,3] strokes."""
+    ``source`` and save ``./<output>_p<k>.png`` per page (``vis.save_page_png``).  ``svg``: also ``./<output>_p<k>.svg``, the
+    same lines as curves (``vector.stroke_paths`` with the same page arguments at its default smoothing and thinning,
+    ``vector.save_page_svg``).  Returns the list of [L_i,3] strokes."""
     from .checkpoint import load_model
+    from .vector import save_page_svg, stroke_paths
     from .vis import save_page_png
 
     lines, _ = wrap_text(text, page_kwargs.get("max_chars", 40))
@@ -1026,6 +1029,12 @@ def write_page_file(text: str, source, config_path: str | None = None, checkpoin
     out = out.cpu()
     for k in range(out.shape[0]):
         save_page_png(out[k], f"{output}_p{k}")
+    if svg:
+        _, slots = wrap_text(text, page_kwargs.get("max_chars", 40))
+        geometry = {k: v for k, v in page_kwargs.items() if k in ("height", "width", "lines_per_page", "margin_left", "margin_top", "pitch", "scale")}
+        paths = stroke_paths(pad_strokes(strokes), [len(s) for s in strokes], slots, pages=int(out.shape[0]), **geometry)
+        for k in range(paths.pages):
+            save_page_svg(paths, k, f"{output}_p{k}", line_width=page_kwargs.get("line_width", 2.0))
     return strokes
 
 

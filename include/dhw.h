@@ -489,6 +489,63 @@ int dhw_page(const float* strokes,      /* device f32 [N,L,3]                   
              float* boxes_out,          /* device f32 [N,4]                                               */
              void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Stroke paths: the vector twin of dhw_page.  N lines -> the pen-down polylines of every line in page pixels, at dhw_page's
+ * ONE shared scale and in dhw_page's slots, smoothed, thinned, with a tangent per point (a cubic Bezier segment from point k
+ * to k + 1 has the control points P_k + t_k and P_k+1 - t_k+1: the Catmull-Rom spline through the kept points).  No handle:
+ * errors are read through dhw_last_error(NULL).  The call allocates nothing, synchronises nothing and can be captured into a
+ * graph.  All argument checks run before the first HIP call (DHW_ERR_ARG names the argument): N, L, P, H, W, lines_per_page,
+ * margin_left, margin_top, pitch, scale and strokes by dhw_page's rules (there is no line_width); 0 <= smooth <= 8,
+ * 0 <= rounds <= 8, tol finite and >= 0; non-NULL points_out / index_out / counts_out / scale_out / boxes_out / workspace;
+ * points_out and workspace 16-byte aligned, every other pointer 4-byte aligned; workspace_bytes >=
+ * dhw_paths_workspace_bytes(N, L) (0 for an N or L outside the ranges).
+ *
+ * Line n, with lens[n] (L when lens is NULL) strokes and slot[n] = slots[n] (n when slots is NULL):
+ *    1. Rules 1.-5. of dhw_render, unchanged: pos = the prefix sums (in the line rasteriser's summation order: the positions
+ *       have the raster's bits), lift, last, segment i is drawn iff 1 <= i < last and !lift[i], (xmin, xmax, ymin, ymax)_n =
+ *       the box of the endpoints of drawn segments.  A device-side lens entry outside [1, L] is clamped to [0, L].
+ *    2. Rules 6.-9. of dhw_page, unchanged: which lines take part, ex_n, ey_n and s_n, the shared s (scale when scale > 0),
+ *       the page slot[n] / lines_per_page and top_n = margin_top + (slot[n] % lines_per_page) pitch.
+ *    3. Position i (0 <= i < lens) is a path point iff segment i or segment i + 1 is drawn (segment 0 and segment lens never
+ *       are).  It starts a polyline iff segment i is not drawn and ends one iff segment i + 1 is not.  Polylines are numbered
+ *       0, 1, ... in stroke order; each has at least 2 points; a position belongs to at most one.
+ *    4. Placement, fp32: x = margin_left + (pos.x - xmin_n) s;  oy = top_n + (pitch - ey_n s) 0.5;  y = oy + (ymax_n - pos.y) s.
+ *       Here and below every difference, product, sum and quotient is one fp32 operation in the order written; none is fused.
+ *    5. Smoothing, `smooth` times: every point that neither starts nor ends a polyline becomes (p[i-1] + p[i+1]) 0.25 +
+ *       p[i] 0.5 per coordinate, all from the values before the pass.  End points never move.
+ *    6. Thinning, `rounds` times, tol2 = tol tol.  At the start of a round the rank of a kept point is the number of kept
+ *       points of its polyline before it.  A kept point P is a candidate iff its rank is odd and it does not end its polyline;
+ *       A = its previous and B = its next kept neighbour (both of even rank: they survive the round).  With ab = B - A,
+ *       ap = P - A and len2 = ab.x ab.x + ab.y ab.y:  d2 = ap.x ap.x + ap.y ap.y if len2 == 0, else t = min(max((ap.x ab.x +
+ *       ap.y ab.y) / len2, 0), 1), e = ap - t ab, d2 = e.x e.x + e.y e.y.  P is removed iff d2 <= tol2.  All decisions of a
+ *       round use the state at its start.  What this bounds: a point removed in a round lies within tol of the segment
+ *       between its neighbours OF THAT ROUND.  Later rounds may remove those neighbours, so after r rounds a removed point
+ *       may lie further than tol from the final path.  This is not Ramer-Douglas-Peucker and no global error bound is
+ *       claimed; rounds = 0 keeps every point.
+ *    7. Tangent of a kept point: t = (next - prev) / 6.0f per coordinate, next / prev = its kept neighbours in the same
+ *       polyline, the point itself where there is none.
+ *    8. Outputs, compacted in stroke order: row k of points_out[n] = (x, y, tx, ty) of the k-th kept point, row k of
+ *       index_out[n] = (i, polyline number).  Rows at or past the count hold 0 in points_out and (-1, -1) in index_out.
+ *       counts_out[n] = (kept points, polylines); (0, 0) for a line that takes no part.
+ *    9. scale_out[0] = s.  boxes_out[n] = (margin_left, oy, margin_left + ex_n s, oy + ey_n s) with oy of rule 4, each
+ *       operation on its own (dhw_page may fuse them: the two boxes can differ in the last bit); zeros for a line that takes
+ *       no part.
+ *   10. No atomics, one writer per output element: the same call gives the same bits; line n inside any batch has the bits
+ *       of line n alone (N = 1, the same slot, scale = the batch's s); the result does not depend on the order of the lines. */
+size_t dhw_paths_workspace_bytes(int N, int L);
+int dhw_paths(const float* strokes,      /* device f32 [N,L,3]                                             */
+              const int32_t* lens,       /* DEVICE int32 [N] or NULL, any 1 <= n <= L                      */
+              const int32_t* slots,      /* DEVICE int32 [N] or NULL (slot[n] = n)                         */
+              int N, int L, int P, int H, int W, int lines_per_page,
+              float margin_left, float margin_top, float pitch,      /* page pixels                        */
+              float scale,                                           /* 0: automatic                       */
+              int smooth, float tol, int rounds,                     /* tol in page pixels                 */
+              float* points_out,         /* device f32 [N,L,4] = (x, y, tx, ty), page pixels               */
+              int32_t* index_out,        /* device i32 [N,L,2] = (stroke row i, polyline number)           */
+              int32_t* counts_out,       /* device i32 [N,2]   = (kept points, polylines)                  */
+              float* scale_out,          /* device f32 [1]                                                 */
+              float* boxes_out,          /* device f32 [N,4]                                               */
+              void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Stroke encoder: raw pen trajectories (tablet points grouped into pen-down strokes, the IAM-OnDB lineStrokes data) -> the
  * model's (dx, dy, pen) rows, normalised and thinned as the reference's parse_strokes_xml + combine_strokes + pad_stroke_seq
  * prepare the training corpus.  No handle: errors are read through dhw_last_error(NULL).  The call allocates nothing,

@@ -39,7 +39,11 @@ Classifier-free guidance (a checkpoint trained with `train.py --cond-drop`; work
 
 A whole text as pages (word-wrapped, every line at the same scale, composed on the GPU into <output>_p<k>.png):
 
-    python infer.py --page-file letter.txt style.npy --experiment-path data/best_exp --output letter"""
+    python infer.py --page-file letter.txt style.npy --experiment-path data/best_exp --output letter
+
+The pages as curves too (<output>_p<k>.svg next to each PNG: for pen plotters, print at any size, drawing programs):
+
+    python infer.py --page-file letter.txt style.npy --experiment-path data/best_exp --output letter --svg"""
 import argparse
 
 import dhg_amd
@@ -76,7 +80,10 @@ def main(argv=None):
                                                                               "and the writer); needs a checkpoint trained with train.py --cond-drop")
     ap.add_argument("--page-file", metavar="TXT", help="a text to write as pages: wrapped to lines, every line sampled, all lines composed on the "
                                                        "GPU at one shared scale into <output>_p<k>.png (a blank line leaves a gap)")
+    ap.add_argument("--svg", action="store_true", help="with --page-file: also write every page as curves to <output>_p<k>.svg")
     a = ap.parse_args(argv)
+    if a.svg and not a.page_file:
+        ap.error("--svg writes pages as curves: it needs --page-file")
     if a.page_file and (a.score or a.align or a.restyle):
         ap.error("--page-file writes a text: it goes with neither --score, --align nor --restyle")
     if a.page_file and a.prompts_file:
@@ -149,9 +156,9 @@ def main(argv=None):
         if not text.split():
             ap.error(f"{a.page_file} holds no word")
         out = dhg_amd.write_page_file(text, source, a.config_path, a.checkpoint_path, a.experiment_path, a.output, a.diffusion_mode,
-                                      precision=a.precision, seed=a.seed, style_weights=a.style_weights, **cand)
+                                      precision=a.precision, seed=a.seed, style_weights=a.style_weights, **cand, **(dict(svg=True) if a.svg else {}))
         save(out)
-        print(f"{len(out)} lines -> ./{a.output}_p<k>.png")
+        print(f"{len(out)} lines -> ./{a.output}_p<k>.png" + (f" and ./{a.output}_p<k>.svg" if a.svg else ""))
         return
     if a.prompts_file:
         if a.prompt is not None and a.source is not None:
