@@ -7,13 +7,13 @@ time-warped copy of a training line?").
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
+
+from . import _call
 
 DTW_MAX_N, DTW_MAX_PAIRS, DTW_MAX_L, DTW_MAX_F = 16384, 1 << 26, 1024, 4   # csrc/dtw/dtw.h
 KINDS = ("positions", "offsets")
-_workspaces = {}   # device index -> workspace tensors of dhw_dtw (vis._workspace)
+WHO = "dynamic time warping"   # in the no-GPU refusal of every function here
 
 
 def _check_strokes(strokes, lengths, who: str):
@@ -45,16 +45,8 @@ def _check_strokes(strokes, lengths, who: str):
 def _check_kind(kind, pen_weight, who: str):
     if kind not in KINDS:
         raise ValueError(f"{who}: kind = {kind!r} must be one of {', '.join(KINDS)}")
-    if isinstance(pen_weight, bool) or not isinstance(pen_weight, (int, float, np.integer, np.floating)) or not np.isfinite(pen_weight) or pen_weight < 0:
+    if not _call.is_number(pen_weight) or not np.isfinite(pen_weight) or pen_weight < 0:
         raise ValueError(f"{who}: pen_weight = {pen_weight!r} must be a finite number >= 0")
-
-
-def _device(x):
-    import torch
-
-    if not torch.cuda.is_available():
-        raise RuntimeError("dynamic time warping needs an MI355X (HIP device): there is no CPU path in this package")
-    return x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
 
 
 def _features(x, kind: str, pen_weight, dev):
@@ -81,7 +73,7 @@ def stroke_features(strokes, lengths=None, kind: str = "positions", pen_weight: 
     past a line's length are carried along unread.  ValueError for non-finite strokes and lengths outside [1, L]."""
     _check_kind(kind, pen_weight, "stroke_features")
     x, _ = _check_strokes(strokes, lengths, "stroke_features")
-    return _features(x, kind, pen_weight, _device(x))
+    return _features(x, kind, pen_weight, _call.pick_device(WHO, like=x))
 
 
 def _aligned(t):
@@ -94,7 +86,7 @@ def _chunks(n: int, step: int):
 
 
 def _check_chunk(chunk):
-    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or not 1 <= chunk <= DTW_MAX_N):
+    if chunk is not None and not (_call.is_int(chunk) and 1 <= chunk <= DTW_MAX_N):
         raise ValueError(f"_chunk = {chunk!r} must be an integer in [1, {DTW_MAX_N}]")
 
 
@@ -106,41 +98,34 @@ def _steps(M: int, N: int, chunk):
     return min(M, DTW_MAX_N, DTW_MAX_PAIRS // cn), cn
 
 
-def _prepare(a, b, lengths_a, lengths_b, kind, pen_weight, who):
-    """Checked inputs -> (device, features a, lens a, features b, lens b, same); lens are int32 device tensors or None."""
-    import torch
-
+def _check_sets(a, b, lengths_a, lengths_b, kind, pen_weight, who):
+    """The host rules of both sets -> (strokes a, lens a, strokes b, lens b, same); ``b`` None: ``a`` against itself."""
     _check_kind(kind, pen_weight, who)
     xa, la = _check_strokes(a, lengths_a, who)
-    same = b is None
-    if same:
+    if b is None:
         if lengths_b is not None:
             raise ValueError(f"{who}: lengths of the second set were given without the set")
-        xb, lb = xa, la
-    else:
-        xb, lb = _check_strokes(b, lengths_b, who)
-    dev = _device(xa)
-    with torch.cuda.device(dev):
-        fa = _features(xa, kind, pen_weight, dev).contiguous()
-        fb = fa if same else _features(xb, kind, pen_weight, dev).contiguous()
-        da = None if la is None else torch.from_numpy(la.astype(np.int32)).to(dev)
-        db = da if same else None if lb is None else torch.from_numpy(lb.astype(np.int32)).to(dev)
-    return dev, fa, da, fb, db, same
+        return xa, la, xa, la, True
+    return (xa, la) + _check_strokes(b, lengths_b, who) + (False,)
 
 
-def _call(l, dev, fa, la, fb, lb, normalize, skip_diag, dist, steps, near, idx):
-    """One dhw_dtw call on the current stream of `dev`; the tensors are contiguous and 16-byte aligned."""
+def _stage(c, xa, la, xb, lb, same, kind, pen_weight):
+    """The checked sets on the call's device: (features a, lens a, features b, lens b); lens are int32 tensors or None."""
     import torch
 
-    from . import _lib
-    from .vis import _workspace
-    M, N = int(fa.shape[0]), int(fb.shape[0])
-    need = int(l.dhw_dtw_workspace_bytes(M, N, int(fa.shape[1]), int(fb.shape[1]), 3))
-    ws = _workspace(_workspaces, dev, need)
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    _lib.check(l.dhw_dtw(fa.data_ptr(), ptr(la), M, int(fa.shape[1]), fb.data_ptr(), ptr(lb), N, int(fb.shape[1]), 3, int(bool(normalize)),
-                         int(bool(skip_diag)), ptr(dist), ptr(steps), ptr(near), ptr(idx), ws.data_ptr(), need,
-                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    fa = _features(xa, kind, pen_weight, c.dev).contiguous()
+    fb = fa if same else _features(xb, kind, pen_weight, c.dev).contiguous()
+    da = None if la is None else torch.from_numpy(la.astype(np.int32)).to(c.dev)
+    db = da if same else None if lb is None else torch.from_numpy(lb.astype(np.int32)).to(c.dev)
+    return fa, da, fb, db
+
+
+def _run(c, fa, la, fb, lb, normalize, skip_diag, dist, steps, near, idx):
+    """One dhw_dtw call on the stream of `c`; the tensors are contiguous and 16-byte aligned."""
+    M, La, N, Lb = int(fa.shape[0]), int(fa.shape[1]), int(fb.shape[0]), int(fb.shape[1])
+    ws, need = c.workspace("dtw", "dhw_dtw_workspace_bytes", M, N, La, Lb, 3)
+    c.run("dhw_dtw", fa.data_ptr(), c.ptr(la), M, La, fb.data_ptr(), c.ptr(lb), N, Lb, 3, int(bool(normalize)), int(bool(skip_diag)),
+          c.ptr(dist), c.ptr(steps), c.ptr(near), c.ptr(idx), c.ptr(ws), need)
 
 
 def dtw_distance(a, b=None, lengths_a=None, lengths_b=None, kind: str = "positions", pen_weight: float = 1.0, normalize: bool = True, _chunk=None):
@@ -148,26 +133,25 @@ def dtw_distance(a, b=None, lengths_a=None, lengths_b=None, kind: str = "positio
     with optional lengths: (dist float32 [M,N], steps int32 [M,N]) on the device.  dist is the summed squared feature distance
     along the best warping path (``stroke_features``), divided by the path's number of cells ``steps`` when ``normalize``.  Sets
     beyond one call's limits (16384 lines a side, 2^26 pairs) are computed in blocks; ``_chunk`` (tests) forces blocks of that
-    many lines a side.  A pair's bits do not depend on the blocks."""
+    many lines a side.  A pair's bits do not depend on the blocks.  One workspace is cached per device: calls on one device must
+    be ordered on one stream."""
     import torch
 
-    from . import _lib
     _check_chunk(_chunk)
-    dev, fa, la, fb, lb, _ = _prepare(a, b, lengths_a, lengths_b, kind, pen_weight, "dtw_distance")
-    M, N = int(fa.shape[0]), int(fb.shape[0])
-    cm, cn = _steps(M, N, _chunk)
-    l = _lib.lib()
-    with torch.cuda.device(dev):
-        dist = torch.empty((M, N), dtype=torch.float32, device=dev)
-        steps = torch.empty((M, N), dtype=torch.int32, device=dev)
+    xa, la, xb, lb, same = _check_sets(a, b, lengths_a, lengths_b, kind, pen_weight, "dtw_distance")
+    with _call.open(WHO, like=xa) as c:
+        fa, la, fb, lb = _stage(c, xa, la, xb, lb, same, kind, pen_weight)
+        M, N = int(fa.shape[0]), int(fb.shape[0])
+        cm, cn = _steps(M, N, _chunk)
+        dist, steps = c.empty((M, N)), c.empty((M, N), torch.int32)
         for plo, phi in _chunks(M, cm):
             for qlo, qhi in _chunks(N, cn):
                 whole = qlo == 0 and qhi == N
-                d = dist[plo:phi] if whole else torch.empty((phi - plo, qhi - qlo), dtype=torch.float32, device=dev)
-                k = steps[plo:phi] if whole else torch.empty((phi - plo, qhi - qlo), dtype=torch.int32, device=dev)
+                d = dist[plo:phi] if whole else torch.empty((phi - plo, qhi - qlo), dtype=torch.float32, device=c.dev)   # (a block's own:
+                k = steps[plo:phi] if whole else torch.empty((phi - plo, qhi - qlo), dtype=torch.int32, device=c.dev)    # not kept by c)
                 da, ka = _aligned(d), _aligned(k)
-                _call(l, dev, _aligned(fa[plo:phi]), None if la is None else _aligned(la[plo:phi]), _aligned(fb[qlo:qhi]),
-                      None if lb is None else _aligned(lb[qlo:qhi]), normalize, False, da, ka, None, None)
+                _run(c, _aligned(fa[plo:phi]), None if la is None else _aligned(la[plo:phi]), _aligned(fb[qlo:qhi]),
+                     None if lb is None else _aligned(lb[qlo:qhi]), normalize, False, da, ka, None, None)
                 if not whole or da is not d:
                     dist[plo:phi, qlo:qhi] = da
                     steps[plo:phi, qlo:qhi] = ka
@@ -182,25 +166,24 @@ def nearest_strokes(queries, refs=None, lengths_q=None, lengths_r=None, kind: st
     kept on a tie."""
     import torch
 
-    from . import _lib
     _check_chunk(_chunk)
-    dev, fa, la, fb, lb, same = _prepare(queries, refs, lengths_q, lengths_r, kind, pen_weight, "nearest_strokes")
-    M, N = int(fa.shape[0]), int(fb.shape[0])
-    if same and M < 2:
-        raise ValueError("nearest_strokes: the nearest other line needs at least 2 lines")
-    cm, cn = _steps(M, N, _chunk)
-    if same:
-        cm = cn = min(cm, cn)   # the same blocks on both sides: the diagonal lies in the blocks with equal bounds
-    l = _lib.lib()
-    with torch.cuda.device(dev):
-        best = torch.full((M,), float("inf"), dtype=torch.float32, device=dev)
-        best_idx = torch.full((M,), -1, dtype=torch.int32, device=dev)
+    xa, la, xb, lb, same = _check_sets(queries, refs, lengths_q, lengths_r, kind, pen_weight, "nearest_strokes")
+    with _call.open(WHO, like=xa) as c:
+        fa, la, fb, lb = _stage(c, xa, la, xb, lb, same, kind, pen_weight)
+        M, N = int(fa.shape[0]), int(fb.shape[0])
+        if same and M < 2:
+            raise ValueError("nearest_strokes: the nearest other line needs at least 2 lines")
+        cm, cn = _steps(M, N, _chunk)
+        if same:
+            cm = cn = min(cm, cn)   # the same blocks on both sides: the diagonal lies in the blocks with equal bounds
+        best = torch.full((M,), float("inf"), dtype=torch.float32, device=c.dev)
+        best_idx = torch.full((M,), -1, dtype=torch.int32, device=c.dev)
         for plo, phi in _chunks(M, cm):
             for qlo, qhi in _chunks(N, cn):
-                near = torch.empty(phi - plo, dtype=torch.float32, device=dev)
-                idx = torch.empty(phi - plo, dtype=torch.int32, device=dev)
-                _call(l, dev, _aligned(fa[plo:phi]), None if la is None else _aligned(la[plo:phi]), _aligned(fb[qlo:qhi]),
-                      None if lb is None else _aligned(lb[qlo:qhi]), normalize, same and (plo, phi) == (qlo, qhi), None, None, near, idx)
+                near = torch.empty(phi - plo, dtype=torch.float32, device=c.dev)
+                idx = torch.empty(phi - plo, dtype=torch.int32, device=c.dev)
+                _run(c, _aligned(fa[plo:phi]), None if la is None else _aligned(la[plo:phi]), _aligned(fb[qlo:qhi]),
+                     None if lb is None else _aligned(lb[qlo:qhi]), normalize, same and (plo, phi) == (qlo, qhi), None, None, near, idx)
                 better = near < best[plo:phi]     # blocks ascending and a strict comparison: the smaller index stays on a tie
                 best[plo:phi] = torch.where(better, near, best[plo:phi])
                 best_idx[plo:phi] = torch.where(better, idx + qlo, best_idx[plo:phi])

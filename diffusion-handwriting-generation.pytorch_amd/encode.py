@@ -3,11 +3,12 @@
 reads."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 import xml.etree.ElementTree as ET
 
 import numpy as np
+
+from . import _call
 
 ENCODE_MAX_B, ENCODE_MAX_N, ENCODE_MAX_L, ENCODE_MAX_ROUNDS = 65535, 4096, 4096, 8   # csrc/encode/encode_host.h
 
@@ -64,14 +65,6 @@ def _as_points(i: int, line) -> np.ndarray:
     return pts
 
 
-def _int(name: str, v, lo: int, hi: int) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name} = {v!r} is not an integer")
-    if not lo <= v <= hi:
-        raise ValueError(f"{name} = {v} must lie in [{lo}, {hi}]")
-    return int(v)
-
-
 def encode_strokes(lines, L=None, rounds: int = 3, max_abs: float = 15.0, device=None):
     """Encode a batch of raw pen lines on the GPU (include/dhw.h dhw_encode).
 
@@ -86,37 +79,25 @@ def encode_strokes(lines, L=None, rounds: int = 3, max_abs: float = 15.0, device
         raise ValueError("lines must be a non-empty list of lines")
     if len(lines) > ENCODE_MAX_B:
         raise ValueError(f"lines must hold at most {ENCODE_MAX_B} lines, got {len(lines)}")
-    rounds = _int("rounds", rounds, 0, ENCODE_MAX_ROUNDS)
-    if isinstance(max_abs, bool) or not isinstance(max_abs, (int, float, np.integer, np.floating)):
-        raise ValueError(f"max_abs = {max_abs!r} is not a number")
-    max_abs = float(max_abs)
+    rounds = _call.check_int("rounds", rounds, 0, ENCODE_MAX_ROUNDS)
+    max_abs = _call.check_number("max_abs", max_abs, finite=False)   # (its own message for both rules)
     if not math.isfinite(max_abs) or not max_abs > 0:
         raise ValueError(f"max_abs = {max_abs} must be finite and > 0")
     pts = [_as_points(i, ln) for i, ln in enumerate(lines)]
     if L is None:
         L = max(8, -(-max(upper_bound_rows(len(p), rounds) for p in pts) // 8) * 8)
-    L = _int("L", L, 8, ENCODE_MAX_L)
-    if not torch.cuda.is_available():
-        raise RuntimeError("encode_strokes needs an MI355X (HIP device): there is no CPU path in this package")
-    from . import _lib
-
-    B, N = len(pts), max(len(p) for p in pts)
-    host = np.zeros((B, N, 3), np.float32)
-    for b, p in enumerate(pts):
-        host[b, :len(p)] = p
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    l = _lib.lib()
-    with torch.cuda.device(dev):
-        points = torch.from_numpy(host).to(dev)
-        counts = torch.tensor([len(p) for p in pts], dtype=torch.int32).to(dev)
-        strokes = torch.empty((B, L, 3), device=dev, dtype=torch.float32)
-        lengths = torch.empty((B,), device=dev, dtype=torch.int32)
-        status = torch.empty((B,), device=dev, dtype=torch.int32)
-        need = int(l.dhw_encode_workspace_bytes(B, N))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        st = torch.cuda.current_stream(dev)
-        _lib.check(l.dhw_encode(points.data_ptr(), counts.data_ptr(), B, N, L, rounds, max_abs, strokes.data_ptr(), lengths.data_ptr(),
-                                status.data_ptr(), ws.data_ptr() if ws is not None else None, need, C.c_void_p(st.cuda_stream)))
+    L = _call.check_int("L", L, 8, ENCODE_MAX_L)
+    with _call.open("encode_strokes", device=device) as c:
+        B, N = len(pts), max(len(p) for p in pts)
+        host = np.zeros((B, N, 3), np.float32)
+        for b, p in enumerate(pts):
+            host[b, :len(p)] = p
+        points = c.to(torch.from_numpy(host))
+        counts = c.to(torch.tensor([len(p) for p in pts], dtype=torch.int32), torch.int32)
+        strokes, lengths, status = c.empty((B, L, 3)), c.empty((B,), torch.int32), c.empty((B,), torch.int32)
+        ws, need = c.workspace(None, "dhw_encode_workspace_bytes", B, N)
+        c.run("dhw_encode", points.data_ptr(), counts.data_ptr(), B, N, L, rounds, max_abs, strokes.data_ptr(), lengths.data_ptr(),
+              status.data_ptr(), c.ptr(ws), need)
     return strokes, lengths, status
 
 
@@ -134,7 +115,7 @@ def make_batches(lines, texts, style, max_seq_len: int = 480, max_text_len: int 
         raise ValueError(f"texts must hold {len(lines)} entries, got {len(texts)}")
     if any(not isinstance(t, str) for t in texts):
         raise ValueError("texts must be a list of str")
-    max_text_len = _int("max_text_len", max_text_len, 2, 4096)
+    max_text_len = _call.check_int("max_text_len", max_text_len, 2, 4096)
     style = torch.as_tensor(style)
     if tuple(style.shape) != (len(lines), 14, 1280):
         raise ValueError(f"style must be [{len(lines)}, 14, 1280], got {tuple(style.shape)}")

@@ -2,20 +2,12 @@
 (include/dhw.h dhw_prep), and the style features of many images in batched StyleExtractor calls."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
+
+from . import _call
 
 # csrc/prep/prep_host.h
 PREP_MAX_B, PREP_MAX_HIN, PREP_MAX_WIN, PREP_MIN_H, PREP_MAX_H, PREP_MIN_W, PREP_MAX_W = 65535, 4096, 16384, 8, 512, 8, 4096
-
-
-def _int(name: str, v, lo: int, hi: int) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name} = {v!r} is not an integer")
-    if not lo <= v <= hi:
-        raise ValueError(f"{name} = {v} must lie in [{lo}, {hi}]")
-    return int(v)
 
 
 def _as_image(i: int, item) -> np.ndarray:
@@ -33,8 +25,8 @@ def _as_image(i: int, item) -> np.ndarray:
 
 
 def _check_shape(B: int, height, width) -> tuple[int, int]:
-    height = _int("height", height, PREP_MIN_H, PREP_MAX_H)
-    width = _int("width", width, PREP_MIN_W, PREP_MAX_W)
+    height = _call.check_int("height", height, PREP_MIN_H, PREP_MAX_H)
+    width = _call.check_int("width", width, PREP_MIN_W, PREP_MAX_W)
     if width % 4:
         raise ValueError(f"width = {width} must be a multiple of 4")
     if B * height * width >= 1 << 31:
@@ -58,33 +50,21 @@ def prepare_images(images, height: int = 96, width: int = 1400, thresh: int = 12
     if len(images) > PREP_MAX_B:
         raise ValueError(f"images must hold at most {PREP_MAX_B} images, got {len(images)}")
     height, width = _check_shape(len(images), height, width)
-    thresh = _int("thresh", thresh, 1, 255)
+    thresh = _call.check_int("thresh", thresh, 1, 255)
     host = [_as_image(i, im) for i, im in enumerate(images)]
-    if not torch.cuda.is_available():
-        raise RuntimeError("prepare_images needs an MI355X (HIP device): there is no CPU path in this package")
-    from . import _lib
-
-    B, Hin = len(host), max(a.shape[0] for a in host)
-    Win = -(-max(a.shape[1] for a in host) // 16) * 16
-    packed = np.full((B, Hin, Win), 255, np.uint8)
-    for b, a in enumerate(host):
-        packed[b, :a.shape[0], :a.shape[1]] = a
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    l = _lib.lib()
-    with torch.cuda.device(dev):
-        src = torch.from_numpy(packed).to(dev)
-        sizes = torch.tensor([a.shape for a in host], dtype=torch.int32).to(dev)
-        imgs = torch.empty((B, 1, height, width), device=dev, dtype=torch.float32)
-        widths = torch.empty((B,), device=dev, dtype=torch.int32)
-        boxes = torch.empty((B, 4), device=dev, dtype=torch.int32)
-        status = torch.empty((B,), device=dev, dtype=torch.int32)
-        need = int(l.dhw_prep_workspace_bytes(B))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev)
-        _lib.check(l.dhw_prep(src.data_ptr(), sizes.data_ptr(), B, Hin, Win, height, width, thresh, imgs.data_ptr(), widths.data_ptr(),
-                              boxes.data_ptr(), status.data_ptr(), ws.data_ptr(), need, C.c_void_p(st.cuda_stream)))
-        for t in (src, sizes, ws):
-            t.record_stream(st)
+    with _call.open("prepare_images", device=device, record=True) as c:   # (record: kept as it was, see _call on temporaries)
+        B, Hin = len(host), max(a.shape[0] for a in host)
+        Win = -(-max(a.shape[1] for a in host) // 16) * 16
+        packed = np.full((B, Hin, Win), 255, np.uint8)
+        for b, a in enumerate(host):
+            packed[b, :a.shape[0], :a.shape[1]] = a
+        src = c.to(torch.from_numpy(packed), torch.uint8)
+        sizes = c.to(torch.tensor([a.shape for a in host], dtype=torch.int32), torch.int32)
+        imgs, widths = c.empty((B, 1, height, width)), c.empty((B,), torch.int32)
+        boxes, status = c.empty((B, 4), torch.int32), c.empty((B,), torch.int32)
+        ws, need = c.workspace(None, "dhw_prep_workspace_bytes", B)
+        c.run("dhw_prep", src.data_ptr(), sizes.data_ptr(), B, Hin, Win, height, width, thresh, imgs.data_ptr(), widths.data_ptr(),
+              boxes.data_ptr(), status.data_ptr(), c.ptr(ws), need)
     return imgs, widths, boxes, status
 
 
@@ -99,10 +79,10 @@ def load_styles(sources, style_weights=None, *, width: int = 1400, batch: int = 
     at its own width.  IAMDataset also keeps a sample only when its CONTENT image's resized width is < img_width: that rule is
     the caller's to apply, with `widths` (and a non-zero status marks an image that gave no crop at all: its features are
     those of a white image)."""
-    batch = _int("batch", batch, 1, PREP_MAX_B)
+    batch = _call.check_int("batch", batch, 1, PREP_MAX_B)
     if precision not in ("bf16", "fp32"):
         raise ValueError("precision must be 'bf16' or 'fp32'")
-    width = _int("width", width, 96, PREP_MAX_W)   # the extractor needs a 3 x 3 feature map: at least 96 columns
+    width = _call.check_int("width", width, 96, PREP_MAX_W)   # the extractor needs a 3 x 3 feature map: at least 96 columns
     imgs, widths, _, status = prepare_images(sources, 96, width)
     import torch
 

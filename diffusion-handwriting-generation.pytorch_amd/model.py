@@ -18,6 +18,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._call import DeviceCall
 from .spec import param_spec
 
 
@@ -146,41 +147,6 @@ class _DifferentiableForward(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(tm.p[k].g.clone() for k in tm.names)
 
 
-class _DeviceCall:
-    """The device side of one library call (``DiffusionModel._device_call``): the conversions every entry needs, and the
-    tensors the call hands to the library, kept so that they outlive the stream's work."""
-
-    def __init__(self, dev: torch.device, handle):
-        self.dev, self.h = dev, handle
-        self.stream = torch.cuda.current_stream(dev)
-        self.inputs, self.outputs = [], []
-
-    def to(self, x, dtype=torch.float32):
-        """``x`` (or None) as a contiguous tensor of ``dtype`` on the call's device."""
-        if x is not None:
-            x = x.to(self.dev, dtype).contiguous()
-            self.inputs.append(x)
-        return x
-
-    def empty(self, shape, dtype=torch.float32, wanted: bool = True):
-        if not wanted:
-            return None
-        self.outputs.append(torch.empty(shape, device=self.dev, dtype=dtype))
-        return self.outputs[-1]
-
-    @staticmethod
-    def ptr(x):
-        return x.data_ptr() if x is not None else None
-
-    @staticmethod
-    def lens(lens):
-        return (C.c_int32 * len(lens))(*lens) if lens is not None else None
-
-    def run(self, entry: str, *args):
-        """``entry(handle, *args, stream)``: every denoiser entry of include/dhw.h opens with the handle and ends with the stream."""
-        _lib.check(getattr(_lib.lib(), entry)(self.h, *args, C.c_void_p(self.stream.cuda_stream)), self.h)
-
-
 def _torch_dtype_code(t: torch.Tensor) -> int:
     return {torch.float32: _lib.DHW_F32, torch.bfloat16: _lib.DHW_BF16, torch.float16: _lib.DHW_F16,
             torch.float64: _lib.DHW_F64}[t.dtype]
@@ -272,7 +238,7 @@ class DiffusionModel(nn.Module):
         """The one path from checked arguments to the library: validate the token ids (``seen``: through the model's cache of
         validated prompt tensors; ``forward`` and the attention call read them every time, as ``check_token_ids`` promises), pick
         the device (the first CUDA tensor of ``tensors`` decides), make sure the handle fits, enter the device and yield a
-        ``_DeviceCall``.  The library reads its inputs in place and ``sample``'s graph holds raw pointers, so after the call its
+        ``DeviceCall``.  The library reads its inputs in place and ``sample``'s graph holds raw pointers, so after the call its
         tensors stay referenced in ``self._pinned[slot]`` until the next call of the same slot (one slot per entry: a score call
         must not release what a sampler graph on another stream may still read); ``slot=None`` marks the inputs as in use by
         the stream instead (``record_stream``)."""
@@ -282,7 +248,7 @@ class DiffusionModel(nn.Module):
         dev = self._device(*tensors)
         h = self._ensure_handle(dev, B, L, text.shape[1], S)
         with torch.cuda.device(dev):
-            call = _DeviceCall(dev, h)
+            call = DeviceCall(dev, h)
             yield call
             if slot is None:
                 for x in call.inputs:

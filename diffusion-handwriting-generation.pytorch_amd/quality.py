@@ -10,16 +10,36 @@ sets (include/dhw.h dhw_pairs_*), and ``sample_metrics`` is ``sa
 """
 from __future__ import annotations
 
-import ctypes as C
 import time
 import warnings
 
 import numpy as np
 
+from . import _call
+
 MOMENTS_MAX_N, MOMENTS_MAX_S, MOMENTS_MIN_D, MOMENTS_MAX_D = 16384, 64, 16, 2048   # csrc/moments/moments.h
 PAIRS_MAX_N, PAIRS_MAX_K = 16384, 8                                               # csrc/pairs/pairs.h
-_workspaces = {}   # device index -> workspace tensors of dhw_moments_update (vis._workspace)
-_pairs_workspaces = {}   # the same for dhw_pairs_*
+
+
+def _check_D(D) -> int:
+    if not _call.is_int(D) or D < MOMENTS_MIN_D or D > MOMENTS_MAX_D or D % 16:
+        raise ValueError(f"D = {D!r} must be a multiple of 16 in [{MOMENTS_MIN_D}, {MOMENTS_MAX_D}]")
+    return int(D)
+
+
+def _check_features(features, D: int):
+    """What ``FeatureStats.update`` and ``FeatureSet.update`` take -> (the features as a tensor [N,S,D] where they were, N, S)."""
+    import torch
+
+    x = features if isinstance(features, torch.Tensor) else torch.as_tensor(np.asarray(features))
+    if x.dim() == 2:
+        x = x.unsqueeze(1)
+    if x.dim() != 3 or x.shape[2] != D or not x.is_floating_point():
+        raise ValueError(f"features must be floating-point [N, S, {D}] or [N, {D}], got {tuple(x.shape)} {x.dtype}")
+    N, S = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= S <= MOMENTS_MAX_S:
+        raise ValueError(f"features hold S = {S} positions per sample, must be in [1, {MOMENTS_MAX_S}]")
+    return x, N, S
 
 
 class FeatureStats:
@@ -31,9 +51,7 @@ class FeatureStats:
     chunk = MOMENTS_MAX_N   # samples per dhw_moments_update call (at most MOMENTS_MAX_N)
 
     def __init__(self, D: int = 1280, device=None):
-        if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or D < MOMENTS_MIN_D or D > MOMENTS_MAX_D or D % 16:
-            raise ValueError(f"D = {D!r} must be a multiple of 16 in [{MOMENTS_MIN_D}, {MOMENTS_MAX_D}]")
-        self.D = int(D)
+        self.D = _check_D(D)
         self.device = device
         self.count = 0
         self._host = np.zeros(self.D + self.D * self.D, np.float64)
@@ -45,7 +63,7 @@ class FeatureStats:
         s, g = np.asarray(sum, np.float64), np.asarray(gram, np.float64)
         if s.ndim != 1 or g.shape != (s.shape[0], s.shape[0]):
             raise ValueError(f"sum must be [D] and gram [D, D], got {s.shape} and {g.shape}")
-        if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or count < 0:
+        if not _call.is_int(count) or count < 0:
             raise ValueError(f"count = {count!r} must be a non-negative integer")
         st = cls(s.shape[0], device)
         st.count = int(count)
@@ -57,38 +75,21 @@ class FeatureStats:
         """Add ``features``, [N,S,D] (pooled over S) or [N,D], a tensor on any device or an array."""
         import torch
 
-        x = features if isinstance(features, torch.Tensor) else torch.as_tensor(np.asarray(features))
-        if x.dim() == 2:
-            x = x.unsqueeze(1)
-        if x.dim() != 3 or x.shape[2] != self.D or not x.is_floating_point():
-            raise ValueError(f"features must be floating-point [N, S, {self.D}] or [N, {self.D}], got {tuple(x.shape)} {x.dtype}")
-        N, S = int(x.shape[0]), int(x.shape[1])
-        if not 1 <= S <= MOMENTS_MAX_S:
-            raise ValueError(f"features hold S = {S} positions per sample, must be in [1, {MOMENTS_MAX_S}]")
+        x, N, S = _check_features(features, self.D)
         if N == 0:
             return self
-        if not torch.cuda.is_available():
-            raise RuntimeError("FeatureStats.update needs an MI355X (HIP device): there is no CPU path in this package")
-        from . import _lib
-        from .vis import _workspace
-
-        if self._dev is None:
-            dev = torch.device(self.device) if self.device is not None else (x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device()))
-            self.device = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-            self._dev = torch.from_numpy(self._host).to(self.device)
-            self._host = None
-        dev, D, l = self.device, self.D, _lib.lib()
-        step = max(1, min(int(self.chunk), MOMENTS_MAX_N, (2 ** 31 - 1) // (S * D)))
-        with torch.cuda.device(dev):
-            x = x.detach().to(dev, torch.float32).contiguous()
-            st = torch.cuda.current_stream(dev)
+        with _call.open("FeatureStats.update", like=x, device=self.device, record=True) as c:   # (record: x may be the caller's own)
+            if self._dev is None:
+                self.device = c.dev
+                self._dev = torch.from_numpy(self._host).to(c.dev)
+                self._host = None
+            D = self.D
+            step = max(1, min(int(self.chunk), MOMENTS_MAX_N, (2 ** 31 - 1) // (S * D)))
+            x = c.to(x.detach())
             for lo in range(0, N, step):
                 n = min(step, N - lo)
-                need = int(l.dhw_moments_workspace_bytes(n, S, D))
-                ws = _workspace(_workspaces, dev, need)
-                _lib.check(l.dhw_moments_update(x[lo:lo + n].data_ptr(), n, S, D, self._dev.data_ptr(), self._dev[D:].data_ptr(), ws.data_ptr(),
-                                                need, C.c_void_p(st.cuda_stream)))
-            x.record_stream(st)
+                ws, need = c.workspace("moments", "dhw_moments_workspace_bytes", n, S, D)
+                c.run("dhw_moments_update", x[lo:lo + n].data_ptr(), n, S, D, self._dev.data_ptr(), self._dev[D:].data_ptr(), c.ptr(ws), need)
         self.count += N
         return self
 
@@ -166,9 +167,7 @@ class FeatureSet:
     so ``load`` / ``save`` / ``count`` / ``data`` need no device."""
 
     def __init__(self, D: int = 1280, device=None):
-        if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or D < MOMENTS_MIN_D or D > MOMENTS_MAX_D or D % 16:
-            raise ValueError(f"D = {D!r} must be a multiple of 16 in [{MOMENTS_MIN_D}, {MOMENTS_MAX_D}]")
-        self.D = int(D)
+        self.D = _check_D(D)
         self.device = device
         self.count = 0
         self._host = np.zeros((0, self.D), np.float64)
@@ -190,13 +189,10 @@ class FeatureSet:
 
     def _on_device(self):
         """The device buffer, created from the host rows at the first need of a device."""
-        import torch
-
         if self._dev is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("FeatureSet needs an MI355X (HIP device): there is no CPU path in this package")
-            dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
-            self.device = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+            import torch
+
+            self.device = _call.pick_device("FeatureSet", device=self.device)
             self._dev = torch.empty((max(256, self.count), self.D), dtype=torch.float64, device=self.device)
             self._dev[:self.count] = torch.from_numpy(self._host)
             self._host = None
@@ -219,14 +215,7 @@ class FeatureSet:
         """Append ``features``, [N,S,D] (pooled over S as ``FeatureStats.update`` pools) or [N,D], a tensor on any device or an array."""
         import torch
 
-        x = features if isinstance(features, torch.Tensor) else torch.as_tensor(np.asarray(features))
-        if x.dim() == 2:
-            x = x.unsqueeze(1)
-        if x.dim() != 3 or x.shape[2] != self.D or not x.is_floating_point():
-            raise ValueError(f"features must be floating-point [N, S, {self.D}] or [N, {self.D}], got {tuple(x.shape)} {x.dtype}")
-        N, S = int(x.shape[0]), int(x.shape[1])
-        if not 1 <= S <= MOMENTS_MAX_S:
-            raise ValueError(f"features hold S = {S} positions per sample, must be in [1, {MOMENTS_MAX_S}]")
+        x, N, S = _check_features(features, self.D)
         if N == 0:
             return self
         if self.count + N > PAIRS_MAX_N:
@@ -234,26 +223,19 @@ class FeatureSet:
         x = x.detach().to(torch.float32)
         if not x.is_cuda and not bool(torch.isfinite(x).all()):
             raise ValueError("features hold a non-finite value (NaN or infinite)")
-        if not torch.cuda.is_available():
-            raise RuntimeError("FeatureSet.update needs an MI355X (HIP device): there is no CPU path in this package")
-        from . import _lib
-
-        if self._dev is None and self.device is None and x.is_cuda:
-            self.device = x.device
-        self._on_device()
-        dev, D, l = self.device, self.D, _lib.lib()
-        step = max(1, min(MOMENTS_MAX_N, (2 ** 31 - 1) // (S * D)))
-        with torch.cuda.device(dev):
-            given_on_device = x.is_cuda
-            x = x.to(dev).contiguous()
+        with _call.open("FeatureSet.update", like=x, device=self.device, record=True) as c:   # (record: x may be the caller's own)
+            if self._dev is None:
+                self.device = c.dev
+                self._on_device()
+            given_on_device, D = x.is_cuda, self.D
+            step = max(1, min(MOMENTS_MAX_N, (2 ** 31 - 1) // (S * D)))
+            x = c.to(x)
             if given_on_device and not bool(torch.isfinite(x).all()):
                 raise ValueError("features hold a non-finite value (NaN or infinite)")
             buf = self._reserve(self.count + N)
-            st = torch.cuda.current_stream(dev)
             for lo in range(0, N, step):
                 n = min(step, N - lo)
-                _lib.check(l.dhw_pairs_pool(x[lo:lo + n].data_ptr(), n, S, D, buf[self.count + lo:].data_ptr(), C.c_void_p(st.cuda_stream)))
-            x.record_stream(st)
+                c.run("dhw_pairs_pool", x[lo:lo + n].data_ptr(), n, S, D, buf[self.count + lo:].data_ptr())
         self.count += N
         return self
 
@@ -278,7 +260,7 @@ class FeatureSet:
 
 
 def _check_k(k, rows: int):
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= PAIRS_MAX_K:
+    if not _call.is_int(k) or not 1 <= k <= PAIRS_MAX_K:
         raise ValueError(f"k = {k!r} must be an integer in [1, {PAIRS_MAX_K}]")
     if k >= rows:
         raise ValueError(f"k = {k} needs more than {k} rows in the set (it holds {rows})")
@@ -295,10 +277,10 @@ def _check_sets(*sets, least: int = 1):
 
 
 def _pairs(first, *others):
-    """(library, device, rows of every set on that device): the sets are brought to the first one's device."""
+    """(device, rows of every set on that device): the sets are brought to the first one's device.  The pairwise entries share
+    one cached workspace per device: calls on one device must be ordered on one stream."""
     import torch
 
-    from . import _lib
     x = first._on_device()[:first.count]
     dev = first.device
     rows = [x]
@@ -310,13 +292,7 @@ def _pairs(first, *others):
             raise ValueError(f"the sets live on different devices: {dev} and {s.device}")
         rows.append(r)
     assert all(r.is_contiguous() and r.dtype == torch.float64 for r in rows)
-    return _lib.lib(), dev, rows
-
-
-def _pairs_ws(l, dev, M: int, N: int, D: int):
-    from .vis import _workspace
-    need = int(l.dhw_pairs_workspace_bytes(M, N, D))
-    return _workspace(_pairs_workspaces, dev, need), need
+    return dev, rows
 
 
 def knn_radius(s: FeatureSet, k: int = 3):
@@ -324,15 +300,14 @@ def knn_radius(s: FeatureSet, k: int = 3):
     itself is left out by index, so a duplicated row has radius 0 at k = 1."""
     import torch
 
-    from . import _lib
     _check_sets(s)
     _check_k(k, s.count)
-    l, dev, (x,) = _pairs(s)
+    dev, (x,) = _pairs(s)
     N, D = s.count, s.D
-    with torch.cuda.device(dev):
-        out = torch.empty(N, dtype=torch.float64, device=dev)
-        ws, need = _pairs_ws(l, dev, N, N, D)
-        _lib.check(l.dhw_pairs_knn(x.data_ptr(), N, D, int(k), out.data_ptr(), ws.data_ptr(), need, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    with _call.open("FeatureSet", device=dev) as c:
+        out = c.empty(N, torch.float64)
+        ws, need = c.workspace("pairs", "dhw_pairs_workspace_bytes", N, N, D)
+        c.run("dhw_pairs_knn", x.data_ptr(), N, D, int(k), out.data_ptr(), c.ptr(ws), need)
     return out
 
 
@@ -340,17 +315,13 @@ def _cover(queries: FeatureSet, ref: FeatureSet, radius2=None):
     """(count [M] int32 or None, nearest2 [M] float64, nearest_idx [M] int32) of dhw_pairs_cover, device tensors."""
     import torch
 
-    from . import _lib
-    l, dev, (q, r) = _pairs(queries, ref)
+    dev, (q, r) = _pairs(queries, ref)
     M, N, D = queries.count, ref.count, ref.D
-    with torch.cuda.device(dev):
-        near = torch.empty(M, dtype=torch.float64, device=dev)
-        idx = torch.empty(M, dtype=torch.int32, device=dev)
-        count = None if radius2 is None else torch.empty(M, dtype=torch.int32, device=dev)
-        ws, need = _pairs_ws(l, dev, M, N, D)
-        _lib.check(l.dhw_pairs_cover(q.data_ptr(), M, r.data_ptr(), N, D, None if radius2 is None else radius2.data_ptr(),
-                                     None if count is None else count.data_ptr(), near.data_ptr(), idx.data_ptr(), ws.data_ptr(), need,
-                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    with _call.open("FeatureSet", device=dev) as c:
+        near, idx = c.empty(M, torch.float64), c.empty(M, torch.int32)
+        count = c.empty(M, torch.int32, wanted=radius2 is not None)
+        ws, need = c.workspace("pairs", "dhw_pairs_workspace_bytes", M, N, D)
+        c.run("dhw_pairs_cover", q.data_ptr(), M, r.data_ptr(), N, D, c.ptr(radius2), c.ptr(count), near.data_ptr(), idx.data_ptr(), c.ptr(ws), need)
     return count, near, idx
 
 
@@ -381,13 +352,11 @@ def precision_recall(real: FeatureSet, gen: FeatureSet, k: int = 3) -> dict:
 def _polysum(x: FeatureSet, y: FeatureSet, skip_diag: bool) -> float:
     import torch
 
-    from . import _lib
-    l, dev, (a, b) = _pairs(x, y)
-    with torch.cuda.device(dev):
-        out = torch.empty(2, dtype=torch.float64, device=dev)
-        ws, need = _pairs_ws(l, dev, x.count, y.count, x.D)
-        _lib.check(l.dhw_pairs_polysum(a.data_ptr(), x.count, b.data_ptr(), y.count, x.D, int(skip_diag), out.data_ptr(), ws.data_ptr(), need,
-                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    dev, (a, b) = _pairs(x, y)
+    with _call.open("FeatureSet", device=dev) as c:
+        out = c.empty(2, torch.float64)
+        ws, need = c.workspace("pairs", "dhw_pairs_workspace_bytes", x.count, y.count, x.D)
+        c.run("dhw_pairs_polysum", a.data_ptr(), x.count, b.data_ptr(), y.count, x.D, int(skip_diag), out.data_ptr(), c.ptr(ws), need)
         return float(out[0])
 
 
@@ -406,7 +375,7 @@ def line_features(strokes, extractor, lengths=None, batch: int = 32):
     import torch
 
     from .vis import render_strokes
-    if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
+    if not _call.is_int(batch) or batch < 1:
         raise ValueError(f"batch = {batch!r} must be a positive integer")
     N = int(strokes.shape[0])
     if lengths is not None and len(lengths) != N:
@@ -443,11 +412,11 @@ def _evaluate(who, model, data, extractor, n, batch, seed, real, real_set, with_
     for k in ("strokes", "text", "style"):
         if k not in data:
             raise ValueError(f"data must hold 'strokes', 'text' and 'style' (missing {k!r})")
-    if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
+    if not _call.is_int(batch) or batch < 1:
         raise ValueError(f"batch = {batch!r} must be a positive integer")
     total = int(data["strokes"].shape[0])
     n = total if n is None else n
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= total:
+    if not _call.is_int(n) or not 2 <= n <= total:
         raise ValueError(f"n = {n!r} must be an integer in [2, {total}] (the rows of data)")
     if real is not None and not isinstance(real, FeatureStats):
         raise ValueError("real must be a FeatureStats")
@@ -538,7 +507,7 @@ def sample_metrics(model, data, extractor, n=None, batch: int = 32, seed: int = 
     "dtw_nearest", the mean over generated rows of the distance to the nearest real line, with the index vector
     "dtw_nearest_idx" (a value near 0: the model copies that line); "dtw_self", the mean over generated rows of the distance to
     the nearest other generated line (a value near 0: the samples collapse onto one another).  Every other key is unchanged."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= PAIRS_MAX_K:
+    if not _call.is_int(k) or not 1 <= k <= PAIRS_MAX_K:
         raise ValueError(f"k = {k!r} must be an integer in [1, {PAIRS_MAX_K}]")
     stats, rows = real if isinstance(real, tuple) and len(real) == 2 else (None, real)
     if dtw and "strokes" in data:

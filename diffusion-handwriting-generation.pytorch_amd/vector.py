@@ -2,15 +2,14 @@
 made of them on the host."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from .vis import PAGE_MAX_L, PAGE_MAX_N, _check_page_count, _host_ints, _page_float, _page_int, _workspace, check_page_geometry
+from . import _call
+from .vis import check_page_geometry, check_page_lines, check_page_strokes
 
 PATHS_MAX_SMOOTH = PATHS_MAX_ROUNDS = 8   # csrc/paths/paths_host.h
-_paths_workspaces = {}                    # of stroke_paths: device index -> workspace tensors (vis._workspace)
 
 
 @dataclass
@@ -36,12 +35,12 @@ class StrokePaths:
 
 
 def _paths_options(smooth, tol, rounds):
-    smooth, rounds = _page_int("smooth", smooth, 0), _page_int("rounds", rounds, 0)
+    smooth, rounds = _call.check_int("smooth", smooth, 0), _call.check_int("rounds", rounds, 0)
     if smooth > PATHS_MAX_SMOOTH:
         raise ValueError(f"smooth = {smooth} must lie in [0, {PATHS_MAX_SMOOTH}]")
     if rounds > PATHS_MAX_ROUNDS:
         raise ValueError(f"rounds = {rounds} must lie in [0, {PATHS_MAX_ROUNDS}]")
-    tol = _page_float("tol", tol)
+    tol = _call.check_number("tol", tol)
     if tol < 0:
         raise ValueError(f"tol = {tol} must be >= 0")
     return smooth, tol, rounds
@@ -64,67 +63,19 @@ def stroke_paths(strokes, lengths=None, slots=None, *, pages=None, height: int =
     touched.  One workspace is cached per device: calls on one device must be ordered on one stream."""
     import torch
 
-    x = strokes if isinstance(strokes, torch.Tensor) else torch.as_tensor(np.asarray(strokes))
-    if x.dim() != 3 or x.shape[2] != 3:
-        raise ValueError(f"strokes must be [N, L, 3], got {tuple(x.shape)}")
-    if not x.is_floating_point():
-        raise ValueError(f"strokes must be floating-point, got {x.dtype}")
-    N, L = int(x.shape[0]), int(x.shape[1])
-    if not 1 <= N <= PAGE_MAX_N or not 1 <= L <= PAGE_MAX_L:
-        raise ValueError(f"strokes must be [N, L, 3] with N in [1, {PAGE_MAX_N}] and L in [1, {PAGE_MAX_L}], got {tuple(x.shape)}")
+    x, N, L = check_page_strokes(strokes)
     g = check_page_geometry(pages, height, width, lines_per_page, margin_left, margin_top, pitch, 2.0, scale)   # (no line width here)
     smooth, tol, rounds = _paths_options(smooth, tol, rounds)
-
-    def on_device(v):
-        return isinstance(v, torch.Tensor) and v.is_cuda
-
-    host_lens = host_slots = None
-    if lengths is not None:
-        if on_device(lengths):
-            if lengths.numel() != N:
-                raise ValueError(f"lengths must hold {N} entries, got {lengths.numel()}")
-        else:
-            host_lens = _host_ints("lengths", lengths, N)
-            if any(v < 1 or v > L for v in host_lens):
-                raise ValueError(f"lengths must be {N} integers in [1, {L}], got {host_lens}")
-    if slots is not None:
-        if on_device(slots):
-            if slots.numel() != N:
-                raise ValueError(f"slots must hold {N} entries, got {slots.numel()}")
-        else:
-            host_slots = _host_ints("slots", slots, N)
-    P = g["pages"]
-    if P is None:
-        lpp = g["lines_per_page"]
-        P = max(0, max(host_slots)) // lpp + 1 if host_slots is not None else -(-N // lpp)
-        _check_page_count(g, P)
-    if not torch.cuda.is_available():
-        raise RuntimeError("stroke_paths needs an MI355X (HIP device): there is no CPU path in this package")
-    from . import _lib
-
-    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    l = _lib.lib()
-    with torch.cuda.device(dev):
-        x = x.detach().to(dev, torch.float32).contiguous()
-
-        def ints(host, given):
-            if given is None:
-                return None
-            return torch.tensor(host, dtype=torch.int32).to(dev) if host is not None else given.to(dev, torch.int32).contiguous()
-
-        lens, slot_t = ints(host_lens, lengths), ints(host_slots, slots)
-        need = int(l.dhw_paths_workspace_bytes(N, L))
-        ws = _workspace(_paths_workspaces, dev, need)
-        points = torch.empty((N, L, 4), device=dev, dtype=torch.float32)
-        index = torch.empty((N, L, 2), device=dev, dtype=torch.int32)
-        counts = torch.empty((N, 2), device=dev, dtype=torch.int32)
-        scale_out = torch.empty((1,), device=dev, dtype=torch.float32)
-        boxes = torch.empty((N, 4), device=dev, dtype=torch.float32)
-        st = torch.cuda.current_stream(dev)
-        _lib.check(l.dhw_paths(x.data_ptr(), lens.data_ptr() if lens is not None else None, slot_t.data_ptr() if slot_t is not None else None,
-                               N, L, P, g["height"], g["width"], g["lines_per_page"], g["margin_left"], g["margin_top"], g["pitch"], g["scale"],
-                               smooth, tol, rounds, points.data_ptr(), index.data_ptr(), counts.data_ptr(), scale_out.data_ptr(),
-                               boxes.data_ptr(), ws.data_ptr(), need, C.c_void_p(st.cuda_stream)))
+    host_lens, host_slots, P = check_page_lines(lengths, slots, N, L, g)
+    with _call.open("stroke_paths", like=x) as c:
+        x = c.to(x.detach())
+        lens, slot_t = _call.stage_ints(c, host_lens, lengths), _call.stage_ints(c, host_slots, slots)
+        ws, need = c.workspace("paths", "dhw_paths_workspace_bytes", N, L)
+        points, index, counts = c.empty((N, L, 4)), c.empty((N, L, 2), torch.int32), c.empty((N, 2), torch.int32)
+        scale_out, boxes = c.empty((1,)), c.empty((N, 4))
+        c.run("dhw_paths", x.data_ptr(), c.ptr(lens), c.ptr(slot_t), N, L, P, g["height"], g["width"], g["lines_per_page"], g["margin_left"],
+              g["margin_top"], g["pitch"], g["scale"], smooth, tol, rounds, points.data_ptr(), index.data_ptr(), counts.data_ptr(),
+              scale_out.data_ptr(), boxes.data_ptr(), c.ptr(ws), need)
     return StrokePaths(points, index, counts, scale_out, boxes, host_slots if host_slots is not None else slot_t, P, g["height"], g["width"],
                        g["lines_per_page"], g["margin_left"], g["margin_top"], g["pitch"])
 
@@ -140,11 +91,11 @@ def page_svg(paths: StrokePaths, page: int, line_width: float = 2.0, curves: boo
     ``<path id="line{n}" fill="none" stroke="black" stroke-width=... stroke-linecap="round" stroke-linejoin="round">``.  Each
     polyline is ``M x y`` and then, per further point, ``C (P_k + t_k) (P_k+1 - t_k+1) P_k+1`` (``curves``) or ``L x y``.
     Numbers are written with ``precision`` decimals."""
-    page = _page_int("page", page, 0)
+    page = _call.check_int("page", page, 0)
     if page >= paths.pages:
         raise ValueError(f"page = {page} must be below the record's {paths.pages} pages")
-    precision = _page_int("precision", precision, 0)
-    line_width = _page_float("line_width", line_width)
+    precision = _call.check_int("precision", precision, 0)
+    line_width = _call.check_number("line_width", line_width)
     if not line_width > 0:
         raise ValueError(f"line_width = {line_width} must be > 0")
     counts, points, index = _host(paths.counts), _host(paths.points), _host(paths.index)

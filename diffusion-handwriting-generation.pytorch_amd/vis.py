@@ -1,30 +1,13 @@
 """Output side of the sampler (reference utils/vis.py:5-36): offsets -> pen positions -> polylines."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
+
+from . import _call, _lib
 
 RENDER_CHUNK = 256   # segments per LDS chunk of the raster kernel (csrc/render/render.h RENDER_CHUNK): a tile that keeps more
                      # than this many segments goes through several chunks
 RENDER_TILE_W = 32   # columns per raster tile (csrc/render/render.h RENDER_TILE_W)
-# device index -> [uint8 workspace tensors, the newest (largest) last]: one cache per call, so each keeps its own buffers
-_render_workspaces = {}   # of render_strokes
-_page_workspaces = {}     # of render_page
-
-
-def _workspace(cache: dict, dev, need: int):
-    """One workspace per device in `cache`, grown by doubling.  Outgrown buffers stay referenced (a captured graph may still
-    point at one): at most one per doubling, together smaller than the newest."""
-    import torch
-
-    bufs = cache.setdefault(dev.index, [])
-    if not bufs or bufs[-1].numel() < need:
-        size = 1 << 16
-        while size < need:
-            size *= 2
-        bufs.append(torch.empty(size, dtype=torch.uint8, device=dev))
-    return bufs[-1]
 
 
 def render_workspace_segments(device, B: int, L: int):
@@ -33,9 +16,8 @@ def render_workspace_segments(device, B: int, L: int):
     header[b,0]).  For tools that look at the cull (tools/bench_render.py)."""
     import torch
 
-    from . import _lib
     idx = torch.device(device).index
-    ws = _render_workspaces[torch.cuda.current_device() if idx is None else idx][-1].cpu().numpy()
+    ws = _call.newest_workspace("render", torch.cuda.current_device() if idx is None else idx).cpu().numpy()
     need = int(_lib.lib().dhw_render_workspace_bytes(B, L))
     hdr_bytes = need - B * L * 16
     return ws[:B * 8].view(np.int32).reshape(B, 2).copy(), ws[hdr_bytes:need].view(np.float32).reshape(B, L, 4).copy()
@@ -90,34 +72,21 @@ def render_strokes(strokes, lengths=None, height: int = 96, width: int = 1400, l
     x = strokes if isinstance(strokes, torch.Tensor) else torch.as_tensor(np.asarray(strokes))
     if x.dim() != 3 or x.shape[2] != 3:
         raise ValueError(f"strokes must be [B, L, 3], got {tuple(x.shape)}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("render_strokes needs an MI355X (HIP device): there is no CPU path in this package")
-    from . import _lib
-
     B, L = int(x.shape[0]), int(x.shape[1])
-    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    l = _lib.lib()
-    with torch.cuda.device(dev):
-        x = x.detach().to(dev, torch.float32).contiguous()
-        lens = None
-        if lengths is not None:
-            if isinstance(lengths, torch.Tensor) and lengths.is_cuda:   # stays on the device: no host read, no host check
-                lens = lengths.to(dev, torch.int32).contiguous()
-            else:
-                host = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-                if len(host) != B or any(v < 1 or v > L for v in host):
-                    raise ValueError(f"lengths must be {B} integers in [1, {L}], got {host}")
-                lens = torch.tensor(host, dtype=torch.int32).to(dev)
-            if lens.numel() != B:
-                raise ValueError(f"lengths must hold {B} entries")
-        need = int(l.dhw_render_workspace_bytes(B, L))
-        ws = _workspace(_render_workspaces, dev, need) if need else None
-        images = torch.empty((B, 1, int(height), int(width)), device=dev, dtype=torch.float32)
-        widths = torch.empty((B,), device=dev, dtype=torch.int32)
-        st = torch.cuda.current_stream(dev)
-        _lib.check(l.dhw_render(x.data_ptr(), lens.data_ptr() if lens is not None else None, B, L, int(height), int(width),
-                                float(line_width), images.data_ptr(), widths.data_ptr(), ws.data_ptr() if ws is not None else None,
-                                need, C.c_void_p(st.cuda_stream)))
+    with _call.open("render_strokes", like=x) as c:
+        x = c.to(x.detach())
+        host = None
+        if lengths is not None and not _call.on_device(lengths):   # (a device tensor stays there: no host read, no host check)
+            host = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]   # looser than host_ints: §48
+            if len(host) != B or any(v < 1 or v > L for v in host):
+                raise ValueError(f"lengths must be {B} integers in [1, {L}], got {host}")
+        lens = _call.stage_ints(c, host, lengths)
+        if lens is not None and lens.numel() != B:
+            raise ValueError(f"lengths must hold {B} entries")
+        ws, need = c.workspace("render", "dhw_render_workspace_bytes", B, L)
+        images, widths = c.empty((B, 1, int(height), int(width))), c.empty((B,), torch.int32)
+        c.run("dhw_render", x.data_ptr(), c.ptr(lens), B, L, int(height), int(width), float(line_width), images.data_ptr(),
+              widths.data_ptr(), c.ptr(ws), need)
     return images, widths
 
 
@@ -134,31 +103,14 @@ def save_line_png(image, width, name: str) -> None:
 PAGE_MAX_N = PAGE_MAX_L = 4096   # csrc/page/page_host.h
 
 
-def _page_int(name: str, v, lo: int) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name} = {v!r} is not an integer")
-    if v < lo:
-        raise ValueError(f"{name} = {v} must be >= {lo}")
-    return int(v)
-
-
-def _page_float(name: str, v) -> float:
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError(f"{name} = {v!r} is not a number")
-    v = float(np.float32(v))
-    if not np.isfinite(v):
-        raise ValueError(f"{name} = {v} must be finite")
-    return v
-
-
 def check_page_geometry(pages, height, width, lines_per_page, margin_left, margin_top, pitch, line_width, scale) -> dict:
     """The geometry rules of dhw_page (include/dhw.h) with ValueError, on the host: what render_page and write_page check
     before they touch a device.  ``pages`` may be None (decided later).  Returns the checked values."""
-    g = dict(pages=None if pages is None else _page_int("pages", pages, 1), height=_page_int("height", height, 8),
-             width=_page_int("width", width, 8), lines_per_page=_page_int("lines_per_page", lines_per_page, 1),
-             margin_left=_page_float("margin_left", margin_left), margin_top=_page_float("margin_top", margin_top),
-             pitch=_page_float("pitch", pitch), line_width=_page_float("line_width", line_width),
-             scale=0.0 if scale is None else _page_float("scale", scale))
+    i, f = _call.check_int, _call.check_number
+    g = dict(pages=None if pages is None else i("pages", pages, 1), height=i("height", height, 8), width=i("width", width, 8),
+             lines_per_page=i("lines_per_page", lines_per_page, 1), margin_left=f("margin_left", margin_left),
+             margin_top=f("margin_top", margin_top), pitch=f("pitch", pitch), line_width=f("line_width", line_width),
+             scale=0.0 if scale is None else f("scale", scale))
     if g["width"] % 4:
         raise ValueError(f"width = {g['width']} must be a multiple of 4")
     if not g["pitch"] > 0:
@@ -185,17 +137,45 @@ def _check_page_count(g: dict, pages) -> None:
         raise ValueError(f"pages x width (or height) is beyond the launch grid (pages {pages}, height {g['height']}, width {g['width']})")
 
 
-def _host_ints(name: str, v, N: int):
-    """A host list / array / CPU tensor of N integers -> list of int (ValueError otherwise)."""
-    host = v.tolist() if hasattr(v, "tolist") else list(v)
-    if len(host) != N:
-        raise ValueError(f"{name} must hold {N} entries, got {len(host)}")
-    for i, x in enumerate(host):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-            raise ValueError(f"{name}[{i}] = {x!r} is not an integer")
-        if not -2 ** 31 <= x < 2 ** 31:
-            raise ValueError(f"{name}[{i}] = {x} does not fit int32")
-    return [int(x) for x in host]
+def check_page_strokes(strokes):
+    """The strokes rule ``render_page`` and ``stroke_paths`` open with, on the host: (strokes as a tensor [N,L,3] where it was, N, L)."""
+    import torch
+
+    x = strokes if isinstance(strokes, torch.Tensor) else torch.as_tensor(np.asarray(strokes))
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise ValueError(f"strokes must be [N, L, 3], got {tuple(x.shape)}")
+    if not x.is_floating_point():
+        raise ValueError(f"strokes must be floating-point, got {x.dtype}")
+    N, L = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= N <= PAGE_MAX_N or not 1 <= L <= PAGE_MAX_L:
+        raise ValueError(f"strokes must be [N, L, 3] with N in [1, {PAGE_MAX_N}] and L in [1, {PAGE_MAX_L}], got {tuple(x.shape)}")
+    return x, N, L
+
+
+def check_page_lines(lengths, slots, N: int, L: int, g: dict):
+    """The rules of ``render_page`` and ``stroke_paths`` that follow the geometry ``g`` (check_page_geometry), on the host: (lengths,
+    slots as checked host lists (None: not given, or a device tensor, which is only counted), the pages P)."""
+    host_lens = host_slots = None
+    if lengths is not None:
+        if _call.on_device(lengths):
+            if lengths.numel() != N:
+                raise ValueError(f"lengths must hold {N} entries, got {lengths.numel()}")
+        else:
+            host_lens = _call.host_ints("lengths", lengths, N)
+            if any(v < 1 or v > L for v in host_lens):
+                raise ValueError(f"lengths must be {N} integers in [1, {L}], got {host_lens}")
+    if slots is not None:
+        if _call.on_device(slots):
+            if slots.numel() != N:
+                raise ValueError(f"slots must hold {N} entries, got {slots.numel()}")
+        else:
+            host_slots = _call.host_ints("slots", slots, N)
+    P = g["pages"]
+    if P is None:
+        lpp = g["lines_per_page"]
+        P = max(0, max(host_slots)) // lpp + 1 if host_slots is not None else -(-N // lpp)
+        _check_page_count(g, P)
+    return host_lens, host_slots, P
 
 
 def render_page(strokes, lengths=None, slots=None, *, pages=None, height: int = 1980, width: int = 1400, lines_per_page: int = 20,
@@ -213,66 +193,16 @@ def render_page(strokes, lengths=None, slots=None, *, pages=None, height: int = 
     Returns (pages f32 [P,1,height,width] grey levels 0..255, scale f32 [1], boxes f32 [N,4] = left, top, right, bottom of each
     line's ink in page pixels, zeros for a line that draws nothing), all on the GPU.  Every argument rule raises ValueError
     before a device is touched.  One workspace is cached per device: calls on one device must be ordered on one stream."""
-    import torch
-
-    x = strokes if isinstance(strokes, torch.Tensor) else torch.as_tensor(np.asarray(strokes))
-    if x.dim() != 3 or x.shape[2] != 3:
-        raise ValueError(f"strokes must be [N, L, 3], got {tuple(x.shape)}")
-    if not x.is_floating_point():
-        raise ValueError(f"strokes must be floating-point, got {x.dtype}")
-    N, L = int(x.shape[0]), int(x.shape[1])
-    if not 1 <= N <= PAGE_MAX_N or not 1 <= L <= PAGE_MAX_L:
-        raise ValueError(f"strokes must be [N, L, 3] with N in [1, {PAGE_MAX_N}] and L in [1, {PAGE_MAX_L}], got {tuple(x.shape)}")
+    x, N, L = check_page_strokes(strokes)
     g = check_page_geometry(pages, height, width, lines_per_page, margin_left, margin_top, pitch, line_width, scale)
-
-    def on_device(v):
-        return isinstance(v, torch.Tensor) and v.is_cuda
-
-    host_lens = host_slots = None
-    if lengths is not None:
-        if on_device(lengths):
-            if lengths.numel() != N:
-                raise ValueError(f"lengths must hold {N} entries, got {lengths.numel()}")
-        else:
-            host_lens = _host_ints("lengths", lengths, N)
-            if any(v < 1 or v > L for v in host_lens):
-                raise ValueError(f"lengths must be {N} integers in [1, {L}], got {host_lens}")
-    if slots is not None:
-        if on_device(slots):
-            if slots.numel() != N:
-                raise ValueError(f"slots must hold {N} entries, got {slots.numel()}")
-        else:
-            host_slots = _host_ints("slots", slots, N)
-    P = g["pages"]
-    if P is None:
-        lpp = g["lines_per_page"]
-        P = max(0, max(host_slots)) // lpp + 1 if host_slots is not None else -(-N // lpp)
-        _check_page_count(g, P)
-    if not torch.cuda.is_available():
-        raise RuntimeError("render_page needs an MI355X (HIP device): there is no CPU path in this package")
-    from . import _lib
-
-    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    l = _lib.lib()
-    with torch.cuda.device(dev):
-        x = x.detach().to(dev, torch.float32).contiguous()
-
-        def ints(host, given):
-            if given is None:
-                return None
-            return torch.tensor(host, dtype=torch.int32).to(dev) if host is not None else given.to(dev, torch.int32).contiguous()
-
-        lens, slot_t = ints(host_lens, lengths), ints(host_slots, slots)
-        need = int(l.dhw_page_workspace_bytes(N, L))
-        ws = _workspace(_page_workspaces, dev, need)
-        out = torch.empty((P, 1, g["height"], g["width"]), device=dev, dtype=torch.float32)
-        scale_out = torch.empty((1,), device=dev, dtype=torch.float32)
-        boxes = torch.empty((N, 4), device=dev, dtype=torch.float32)
-        st = torch.cuda.current_stream(dev)
-        _lib.check(l.dhw_page(x.data_ptr(), lens.data_ptr() if lens is not None else None, slot_t.data_ptr() if slot_t is not None else None,
-                              N, L, P, g["height"], g["width"], g["lines_per_page"], g["margin_left"], g["margin_top"], g["pitch"],
-                              g["line_width"], g["scale"], out.data_ptr(), scale_out.data_ptr(), boxes.data_ptr(), ws.data_ptr(), need,
-                              C.c_void_p(st.cuda_stream)))
+    host_lens, host_slots, P = check_page_lines(lengths, slots, N, L, g)
+    with _call.open("render_page", like=x) as c:
+        x = c.to(x.detach())
+        lens, slot_t = _call.stage_ints(c, host_lens, lengths), _call.stage_ints(c, host_slots, slots)
+        ws, need = c.workspace("page", "dhw_page_workspace_bytes", N, L)
+        out, scale_out, boxes = c.empty((P, 1, g["height"], g["width"])), c.empty((1,)), c.empty((N, 4))
+        c.run("dhw_page", x.data_ptr(), c.ptr(lens), c.ptr(slot_t), N, L, P, g["height"], g["width"], g["lines_per_page"], g["margin_left"],
+              g["margin_top"], g["pitch"], g["line_width"], g["scale"], out.data_ptr(), scale_out.data_ptr(), boxes.data_ptr(), c.ptr(ws), need)
     return out, scale_out, boxes
 
 
