@@ -89,6 +89,9 @@ SIGNATURES = {
     "dhw_paths_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "dhw_paths": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
                             C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "dhw_truth_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dhw_truth": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                            C.c_float, C.c_float, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "dhw_encode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "dhw_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, C.c_size_t, _P]),
     "dhw_prep_workspace_bytes": (C.c_size_t, [C.c_int]),

@@ -17,7 +17,8 @@ SOURCES = ["train/sgemm_f32.hip", "train/sgemm_bf16.hip", "train/sgemm_group.hip
            "render/dhw_render_api.cpp", "cond/dhw_cond_api.cpp", "score/dhw_score_api.cpp", "attnmap/dhw_attnmap_api.cpp", "sampler/weights.cpp", "sampler/workspace.cpp", "sampler/denoiser.cpp", "sampler/sample.cpp", "sampler/debug.cpp",
            "step/step.hip", "step/dhw_step_api.cpp", "page/page.hip", "page/dhw_page_api.cpp", "encode/encode.hip", "encode/dhw_encode_api.cpp",
            "prep/prep.hip", "prep/dhw_prep_api.cpp", "train/cond_drop.hip", "moments/moments.hip", "moments/dhw_moments_api.cpp",
-           "pairs/pairs.hip", "pairs/dhw_pairs_api.cpp", "dtw/dtw.hip", "dtw/dhw_dtw_api.cpp", "paths/paths.hip", "paths/dhw_paths_api.cpp"]
+           "pairs/pairs.hip", "pairs/dhw_pairs_api.cpp", "dtw/dtw.hip", "dtw/dhw_dtw_api.cpp", "paths/paths.hip", "paths/dhw_paths_api.cpp",
+           "truth/truth.hip", "truth/dhw_truth_api.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 # per-source additions.  dtw.hip: its loop is plain fp32 VALU; packed f32 instructions (v_pk_add_f32 / v_pk_mul_f32), which the SLP
 # vectoriser makes of neighbouring features, issue slower there than the two scalar ones they replace

@@ -1,5 +1,5 @@
 // host/error.h — the library's one global message slot, read through dhw_last_error(NULL): errors of calls that have no
-// handle (dhw_create, dhw_schedule, dhw_render, dhw_page, dhw_paths, dhw_encode, dhw_prep, dhw_moments_update).  The slot itself lives in dhw_api.cpp.
+// handle (dhw_create, dhw_schedule, dhw_render, dhw_page, dhw_paths, dhw_truth, dhw_encode, dhw_prep, dhw_moments_update).  The slot itself lives in dhw_api.cpp.
 #pragma once
 #include <cstdarg>
 

@@ -616,6 +616,32 @@ def align(model: DiffusionModel, strokes: torch.Tensor, text: torch.Tensor, styl
     return Alignment(mean, full, token_spans(full, text.shape[1]), lens, li)
 
 
+def align_monotone(alignment: Alignment, text: torch.Tensor) -> Alignment:
+    """``alignment`` read monotonically: the same ``mean``, with ``token`` replaced by ``truth.monotone_tokens`` (the best
+    non-decreasing token sequence under the map, decoded on the host) repeated to the L stroke rows, and ``spans`` recomputed, so
+    that every token's rows are one contiguous span and the spans are in text order.  ``text`` int [B,Lt] (0 = pad): line b has
+    as many tokens as it has non-zero ids.  ``align`` picks each row's token on its own; this is the reading to build word and
+    character boxes on (``truth.page_truth``)."""
+    from .truth import monotone_tokens
+
+    mean, token = alignment.mean, alignment.token
+    if not isinstance(mean, torch.Tensor) or mean.dim() != 3 or not isinstance(token, torch.Tensor) or token.dim() != 2:
+        raise ValueError("alignment must hold mean [B,Lq,Lt] and token [B,L] tensors")
+    B, Lq, Lt = mean.shape
+    if not isinstance(text, torch.Tensor) or tuple(text.shape) != (B, Lt) or text.dtype.is_floating_point or text.dtype == torch.bool:
+        raise ValueError(f"text must hold integer token ids [B, Lt] = [{B}, {Lt}]")
+    L = int(token.shape[1])
+    if token.shape[0] != B or L % Lq:
+        raise ValueError(f"alignment.token {tuple(token.shape)} does not go with mean {tuple(mean.shape)}")
+    n_tokens = [int(v) for v in (text != 0).sum(1).cpu().tolist()]
+    if min(n_tokens) < 1:
+        raise ValueError("every prompt needs at least one token")
+    rep = L // Lq
+    rows = None if alignment.lengths is None else [int(n) // rep for n in alignment.lengths]
+    full = monotone_tokens(mean, n_tokens, rows).to(token.device).repeat_interleave(rep, dim=1)
+    return Alignment(mean, full, token_spans(full, Lt), alignment.lengths, alignment.layer)
+
+
 def rewrite_mask(alignment: Alignment, tok_lo, tok_hi) -> torch.Tensor:
     """The ``keep`` mask [B,L] (bool) that rewrites tokens [tok_lo, tok_hi) of every line and pins the rest: True inside the
     sample's length where the row's token lies outside the range, False on the rows to rewrite and past the length — ready
@@ -955,6 +981,12 @@ def wrap_text(text: str, max_chars: int = 40):
     return lines, slots
 
 
+def _round_size(model: DiffusionModel, guided: bool = False) -> int:
+    """Lines per round of ``write_page`` and of the alignment of ``write_page_file``: the model's batch capacity, halved for a
+    guided round (one forward of twice its lines)."""
+    return max(1, int(model._cap["max_B"]) // (2 if guided else 1))
+
+
 def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, max_chars: int = 40, diffusion_mode: str = "new",
                T: int = 60, seed: int = 0, first_sample: int = 0, candidates: int = 1, levels=None, steps: int | None = None,
                guidance=None, order: int | None = None, pages=None, height: int = 1980, width: int = 1400, lines_per_page: int = 20, margin_left: float = 70.0,
@@ -993,7 +1025,7 @@ def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, 
         raise ValueError(f"style_vector must be [1,S,1280], got {tuple(sv.shape)}")
     _encode_batch("write_page", lines, sv)   # (an empty or untokenisable line is refused here, before the first round)
 
-    cap = max(1, int(model._cap["max_B"]) // (2 if guided else 1))
+    cap = _round_size(model, bool(guided))
     strokes = []
     for i0 in range(0, len(lines), cap):
         strokes += infer_batch(lines[i0:i0 + cap], sv, model, diffusion_mode=diffusion_mode, T=T, seed=seed,
@@ -1007,11 +1039,15 @@ def write_page(text: str, style_vector: torch.Tensor, model: DiffusionModel, *, 
 def write_page_file(text: str, source, config_path: str | None = None, checkpoint_path: str | None = None,
                     experiment_path: str | None = None, output: str = "result", diffusion_mode: str = "new", *,
                     precision: str = "bf16", seed: int = 0, style_weights: str | None = None, candidates: int = 1,
-                    steps: int | None = None, guidance=None, order: int | None = None, svg: bool = False, **page_kwargs) -> list:
+                    steps: int | None = None, guidance=None, order: int | None = None, svg: bool = False, truth: bool = False,
+                    truth_level: str = "word", truth_labels: bool = False, **page_kwargs) -> list:
     """``infer.py --page-file``: resolve config / checkpoint as ``infer_file`` does, ``write_page`` the text in the hand of
     ``source`` and save ``./<output>_p<k>.png`` per page (``vis.save_page_png``).  ``svg``: also ``./<output>_p<k>.svg``, the
     same lines as curves (``vector.stroke_paths`` with the same page arguments at its default smoothing and thinning,
-    ``vector.save_page_svg``).  Returns the list of [L_i,3] strokes."""
+    ``vector.save_page_svg``).  ``truth``: also ``./<output>_p<k>.json``, the box, stroke rows and text of every word
+    (``truth_level="char"``: character) of the page, and with ``truth_labels`` ``./<output>_p<k>_labels.npy``, which item every
+    ink pixel belongs to (``truth.page_truth`` with the very page arguments of the PNG, on one ``align`` + ``align_monotone`` per
+    round of lines; ``truth.save_page_truth``).  Returns the list of [L_i,3] strokes."""
     from .checkpoint import load_model
     from .vector import save_page_svg, stroke_paths
     from .vis import save_page_png
@@ -1019,6 +1055,8 @@ def write_page_file(text: str, source, config_path: str | None = None, checkpoin
     lines, _ = wrap_text(text, page_kwargs.get("max_chars", 40))
     if not lines:
         raise ValueError("write_page_file: the text holds no word")
+    if truth_level not in ("word", "char"):
+        raise ValueError(f"truth_level must be 'word' or 'char', got {truth_level!r}")
     candidates = _check_candidates(candidates)
     ddim = _ddim_kw(steps, order, guidance, candidates, 1)
     config_path, checkpoint_path = _resolve_experiment(config_path, checkpoint_path, experiment_path)
@@ -1029,12 +1067,30 @@ def write_page_file(text: str, source, config_path: str | None = None, checkpoin
     out = out.cpu()
     for k in range(out.shape[0]):
         save_page_png(out[k], f"{output}_p{k}")
-    if svg:
+    if svg or truth:
         _, slots = wrap_text(text, page_kwargs.get("max_chars", 40))
+        lens = [len(s) for s in strokes]
         geometry = {k: v for k, v in page_kwargs.items() if k in ("height", "width", "lines_per_page", "margin_left", "margin_top", "pitch", "scale")}
-        paths = stroke_paths(pad_strokes(strokes), [len(s) for s in strokes], slots, pages=int(out.shape[0]), **geometry)
+    if svg:
+        paths = stroke_paths(pad_strokes(strokes), lens, slots, pages=int(out.shape[0]), **geometry)
         for k in range(paths.pages):
             save_page_svg(paths, k, f"{output}_p{k}", line_width=page_kwargs.get("line_width", 2.0))
+    if truth:
+        from .truth import page_truth, save_page_truth
+
+        if "line_width" in page_kwargs:
+            geometry["line_width"] = page_kwargs["line_width"]
+        token = torch.full((len(lines), max(lens)), -1, dtype=torch.int32)
+        cap = _round_size(model)
+        for i0 in range(0, len(lines), cap):   # one align + align_monotone per round of lines
+            txt, _, sv = _encode_batch("write_page_file", lines[i0:i0 + cap], style)
+            st = torch.from_numpy(pad_strokes(strokes[i0:i0 + cap]))
+            al = align_monotone(align(model, st, txt, sv, lengths=lens[i0:i0 + cap]), txt)
+            token[i0:i0 + cap, :al.token.shape[1]] = al.token.cpu()
+        rec = page_truth(pad_strokes(strokes), token, lines, lens, slots, level=truth_level, labels=bool(truth_labels), pages=int(out.shape[0]),
+                         **geometry)
+        for k in range(rec.pages):
+            save_page_truth(rec, k, f"{output}_p{k}")
     return strokes
 
 

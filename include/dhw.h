@@ -546,6 +546,59 @@ int dhw_paths(const float* strokes,      /* device f32 [N,L,3]                  
               float* boxes_out,          /* device f32 [N,4]                                               */
               void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Page ground truth: where every group of stroke rows (a word, a character) sits on the pages of dhw_page, which rows it
+ * spans, and, when asked, a per-pixel map of the group whose ink is nearest.  No handle: errors are read through
+ * dhw_last_error(NULL).  The call allocates nothing, synchronises nothing, never reads lens, slots or groups on the host and
+ * can be captured into a graph; at most three launches, one fewer when labels_out is NULL and one fewer when scale > 0.  All
+ * argument checks run before the first HIP call (DHW_ERR_ARG names the argument): N, L, P, H, W, lines_per_page,
+ * margin_left, margin_top, pitch, line_width, scale and strokes by dhw_page's rules; 1 <= G <= 256; non-NULL groups /
+ * boxes_out / spans_out / scale_out / workspace; labels_out (which may be NULL) and workspace 16-byte aligned, every other
+ * pointer 4-byte aligned; workspace_bytes >= dhw_truth_workspace_bytes(N, L, G) (0 for an N, L or G outside the ranges).
+ *
+ * Line n, with lens[n] (L when lens is NULL) strokes and slot[n] = slots[n] (n when slots is NULL):
+ *    1. Rules 1.-5. of dhw_render and 6.-9. of dhw_page, unchanged: pos = the prefix sums (in the line rasteriser's summation
+ *       order: the positions have the raster's bits), lift, last, segment i is drawn iff 1 <= i < last and !lift[i],
+ *       (xmin, xmax, ymin, ymax)_n = the box of the endpoints of drawn segments, which lines take part, ex_n, ey_n and s_n,
+ *       the shared s (scale when scale > 0), the page slot[n] / lines_per_page and top_n = margin_top + (slot[n] %
+ *       lines_per_page) pitch.  A device-side lens entry outside [1, L] is clamped to [0, L].
+ *    2. Segment i runs from pos[i-1] to pos[i] and belongs to group g = groups[n,i].  A segment with g outside [0, G) is
+ *       unassigned: it is ink, but belongs to no group.  groups[n,i] of a row that is not drawn is never read.
+ *    3. The box of group g in stroke units: (gxmin, gxmax, gymin, gymax) = min / max over the endpoints of the drawn segments
+ *       of the group.  Placement, fp32, every difference, product and sum one operation in the order written, none fused
+ *       (rule 4 of dhw_paths):  oy = top_n + (pitch - ey_n s) 0.5;  left = margin_left + (gxmin - xmin_n) s;  right =
+ *       margin_left + (gxmax - xmin_n) s;  top = oy + (ymax_n - gymax) s;  bottom = oy + (ymax_n - gymin) s.
+ *       boxes_out[n,g] = (left, top, right, bottom).
+ *    4. spans_out[n,g] = (first drawn row of the group, its last drawn row + 1, its number of drawn segments).  The rows
+ *       between the first and the last need not all be the group's: groups may interleave.
+ *    5. A group without a drawn segment, and every group of a line that takes no part, has zeros in both outputs.
+ *    6. scale_out[0] = s.
+ *    7. labels_out, when not NULL.  Pixel centres, the placement of the segments and the squared distance d2 from a centre to
+ *       a segment are those of rule 12 of dhw_page, in the same tile-relative fp32 arithmetic.  Drawn segment i of line n has
+ *       id = 1 + n G + g, or id = 0 when unassigned.  Pixel (r, c) of page p takes the id of the lexicographic minimum of
+ *       (d2, id) over ALL drawn segments of the lines of that page, if sqrt(d2) < line_width/2 + 0.5 (exactly where dhw_page's
+ *       coverage is above 0); otherwise 0.  Ink outside the page is clipped.  The lexicographic minimum is exact, commutative
+ *       and associative: the map is bit-deterministic and independent of the order in which segments, chunks and lines are
+ *       visited.  A pixel whose nearest point of the ink is a joint shared by two groups is at the same distance from both in
+ *       exact arithmetic: there the fp32 rounding of the two distances decides, and only where they round to the same float
+ *       does the smaller id win.  Such pixels form a wedge behind every joint between two groups; they are not rare.
+ *    8. No global atomics and no float atomics.  The per-group min / max are integer min / max in LDS on an order-preserving
+ *       integer image of the float, which is exact and commutative: the same call gives the same bits; line n inside any
+ *       batch has the boxes and spans of line n alone (N = 1, the same slot, scale = the batch's s); boxes and spans do not
+ *       depend on the order of the lines (the ids in the label map, 1 + n G + g, do by their definition). */
+size_t dhw_truth_workspace_bytes(int N, int L, int G);
+int dhw_truth(const float* strokes,      /* device f32 [N,L,3]                                             */
+              const int32_t* lens,       /* DEVICE int32 [N] or NULL, any 1 <= n <= L                      */
+              const int32_t* slots,      /* DEVICE int32 [N] or NULL (slot[n] = n)                         */
+              const int32_t* groups,     /* DEVICE int32 [N,L]: the group of stroke row i of line n        */
+              int N, int L, int G, int P, int H, int W, int lines_per_page,
+              float margin_left, float margin_top, float pitch,      /* page pixels                        */
+              float line_width, float scale,                         /* scale 0: automatic                 */
+              float* boxes_out,          /* device f32 [N,G,4] = (left, top, right, bottom), page pixels   */
+              int32_t* spans_out,        /* device i32 [N,G,3] = (first row, last row + 1, drawn segments) */
+              int32_t* labels_out,       /* device i32 [P,1,H,W] or NULL                                   */
+              float* scale_out,          /* device f32 [1]                                                 */
+              void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Stroke encoder: raw pen trajectories (tablet points grouped into pen-down strokes, the IAM-OnDB lineStrokes data) -> the
  * model's (dx, dy, pen) rows, normalised and thinned as the reference's parse_strokes_xml + combine_strokes + pad_stroke_seq
  * prepare the training corpus.  No handle: errors are read through dhw_last_error(NULL).  The call allocates nothing,

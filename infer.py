@@ -43,7 +43,13 @@ A whole text as pages (word-wrapped, every line at the same scale, composed on t
 
 The pages as curves too (<output>_p<k>.svg next to each PNG: for pen plotters, print at any size, drawing programs):
 
-    python infer.py --page-file letter.txt style.npy --experiment-path data/best_exp --output letter --svg"""
+    python infer.py --page-file letter.txt style.npy --experiment-path data/best_exp --output letter --svg
+
+Ground truth for the pages (<output>_p<k>.json next to each PNG: the box, stroke rows and text of every word; for training
+recognition, word-spotting and layout models; --truth-level char: every character; --truth-labels: also <output>_p<k>_labels.npy,
+the item every ink pixel belongs to):
+
+    python infer.py --page-file letter.txt style.npy --experiment-path data/best_exp --output letter --truth"""
 import argparse
 
 import dhg_amd
@@ -81,9 +87,17 @@ def main(argv=None):
     ap.add_argument("--page-file", metavar="TXT", help="a text to write as pages: wrapped to lines, every line sampled, all lines composed on the "
                                                        "GPU at one shared scale into <output>_p<k>.png (a blank line leaves a gap)")
     ap.add_argument("--svg", action="store_true", help="with --page-file: also write every page as curves to <output>_p<k>.svg")
+    ap.add_argument("--truth", action="store_true", help="with --page-file: also write every page's word boxes, stroke rows and text to "
+                                                         "<output>_p<k>.json")
+    ap.add_argument("--truth-level", default=None, choices=("word", "char"), help="with --truth: boxes of words (default) or of characters")
+    ap.add_argument("--truth-labels", action="store_true", help="with --truth: also the per-pixel map of item ids, <output>_p<k>_labels.npy")
     a = ap.parse_args(argv)
     if a.svg and not a.page_file:
         ap.error("--svg writes pages as curves: it needs --page-file")
+    if a.truth and not a.page_file:
+        ap.error("--truth writes the ground truth of pages: it needs --page-file")
+    if (a.truth_level or a.truth_labels) and not a.truth:
+        ap.error("--truth-level and --truth-labels say what --truth writes: pass --truth")
     if a.page_file and (a.score or a.align or a.restyle):
         ap.error("--page-file writes a text: it goes with neither --score, --align nor --restyle")
     if a.page_file and a.prompts_file:
@@ -156,9 +170,11 @@ def main(argv=None):
         if not text.split():
             ap.error(f"{a.page_file} holds no word")
         out = dhg_amd.write_page_file(text, source, a.config_path, a.checkpoint_path, a.experiment_path, a.output, a.diffusion_mode,
-                                      precision=a.precision, seed=a.seed, style_weights=a.style_weights, **cand, **(dict(svg=True) if a.svg else {}))
+                                      precision=a.precision, seed=a.seed, style_weights=a.style_weights, **cand, **(dict(svg=True) if a.svg else {}),
+                                      **(dict(truth=True, truth_level=a.truth_level or "word", truth_labels=a.truth_labels) if a.truth else {}))
         save(out)
-        print(f"{len(out)} lines -> ./{a.output}_p<k>.png" + (f" and ./{a.output}_p<k>.svg" if a.svg else ""))
+        print(f"{len(out)} lines -> ./{a.output}_p<k>.png" + (f" and ./{a.output}_p<k>.svg" if a.svg else "")
+              + (f" and ./{a.output}_p<k>.json" if a.truth else ""))
         return
     if a.prompts_file:
         if a.prompt is not None and a.source is not None:
